@@ -8,6 +8,10 @@ traced samples).  Prints ONE JSON line on rank 0.  See DESIGN.md "Measurement".
   python bench.py --gpus N --steps K --warmup W          (N > 1 without a torchrun environment: spawns the N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...
 
+A plain run sets up, burns in, warms up, times the K steps and prints the headline.  Everything else the line can carry
+(per-class HIP-event profiling and the roofline, run-to-run repeats, CPU baselines, the other single-GPU BASELINE shapes)
+runs only with --full.  --dump-outputs DIR writes what the timed region computed (see dump_outputs).
+
 Other BASELINE.json configurations (parity-test cases; their lines are kept under profiles/):
   --config fhn_noiseless | sir      --solver quasi-newton      --splitting gaussian
 """
@@ -74,11 +78,20 @@ def parse():
                          "C-ABI collective (chmc_comm_unique_id on rank 0, the 128-byte id broadcast through torch.distributed, "
                          "chmc_comm_init, chmc_gather_samples = ncclAllGather between device buffers)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run (configs[1], one GPU) only: skip the short legs of the other single-GPU BASELINE shapes "
+                    help="--full default run (configs[1], one GPU) only: skip the short legs of the other single-GPU BASELINE shapes "
                          "that follow the headline's timed region (config.other_configs)")
     ap.add_argument("--repeats", type=int, default=3,
                     help="the timed region is repeated this many times AFTER the official one (same K steps each) for the "
                          "run-to-run spread (config.value_repeats); `value` is always the first, official region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: HIP-event profiling of the warm-up and of the "
+                         "dominant kernel class in the timed region (roofline, config.kernel_classes_warmup), the --repeats "
+                         "regions, the CPU baselines and the other single-GPU BASELINE shapes.  The options that tune these "
+                         "legs (--no-cpu-baseline, --no-profile, --profile-stride, --cpu-steps, --cpu-autodiff-baseline, "
+                         "--no-other-configs, --repeats) only act with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region write what its last step computed as DIR/<name>.npy (float64; arrays "
+                         "larger than 2^21 elements as a fixed, seeded sample of their flattened elements)")
     return ap.parse_args()
 
 
@@ -106,8 +119,8 @@ def run_other_configs(a):
     import subprocess
     out = {}
     for name, extra in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-other-configs", "--steps", "32",
-               "--warmup", "16", "--repeats", "0"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-other-configs", "--steps",
+               "32", "--warmup", "16", "--repeats", "0"] + extra
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
@@ -257,6 +270,31 @@ def _finite(o):
     return o
 
 
+DUMP_MAX_ELEMS = 1 << 21  # per array: 16 MB of float64, so the whole dump stays well under 64 MB
+
+
+def dump_outputs(out_dir, ctx, last, samples):
+    """--dump-outputs: what the timed region computed, as a caller of the trajectory path receives it, written as
+    out_dir/<name>.npy in float64 (rank 0's chains).  `last` is the result of the timed region's last batched call (per
+    chain: status, iteration counts, reversibility error, steps done); q, p, x_obs_seq, partition and the Hamiltonian
+    are the state the chains hold after it; `samples` is the timed region's gather of traced variables over all ranks.
+    Arrays of more than DUMP_MAX_ELEMS elements are replaced by a fixed sample of their flattened elements (seed 0,
+    in index order), so two runs with the same arguments, or two builds, compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    q, p, xo, part = ctx.get_state()
+    arrays = {"q": q, "p": p, "x_obs_seq": xo, "partition": np.array([part]), "hamiltonian": ctx.hamiltonian()}
+    if samples is not None:
+        arrays["samples"] = samples
+    for k, v in (last or {}).items():
+        arrays["last_" + k] = v
+    for name, v in arrays.items():
+        v = np.asarray(v, dtype=np.float64)
+        if v.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, DUMP_MAX_ELEMS, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def lib_sha256():
     from manifold_mcmc_for_diffusions_amd import _lib
     h = hashlib.sha256()
@@ -400,23 +438,29 @@ def main():
                                       iters_ok=int((r["iters_fwd"] + r["iters_bwd"])[on & (r["status"] == 0)].sum()),
                                       steps_clean=int(r["n_done"][on & (r["status"] == 0)].sum())))
                 run_steps.act &= (r["status"] == 0).astype(np.int32)
+            run_steps.last = r
             k += m
             done += m
         run_steps.k = k
 
     run_steps.k = 0
-    # warm-up steps double as the full per-class profiling pass (HIP events around every launch perturb the host
-    # side, so the timed region only records events for the dominant kernel class found here)
-    L.chmc_profile_enable(1)
+    run_steps.last = None
+    # --full: the warm-up steps double as the full per-class profiling pass (HIP events around every launch perturb
+    # the host side, so the timed region only records events for the dominant kernel class found here)
+    if a.full:
+        L.chmc_profile_enable(1)
     run_steps(a.warmup)
     ms_w = np.zeros(10)
     nl_w = np.zeros(10, dtype=np.int64)
-    L.chmc_profile_get(ms_w.ctypes.data_as(_lib.dp), nl_w.ctypes.data_as(C.POINTER(C.c_longlong)))
-    dom = int(np.argmax(ms_w)) if a.warmup > 0 else 1
+    dom = 1
+    if a.full:
+        L.chmc_profile_get(ms_w.ctypes.data_as(_lib.dp), nl_w.ctypes.data_as(C.POINTER(C.c_longlong)))
+        dom = int(np.argmax(ms_w)) if a.warmup > 0 else 1
     D.barrier()
     sync()
-    L.chmc_profile_enable(0 if a.no_profile else (1 << dom if dom > 0 else 1))
-    L.chmc_profile_stride(a.profile_stride)  # events around every n-th launch of the dominant kernel
+    if a.full:
+        L.chmc_profile_enable(0 if a.no_profile else (1 << dom if dom > 0 else 1))
+        L.chmc_profile_stride(a.profile_stride)  # events around every n-th launch of the dominant kernel
     stats = []
     qd = torch.empty((B, ctx.Q), dtype=torch.float64, device=dev)  # gather staging
 
@@ -459,13 +503,16 @@ def main():
         print(f"[rank {rank}] steps {t_steps * 1e3:.1f} ms, gather + sync {(elapsed - t_steps) * 1e3:.1f} ms", file=sys.stderr)
     ms = np.zeros(10)
     nl = np.zeros(10, dtype=np.int64)
-    L.chmc_profile_get(ms.ctypes.data_as(_lib.dp), nl.ctypes.data_as(C.POINTER(C.c_longlong)))
-    L.chmc_profile_enable(0)
-    L.chmc_profile_stride(1)
+    if a.full:
+        L.chmc_profile_get(ms.ctypes.data_as(_lib.dp), nl.ctypes.data_as(C.POINTER(C.c_longlong)))
+        L.chmc_profile_enable(0)
+        L.chmc_profile_stride(1)
     counters_after = ctx.counters()["projection_iterations"]
-    # run-to-run spread: the same region again (K steps + gather, no HIP events), after the official one
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, ctx, run_steps.last, samples)
+    # --full, run-to-run spread: the same region again (K steps + gather, no HIP events), after the official one
     rep_local = []
-    for _ in range(max(a.repeats, 0)):
+    for _ in range(max(a.repeats, 0) if a.full else 0):
         st_r = []
         D.barrier()
         sync()
@@ -496,116 +543,6 @@ def main():
         # as work done and end that chain's trajectory"); with every step succeeding this is chains x steps
         total_steps = float(agg[1])
         value = total_steps / t_max
-        cm = class_model(ctx, wl, model, wl.solver["newton"])
-        # measured HBM bytes per launch of every class (two separate rocprofv3 --pmc passes, tools/pmc_summary.py);
-        # only quoted when the file was produced by THIS build of the library
-        traffic_all, traffic_note = {}, "profiles/traffic.json absent"
-        tf = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tf) and not emu:
-            try:
-                tj = json.load(open(tf))
-                key = config_key(a.config, S, B)
-                sect = tj.get("configs", {}).get(key)
-                switches = sorted(k for k in os.environ if k.startswith("CHMC_") and k not in (
-                    "CHMC_BENCH_DEVICE", "CHMC_BENCH_VERBOSE", "CHMC_HIP_LIBRARY", "CHMC_DIST_BACKEND"))
-                if tj.get("_lib_sha256") != lib_sha256():
-                    traffic_note = "profiles/traffic.json is from another build of the library: not quoted"
-                elif switches:  # (the counters were taken with the default kernel choices)
-                    traffic_note = f"environment switches {switches} select other kernels than the profiled defaults: not quoted"
-                elif wl.solver["newton"] is False or gaussian or sect is None:
-                    traffic_note = f"profiles/traffic.json holds no counters for this workload ({key}): not quoted"
-                else:
-                    traffic_all = sect
-                    traffic_note = f"profiles/traffic.json [{key}] ({sect.get('_command', 'rocprofv3 --pmc passes')}), same library build"
-            except Exception as e:  # noqa: BLE001
-                traffic_note = f"profiles/traffic.json unreadable ({e})"
-        # chains one launch processes: the Newton-loop kernels are masked per chain, so the later iterations of a solve
-        # (and the one speculatively enqueued iteration that finds every chain converged) touch only the chains still
-        # active.  For newton_blk the (chain, iteration) pairs of the timed region are known exactly from the
-        # per-chain iteration counters; the other classes run over every chain.
-        name = _lib.KERNEL_CLASSES[dom]
-        avg_ms = ms[dom] / max(nl[dom], 1) if nl[dom] else float("nan")
-        launches_all = nl[dom] * a.profile_stride
-        pairs = iters_all  # (chain, Newton iteration) pairs of the timed region
-        if name == "newton_blk" and nl[dom]:
-            chains_per_launch = pairs / launches_all
-        elif name in ("update", "constr", "solve_chain", "sym_blk") and nl[dom]:
-            # one masked launch per Newton / quasi-Newton iteration (the chains still iterating) plus the launches
-            # that run over every chain (state evaluation, momentum projections)
-            full = max(launches_all - float(counters_after - iters_before), 0.0)
-            chains_per_launch = (pairs + B * full) / launches_all
-        else:
-            chains_per_launch = float(B)
-        mdl = cm.get(name, dict(bytes=8.0 * 3 * ctx.Q, flops=2.0 * ctx.Q))
-        traffic = traffic_all.get(name)
-        alg_bytes = mdl["bytes"] * chains_per_launch          # SURVEY.md 8(d) operator-level bytes of the launch's chains
-        hbm_bytes = mdl.get("hbm_bytes", mdl["bytes"]) * chains_per_launch  # what the fused kernel has to move
-        alg_flops = mdl["flops"] * chains_per_launch
-        sec = avg_ms * 1e-3
-        # HARDWARE fractions of the dominant class: HBM (counter bytes when profiles/traffic.json belongs to this build,
-        # otherwise the bytes the kernel has to move) and fp64 vector flops; `frac` is the larger of the two and `bound`
-        # names it.  The builder-measured latency floor of the forward scan is a secondary figure, not `frac`.
-        hbm_frac_alg = hbm_bytes / sec / 1e9 / HBM_PEAK_GBS if sec > 0 else None
-        hbm_frac_cnt = (traffic / sec / 1e9 / HBM_PEAK_GBS) if (traffic and sec > 0) else None
-        fp64_frac = alg_flops / sec / 1e12 / FP64_VALU_PEAK_TFLOPS if sec > 0 else None
-        hbm_frac = hbm_frac_cnt if hbm_frac_cnt is not None else hbm_frac_alg
-        if (fp64_frac or 0.0) > (hbm_frac or 0.0):
-            bound, achieved, peak, unit, frac = "fp64_valu", alg_flops / sec / 1e12, FP64_VALU_PEAK_TFLOPS, "TFLOP/s", fp64_frac
-        else:
-            bound, achieved, peak, unit, frac = ("hbm", (traffic if hbm_frac_cnt is not None else hbm_bytes) / sec / 1e9,
-                                                 HBM_PEAK_GBS, "GB/s", hbm_frac)
-        roofline = {
-            "bound": bound, "kernel": name, "achieved": achieved, "peak": peak, "unit": unit, "frac": frac, "traffic": traffic,
-            "hbm_frac_counters": hbm_frac_cnt, "hbm_frac_bytes_to_move": hbm_frac_alg, "fp64_valu_frac": fp64_frac,
-            "traffic_source": traffic_note,
-            "algorithmic_flops_per_launch": alg_flops, "algorithmic_bytes_per_launch": alg_bytes,
-            "bytes_to_move_per_launch": hbm_bytes,
-            "operator_level_byte_rate_GBs_not_a_utilisation": alg_bytes / sec / 1e9 if sec > 0 else None,
-            "chains_per_launch": chains_per_launch, "avg_launch_ms": avg_ms, "launches_timed": int(nl[dom]),
-            "timed_every": a.profile_stride,
-            "note": "frac = the larger HARDWARE fraction of the dominant kernel class: HBM bytes of the launch (rocprofv3 "
-                    "FETCH/WRITE counters from profiles/traffic.json when that file was produced by this build, else the "
-                    "bytes the fused kernel has to move) / HIP-event launch time / 8 TB/s, or algorithmic fp64 flops "
-                    "(SURVEY.md 8d) / time / 78.6 TFLOP/s.  `operator_level_byte_rate...` prices SURVEY.md 8(d)'s unfused "
-                    "operator decomposition and may exceed the HBM peak: it is a throughput figure, never a utilisation.",
-        }
-        if name == "constr":
-            # secondary: the sequential recursion's dependent-instruction latency floor (tools/ubench/fwd_latency.hip,
-            # output kept in profiles/r03_fwd_latency_ubench.txt: 36 ns per FitzHugh-Nagumo step at one wavefront per SIMD)
-            steps = max(b["nsteps"] for b in ctx.blocks[ctx.partition])
-            roofline["sequential_steps_per_launch"] = steps
-            roofline["Msteps_per_s_per_lane"] = steps / sec / 1e6 if sec > 0 else None
-            if model == "fhn":
-                roofline["latency_floor_frac"] = steps * 36e-9 / sec if sec > 0 else None
-                roofline["latency_floor_source"] = "profiles/r03_fwd_latency_ubench.txt (36 ns per step)"
-            roofline["note"] += ("  The forward scans keep B x K lanes = a few dozen wavefronts busy with a sequential "
-                                 "nonlinear recursion, so neither HBM nor the vector pipes are the limit; "
-                                 "`latency_floor_frac` = steps x 36 ns / launch time is the builder-measured ceiling.")
-        # the whole step attributed: every class with its time, binding resource and fraction of that resource's peak
-        table = {}
-        for i, k in enumerate(_lib.KERNEL_CLASSES):
-            if not nl_w[i]:
-                continue
-            per_launch = ms_w[i] / nl_w[i]
-            row = {"ms_per_step": round(ms_w[i] / max(a.warmup, 1), 3), "ms_per_launch": round(per_launch, 4),
-                   "launches_per_step": round(nl_w[i] / max(a.warmup, 1), 1), "bound": BOUND.get(k, "latency")}
-            if k in cm:
-                row["compulsory_bytes_per_chain"] = cm[k]["bytes"]
-                if "hbm_bytes" in cm[k]:
-                    row["hbm_bytes_per_chain"] = cm[k]["hbm_bytes"]
-                if BOUND.get(k) == "hbm" and k != "update":  # (update launches are masked: chains per launch unknown here)
-                    row["frac_of_hbm_peak"] = round(cm[k].get("hbm_bytes", cm[k]["bytes"]) * B / (per_launch * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)
-                if BOUND.get(k) == "fp64_valu" and k not in ("newton_blk", "constr"):
-                    row["frac_of_fp64_peak"] = round(cm[k]["flops"] * B / (per_launch * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS, 3)
-            if traffic_all.get(k):
-                row["counter_bytes_per_launch"] = traffic_all[k]
-                row["hbm_traffic_frac"] = round(traffic_all[k] / (per_launch * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)
-            table[k] = row
-        # whole step against HBM: sum over classes of counter bytes per launch x launches per step / time / 8 TB/s
-        whole_bytes = whole_frac = None
-        if traffic_all:
-            whole_bytes = float(sum(traffic_all[k] * table[k]["launches_per_step"] for k in table if traffic_all.get(k)))
-            whole_frac = whole_bytes / (t_max / a.steps) / 1e9 / HBM_PEAK_GBS
         rounds_per_step = (counters_after - iters_before) / max(a.steps, 1)
         out = {
             "metric": METRIC, "value": value, "unit": "steps/s", "n_gpus": world, "steps": a.steps,
@@ -620,7 +557,6 @@ def main():
                 # (`value` counts chain-steps ATTEMPTED -- a chain whose step fails ends its trajectory, SURVEY 8d;
                 # rounds 1-2 quoted chains x steps / time, which is this figure)
                 "nominal_steps_per_s": world * B * a.steps / t_max,
-                "value_repeats": repeats,
                 "parallelism": f"chains x{world} (no data-path collective, 1 gather)",
                 "ranks_joined": int(agg[3]), "per_rank_ms": None if per_rank is None else [round(float(x), 2) for x in per_rank[:, 0]],
                 "mean_newton_iters_fwd_plus_bwd": k_mean, "step_success_rate": float(agg[0] / agg[1]),
@@ -630,8 +566,6 @@ def main():
                 # those bytes; the figure can exceed the 8 TB/s peak)
                 "operator_level_byte_rate_GBs_not_a_utilisation":
                     wl.bytes_per_chain_step(k_mean, newton=wl.solver["newton"]) * value / 1e9 / world,
-                "whole_step_counter_bytes": whole_bytes, "whole_step_hbm_frac": whole_frac,
-                "launches_per_step": round(float(sum(nl_w)) / max(a.warmup, 1), 1),
                 "newton_rounds_per_step": rounds_per_step,
                 "collective_backend": D.backend_name(), "collective_world_size": D.world_size(),
                 "collective_route": ("C ABI: chmc_comm_init + chmc_gather_samples (ncclAllGather), RCCL communicator reports "
@@ -639,22 +573,135 @@ def main():
                                     else "torch.distributed gather",
                 "cabi_comm_world_size": None if cabi_info is None else cabi_info[0],
                 "overlap_halves": int(os.environ.get("CHMC_HALVES", "-1")),
-                "kernel_classes_warmup": table,
             },
-            "roofline": roofline,
         }
-        if world == 1 and not a.no_cpu_baseline:
-            q, p, xo, part = ctx.get_state()
-            n_cpu = a.cpu_steps if a.cpu_steps is not None else (250 if model == "fhn" and S >= 400 else 400)
-            out["cpu_baseline"] = cpu_baseline(wl, model, q, p, xo, part, step_size, n_cpu, wl.solver, gaussian)
-            out["config"]["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
-            if a.cpu_autodiff_baseline:
-                out["cpu_baseline"]["autodiff_restatement_S50"] = cpu_autodiff_baseline()
-            elif a.config == "fhn_noisy" and not a.no_other_configs:  # (the default line: a bounded sample of baseline (ii))
-                out["cpu_baseline"]["autodiff_restatement_S50_T20"] = cpu_autodiff_baseline(20)
-        if world == 1 and a.config == "fhn_noisy" and not a.no_other_configs and not emu and wl.solver["newton"] \
-                and not gaussian and B == 256 and S == 400:
-            out["config"]["other_configs"] = run_other_configs(a)
+        if a.full:
+            cm = class_model(ctx, wl, model, wl.solver["newton"])
+            # measured HBM bytes per launch of every class (two separate rocprofv3 --pmc passes, tools/pmc_summary.py);
+            # only quoted when the file was produced by THIS build of the library
+            traffic_all, traffic_note = {}, "profiles/traffic.json absent"
+            tf = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tf) and not emu:
+                try:
+                    tj = json.load(open(tf))
+                    key = config_key(a.config, S, B)
+                    sect = tj.get("configs", {}).get(key)
+                    switches = sorted(k for k in os.environ if k.startswith("CHMC_") and k not in (
+                        "CHMC_BENCH_DEVICE", "CHMC_BENCH_VERBOSE", "CHMC_HIP_LIBRARY", "CHMC_DIST_BACKEND"))
+                    if tj.get("_lib_sha256") != lib_sha256():
+                        traffic_note = "profiles/traffic.json is from another build of the library: not quoted"
+                    elif switches:  # (the counters were taken with the default kernel choices)
+                        traffic_note = f"environment switches {switches} select other kernels than the profiled defaults: not quoted"
+                    elif wl.solver["newton"] is False or gaussian or sect is None:
+                        traffic_note = f"profiles/traffic.json holds no counters for this workload ({key}): not quoted"
+                    else:
+                        traffic_all = sect
+                        traffic_note = f"profiles/traffic.json [{key}] ({sect.get('_command', 'rocprofv3 --pmc passes')}), same library build"
+                except Exception as e:  # noqa: BLE001
+                    traffic_note = f"profiles/traffic.json unreadable ({e})"
+            # chains one launch processes: the Newton-loop kernels are masked per chain, so the later iterations of a solve
+            # (and the one speculatively enqueued iteration that finds every chain converged) touch only the chains still
+            # active.  For newton_blk the (chain, iteration) pairs of the timed region are known exactly from the
+            # per-chain iteration counters; the other classes run over every chain.
+            name = _lib.KERNEL_CLASSES[dom]
+            avg_ms = ms[dom] / max(nl[dom], 1) if nl[dom] else float("nan")
+            launches_all = nl[dom] * a.profile_stride
+            pairs = iters_all  # (chain, Newton iteration) pairs of the timed region
+            if name == "newton_blk" and nl[dom]:
+                chains_per_launch = pairs / launches_all
+            elif name in ("update", "constr", "solve_chain", "sym_blk") and nl[dom]:
+                # one masked launch per Newton / quasi-Newton iteration (the chains still iterating) plus the launches
+                # that run over every chain (state evaluation, momentum projections)
+                full = max(launches_all - float(counters_after - iters_before), 0.0)
+                chains_per_launch = (pairs + B * full) / launches_all
+            else:
+                chains_per_launch = float(B)
+            mdl = cm.get(name, dict(bytes=8.0 * 3 * ctx.Q, flops=2.0 * ctx.Q))
+            traffic = traffic_all.get(name)
+            alg_bytes = mdl["bytes"] * chains_per_launch          # SURVEY.md 8(d) operator-level bytes of the launch's chains
+            hbm_bytes = mdl.get("hbm_bytes", mdl["bytes"]) * chains_per_launch  # what the fused kernel has to move
+            alg_flops = mdl["flops"] * chains_per_launch
+            sec = avg_ms * 1e-3
+            # HARDWARE fractions of the dominant class: HBM (counter bytes when profiles/traffic.json belongs to this build,
+            # otherwise the bytes the kernel has to move) and fp64 vector flops; `frac` is the larger of the two and `bound`
+            # names it.  The builder-measured latency floor of the forward scan is a secondary figure, not `frac`.
+            hbm_frac_alg = hbm_bytes / sec / 1e9 / HBM_PEAK_GBS if sec > 0 else None
+            hbm_frac_cnt = (traffic / sec / 1e9 / HBM_PEAK_GBS) if (traffic and sec > 0) else None
+            fp64_frac = alg_flops / sec / 1e12 / FP64_VALU_PEAK_TFLOPS if sec > 0 else None
+            hbm_frac = hbm_frac_cnt if hbm_frac_cnt is not None else hbm_frac_alg
+            if (fp64_frac or 0.0) > (hbm_frac or 0.0):
+                bound, achieved, peak, unit, frac = "fp64_valu", alg_flops / sec / 1e12, FP64_VALU_PEAK_TFLOPS, "TFLOP/s", fp64_frac
+            else:
+                bound, achieved, peak, unit, frac = ("hbm", (traffic if hbm_frac_cnt is not None else hbm_bytes) / sec / 1e9,
+                                                     HBM_PEAK_GBS, "GB/s", hbm_frac)
+            roofline = {
+                "bound": bound, "kernel": name, "achieved": achieved, "peak": peak, "unit": unit, "frac": frac, "traffic": traffic,
+                "hbm_frac_counters": hbm_frac_cnt, "hbm_frac_bytes_to_move": hbm_frac_alg, "fp64_valu_frac": fp64_frac,
+                "traffic_source": traffic_note,
+                "algorithmic_flops_per_launch": alg_flops, "algorithmic_bytes_per_launch": alg_bytes,
+                "bytes_to_move_per_launch": hbm_bytes,
+                "operator_level_byte_rate_GBs_not_a_utilisation": alg_bytes / sec / 1e9 if sec > 0 else None,
+                "chains_per_launch": chains_per_launch, "avg_launch_ms": avg_ms, "launches_timed": int(nl[dom]),
+                "timed_every": a.profile_stride,
+                "note": "frac = the larger HARDWARE fraction of the dominant kernel class: HBM bytes of the launch (rocprofv3 "
+                        "FETCH/WRITE counters from profiles/traffic.json when that file was produced by this build, else the "
+                        "bytes the fused kernel has to move) / HIP-event launch time / 8 TB/s, or algorithmic fp64 flops "
+                        "(SURVEY.md 8d) / time / 78.6 TFLOP/s.  `operator_level_byte_rate...` prices SURVEY.md 8(d)'s unfused "
+                        "operator decomposition and may exceed the HBM peak: it is a throughput figure, never a utilisation.",
+            }
+            if name == "constr":
+                # secondary: the sequential recursion's dependent-instruction latency floor (tools/ubench/fwd_latency.hip,
+                # output kept in profiles/r03_fwd_latency_ubench.txt: 36 ns per FitzHugh-Nagumo step at one wavefront per SIMD)
+                steps = max(b["nsteps"] for b in ctx.blocks[ctx.partition])
+                roofline["sequential_steps_per_launch"] = steps
+                roofline["Msteps_per_s_per_lane"] = steps / sec / 1e6 if sec > 0 else None
+                if model == "fhn":
+                    roofline["latency_floor_frac"] = steps * 36e-9 / sec if sec > 0 else None
+                    roofline["latency_floor_source"] = "profiles/r03_fwd_latency_ubench.txt (36 ns per step)"
+                roofline["note"] += ("  The forward scans keep B x K lanes = a few dozen wavefronts busy with a sequential "
+                                     "nonlinear recursion, so neither HBM nor the vector pipes are the limit; "
+                                     "`latency_floor_frac` = steps x 36 ns / launch time is the builder-measured ceiling.")
+            # the whole step attributed: every class with its time, binding resource and fraction of that resource's peak
+            table = {}
+            for i, k in enumerate(_lib.KERNEL_CLASSES):
+                if not nl_w[i]:
+                    continue
+                per_launch = ms_w[i] / nl_w[i]
+                row = {"ms_per_step": round(ms_w[i] / max(a.warmup, 1), 3), "ms_per_launch": round(per_launch, 4),
+                       "launches_per_step": round(nl_w[i] / max(a.warmup, 1), 1), "bound": BOUND.get(k, "latency")}
+                if k in cm:
+                    row["compulsory_bytes_per_chain"] = cm[k]["bytes"]
+                    if "hbm_bytes" in cm[k]:
+                        row["hbm_bytes_per_chain"] = cm[k]["hbm_bytes"]
+                    if BOUND.get(k) == "hbm" and k != "update":  # (update launches are masked: chains per launch unknown here)
+                        row["frac_of_hbm_peak"] = round(cm[k].get("hbm_bytes", cm[k]["bytes"]) * B / (per_launch * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)
+                    if BOUND.get(k) == "fp64_valu" and k not in ("newton_blk", "constr"):
+                        row["frac_of_fp64_peak"] = round(cm[k]["flops"] * B / (per_launch * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS, 3)
+                if traffic_all.get(k):
+                    row["counter_bytes_per_launch"] = traffic_all[k]
+                    row["hbm_traffic_frac"] = round(traffic_all[k] / (per_launch * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)
+                table[k] = row
+            # whole step against HBM: sum over classes of counter bytes per launch x launches per step / time / 8 TB/s
+            whole_bytes = whole_frac = None
+            if traffic_all:
+                whole_bytes = float(sum(traffic_all[k] * table[k]["launches_per_step"] for k in table if traffic_all.get(k)))
+                whole_frac = whole_bytes / (t_max / a.steps) / 1e9 / HBM_PEAK_GBS
+            out["config"].update({
+                "value_repeats": repeats, "whole_step_counter_bytes": whole_bytes, "whole_step_hbm_frac": whole_frac,
+                "launches_per_step": round(float(sum(nl_w)) / max(a.warmup, 1), 1), "kernel_classes_warmup": table})
+            out["roofline"] = roofline
+            if world == 1 and not a.no_cpu_baseline:
+                q, p, xo, part = ctx.get_state()
+                n_cpu = a.cpu_steps if a.cpu_steps is not None else (250 if model == "fhn" and S >= 400 else 400)
+                out["cpu_baseline"] = cpu_baseline(wl, model, q, p, xo, part, step_size, n_cpu, wl.solver, gaussian)
+                out["config"]["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
+                if a.cpu_autodiff_baseline:
+                    out["cpu_baseline"]["autodiff_restatement_S50"] = cpu_autodiff_baseline()
+                elif a.config == "fhn_noisy" and not a.no_other_configs:  # (the --full default line: a bounded sample of baseline (ii))
+                    out["cpu_baseline"]["autodiff_restatement_S50_T20"] = cpu_autodiff_baseline(20)
+            if world == 1 and a.config == "fhn_noisy" and not a.no_other_configs and not emu and wl.solver["newton"] \
+                    and not gaussian and B == 256 and S == 400:
+                out["config"]["other_configs"] = run_other_configs(a)
         print(json.dumps(_finite(out)), flush=True)
     D.barrier()
     ctx.close()

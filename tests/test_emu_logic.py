@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 EMU = os.path.join(HERE, "emu", "libchmc_emu.so")
 
 
-@pytest.fixture(scope="module")
+@pytest.fixture  # per test: a GPU test later in the same module must get the real library back
 def emu_lib():
     from manifold_mcmc_for_diffusions_amd import _lib
     srcs = [os.path.join(HERE, "emu", f) for f in ("chmc_emu.cpp", "backend_emu.h")]

@@ -5,8 +5,8 @@ R=$PWD
 TAG=${1:-ab}; SW=${2:-CHMC_NO_FIX_IN_JW=1}; shift; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; rm -rf $O/*
 for rep in 1 2 3; do
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs "$@" > $O/default_$rep.json 2> $O/e.log || tail -3 $O/e.log
-  env $SW timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs "$@" > $O/switch_$rep.json 2> $O/e.log || tail -3 $O/e.log
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs "$@" > $O/default_$rep.json 2> $O/e.log || tail -3 $O/e.log
+  env $SW timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs "$@" > $O/switch_$rep.json 2> $O/e.log || tail -3 $O/e.log
 done
 O=$O python - <<'PY'
 import glob, json, os

@@ -5,8 +5,8 @@ R=$PWD
 TAG=${1:-ab}; VAR=${2:-flip}; shift; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; rm -rf $O/*
 for rep in 1 2 3; do
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs "$@" > $O/shipped_$rep.json 2> $O/e.log || tail -3 $O/e.log
-  CHMC_HIP_LIBRARY=$R/build/libchmc_$VAR.so timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs "$@" > $O/${VAR}_$rep.json 2> $O/e.log || tail -3 $O/e.log
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs "$@" > $O/shipped_$rep.json 2> $O/e.log || tail -3 $O/e.log
+  CHMC_HIP_LIBRARY=$R/build/libchmc_$VAR.so timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs "$@" > $O/${VAR}_$rep.json 2> $O/e.log || tail -3 $O/e.log
 done
 O=$O python - <<'PY'
 import glob, json, os

@@ -5,7 +5,7 @@ O=$R/gpurun_out/${1:-r04n}; mkdir -p $O; rm -rf $O/*
 timeout -k 10 900 python -m pytest tests -m gpu -x -q -k "sir or Sir or shard or adam or per_chain or trajector or parallel" > $O/pytest.log 2>&1 || { tail -60 $O/pytest.log; exit 1; }
 tail -2 $O/pytest.log
 for b in 256 512 1024; do
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs --config sir --chains-per-gpu $b > $O/bench_sir_${b}.json 2> $O/e1.log || tail -5 $O/e1.log
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs --config sir --chains-per-gpu $b > $O/bench_sir_${b}.json 2> $O/e1.log || tail -5 $O/e1.log
 done
 O=$O python - <<'PY'
 import glob, json, os

@@ -8,7 +8,7 @@ for lib in default d6 d8; do
   for h in 1 2; do
     for shape in "" "--num-steps-per-obs 800 --chains-per-gpu 512"; do
       tag=${lib}_h${h}_$( [ -z "$shape" ] && echo s400 || echo s800 )
-      env ${L:+CHMC_HIP_LIBRARY=$L} $( [ $h = 2 ] && echo CHMC_HALVES=2 ) timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs $shape > $O/$tag.json 2> $O/e.log || tail -3 $O/e.log
+      env ${L:+CHMC_HIP_LIBRARY=$L} $( [ $h = 2 ] && echo CHMC_HALVES=2 ) timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs $shape > $O/$tag.json 2> $O/e.log || tail -3 $O/e.log
     done
   done
 done

@@ -4,8 +4,8 @@ O=$R/gpurun_out/r04i; mkdir -p $O; rm -rf $O/*
 timeout -k 10 900 python -m pytest tests -m gpu -x -q -k "sir or Sir or parallel or shard or adam or row_split or other_baseline or trajector or per_chain" > $O/pytest_sir.log 2>&1 || { tail -60 $O/pytest_sir.log; exit 1; }
 tail -2 $O/pytest_sir.log
 for b in 256 1024; do
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs --config sir --chains-per-gpu $b > $O/bench_sir_$b.json 2> $O/e1.log || tail -5 $O/e1.log
-  CHMC_RETRACT_KERNEL=0 timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs --config sir --chains-per-gpu $b > $O/bench_sir_${b}_batched.json 2> $O/e1.log || tail -5 $O/e1.log
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs --config sir --chains-per-gpu $b > $O/bench_sir_$b.json 2> $O/e1.log || tail -5 $O/e1.log
+  CHMC_RETRACT_KERNEL=0 timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs --config sir --chains-per-gpu $b > $O/bench_sir_${b}_batched.json 2> $O/e1.log || tail -5 $O/e1.log
 done
 python - <<'PY'
 import glob, json

@@ -6,7 +6,7 @@ timeout -k 10 600 python -m pytest tests -m gpu -x -q -k "per_chain_kernels or a
 tail -2 $O/pytest.log
 for b in 256 512 1024 2048; do
   for k in 1 2 0; do
-    CHMC_RETRACT_KERNEL=$k timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs --config sir --chains-per-gpu $b > $O/bench_sir_${b}_k$k.json 2> $O/e1.log || tail -5 $O/e1.log
+    CHMC_RETRACT_KERNEL=$k timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs --config sir --chains-per-gpu $b > $O/bench_sir_${b}_k$k.json 2> $O/e1.log || tail -5 $O/e1.log
   done
 done
 O=$O python - <<'PY'
