@@ -68,19 +68,60 @@ def subseq_shapes(num_obs, num_steps_per_obs, num_obs_per_subseq):
 
 
 class IdentityMetric:
-    """Stand-in for mici.matrices.IdentityMatrix (only the identity metric is restated)."""
+    """Stand-in for mici.matrices.IdentityMatrix."""
+
+    def inv_matmul(self, vct):
+        return vct
+
+    def sqrt_matmul(self, vct):
+        return vct
+
+
+class BlockDiagonalMetric:
+    """Stand-in for mici.matrices.PositiveDefiniteBlockDiagonalMatrix((DensePositiveDefiniteMatrix(M_0),
+    IdentityMatrix())): the only non-identity metric the reference accepts (sde/mici_extensions.py:305-315).
+    `inv_matmul` is `metric.inv @ vct`, `sqrt_matmul` is `metric.sqrt @ vct` (lower Cholesky factor of M_0 on
+    the leading block, as mici's DensePositiveDefiniteMatrix.sqrt), `log_abs_det_0` is `metric.blocks[0].log_abs_det`."""
+
+    def __init__(self, M_0):
+        self.M_0 = onp.array(M_0, dtype=onp.float64)
+        assert self.M_0.ndim == 2 and self.M_0.shape[0] == self.M_0.shape[1]
+        self.dim_0 = self.M_0.shape[0]
+        self.chol_0 = onp.linalg.cholesky(self.M_0)
+        self.inv_0 = onp.linalg.inv(self.M_0)
+        self.log_abs_det_0 = 2.0 * float(onp.log(onp.diag(self.chol_0)).sum())
+
+    def inv_matmul(self, vct):
+        vct = onp.asarray(vct, dtype=onp.float64)
+        return onp.concatenate([self.inv_0 @ vct[:self.dim_0], vct[self.dim_0:]])
+
+    def sqrt_matmul(self, vct):
+        vct = onp.asarray(vct, dtype=onp.float64)
+        return onp.concatenate([self.chol_0 @ vct[:self.dim_0], vct[self.dim_0:]])
 
 
 class ConditionedDiffusionConstrainedSystem:
-    """sde/mici_extensions.py:208-1259 (identity metric only; M_0 != I is out of scope)."""
+    """sde/mici_extensions.py:208-1259.  `metric`: None / IdentityMetric, or BlockDiagonalMetric(M_0) for
+    metric = blockdiag(M_0, I) on the u part (:279-315; not with Gaussian splitting, :293-300)."""
 
     def __init__(self, obs_interval, num_steps_per_obs, num_obs_per_subseq, y_seq, dim_u, dim_x, dim_v,
                  forward_func, generate_x_0, generate_z, obs_func, generate_σ=None,
                  use_gaussian_splitting=False, metric=None, dim_v_0=None):
-        if metric is not None and not isinstance(metric, IdentityMetric):
-            raise NotImplementedError("oracle restates the identity-metric paths only")
+        if use_gaussian_splitting and metric is not None and not isinstance(metric, IdentityMetric):  # :293-300
+            raise ValueError("Only identity matrix metric can be used with Gaussian splitting")
+        elif metric is None:
+            metric = IdentityMetric()
         self.use_gaussian_splitting = use_gaussian_splitting
-        self.metric = IdentityMetric()
+        self.metric = metric
+        if isinstance(metric, IdentityMetric):  # :305-315
+            log_det_sqrt_metric_0 = 0.0
+        elif isinstance(metric, BlockDiagonalMetric):
+            if metric.dim_0 != dim_u:
+                raise ValueError("M_0 must be dim_u x dim_u")
+            log_det_sqrt_metric_0 = metric.log_abs_det_0 / 2
+        else:
+            raise NotImplementedError(
+                "Only identity and block diagonal metrics with identity lower right block currently supported.")
         y_seq = onp.asarray(y_seq, dtype=onp.float64)
         num_obs, dim_y = y_seq.shape
         δ = float(obs_interval) / num_steps_per_obs
@@ -254,7 +295,14 @@ class ConditionedDiffusionConstrainedSystem:
             return tuple(dc_du_blocks), tuple(dc_dv_blocks), dc_dn_blocks
 
         def get_M_0_matrix():  # :794-798
-            return torch.eye(dim_u, dtype=DT)
+            if isinstance(metric, IdentityMetric):
+                return torch.eye(dim_u, dtype=DT)
+            return T(metric.M_0)
+
+        def metric_inv(delta_mu):  # blocks[0].inv @ delta_mu[:dim_u], blocks[1].inv @ delta_mu[dim_u:] (:1033-1041, :1105-1113)
+            if isinstance(metric, IdentityMetric):
+                return delta_mu
+            return torch.cat([T(metric.inv_0) @ delta_mu[:dim_u], delta_mu[dim_u:]])
 
         def compute_D_blocks(dc_dv_l_blocks, dc_dn_l_blocks, dc_dv_r_blocks, dc_dn_r_blocks):  # :765-792
             D_blocks = [torch.einsum("...ij,...kj->...ik", l, r) for l, r in zip(dc_dv_l_blocks, dc_dv_r_blocks)]
@@ -290,7 +338,7 @@ class ConditionedDiffusionConstrainedSystem:
 
         def log_det_sqrt_gram_from_chol(chol_C, chol_D_blocks):  # :800-810
             return (sum(torch.log(torch.abs(torch.diagonal(ch, 0, -2, -1))).sum() for ch in chol_D_blocks)
-                    + torch.log(torch.abs(torch.diagonal(chol_C))).sum() - 0.0)
+                    + torch.log(torch.abs(torch.diagonal(chol_C))).sum() - log_det_sqrt_metric_0)
 
         def log_det_sqrt_gram(q, x_obs_seq, partition=0):  # :812-820
             jac_blocks = jacob_constr_blocks(q, x_obs_seq, partition)
@@ -384,7 +432,7 @@ class ConditionedDiffusionConstrainedSystem:
                 c = constr(q, x_obs_seq, partition)
                 error = float(norm(c))
                 delta_mu = rmult_by_jacob_constr(*jac_prev, lmult_by_inv_gram(*jac_prev, *chol_prev, c))
-                delta_q = delta_mu
+                delta_q = metric_inv(delta_mu)
                 return q - delta_q, mu + delta_mu, float(norm(delta_q)), error
 
             q, mu, i, ndq, err = _loop(q, body, constraint_tol, position_tol, divergence_tol, max_iters)
@@ -399,7 +447,7 @@ class ConditionedDiffusionConstrainedSystem:
                 error = float(norm(c))
                 delta_mu = rmult_by_jacob_constr(
                     *jac_prev, lmult_by_inv_jacob_product(*jac_curr, *jac_prev, *lus, c))
-                delta_q = delta_mu
+                delta_q = metric_inv(delta_mu)
                 return q - delta_q, mu + delta_mu, float(norm(delta_q)), error
 
             q, mu, i, ndq, err = _loop(q, body, constraint_tol, position_tol, divergence_tol, max_iters)
@@ -488,13 +536,15 @@ class ConditionedDiffusionConstrainedSystem:
     def h2(self, state):  # :1198-1202
         if self.use_gaussian_splitting:
             return 0.5 * state.pos @ state.pos + 0.5 * state.mom @ state.mom
-        return 0.5 * state.mom @ state.mom
+        return 0.5 * state.mom @ self.metric.inv_matmul(state.mom)
 
     def h(self, state):
         return self.h1(state) + self.h2(state)
 
     def dh2_dmom(self, state):  # :1204-1208
-        return state.mom
+        if self.use_gaussian_splitting:
+            return state.mom
+        return self.metric.inv_matmul(state.mom)
 
     def h1_flow(self, state, dt):  # mici System.h1_flow: mom -= dt * dh1_dpos
         state.mom = state.mom - dt * self.dh1_dpos(state)
@@ -508,7 +558,8 @@ class ConditionedDiffusionConstrainedSystem:
         else:
             state.pos = state.pos + dt * self.dh2_dmom(state)
 
-    def dh2_flow_dmom(self, dt):  # :1233-1238 (scalars standing for scalar * IdentityMatrix)
+    def dh2_flow_dmom(self, dt):  # :1233-1238 (scalars standing for scalar * IdentityMatrix; the first entry is
+        # dt * metric.inv, which no caller restated here uses: both solvers take the second entry only)
         if self.use_gaussian_splitting:
             return onp.sin(dt), onp.cos(dt)
         return dt, 1.0
@@ -517,14 +568,14 @@ class ConditionedDiffusionConstrainedSystem:
         state.x_obs_seq = self._generate_x_obs_seq(T(state.pos)).numpy()
 
     def normal_space_component(self, state, vct):  # :1243-1250
-        return self._normal_space_component(T(vct), self.jacob_constr_blocks(state),
+        return self._normal_space_component(T(self.metric.inv_matmul(vct)), self.jacob_constr_blocks(state),
                                             self.chol_gram_blocks(state)).numpy()
 
     def project_onto_cotangent_space(self, mom, state):  # :1252-1254
         return mom - self.normal_space_component(state, mom)
 
     def sample_momentum(self, state, rng):  # :1256-1259
-        mom = rng.standard_normal(state.pos.shape)
+        mom = self.metric.sqrt_matmul(rng.standard_normal(state.pos.shape))
         return self.project_onto_cotangent_space(mom, state)
 
 
@@ -596,7 +647,7 @@ def jitted_solve_projection_onto_manifold_quasi_newton(state, state_prev, dt, sy
         T(state.pos), T(state.x_obs_seq), state.partition, jac_prev, chol_prev, dt, constraint_tol, position_tol,
         divergence_tol, max_iters)
     state._call_counts["constr"] = state._call_counts.get("constr", 0) + i
-    state.last_iters = i
+    state.last_iters, state.last_residuals = i, (float(err), float(ndq))
     return _finish_projection("Quasi-Newton", state, q_, mu, i, ndq, err, dh2_flow_mom_dmom, constraint_tol,
                               position_tol, divergence_tol)
 
@@ -611,7 +662,7 @@ def jitted_solve_projection_onto_manifold_newton(state, state_prev, dt, system, 
         divergence_tol, max_iters)
     for k in ("constr", "jacob_constr_blocks", "lu_jacob_product_blocks"):
         state._call_counts[k] = state._call_counts.get(k, 0) + i
-    state.last_iters = i
+    state.last_iters, state.last_residuals = i, (float(err), float(ndq))
     return _finish_projection("Newton", state, q_, mu, i, ndq, err, dh2_flow_mom_dmom, constraint_tol,
                               position_tol, divergence_tol)
 
@@ -642,6 +693,7 @@ class ConstrainedLeapfrogIntegrator:
 
     def _step_b(self, state, dt):
         dt_i = dt / self.n_inner_step
+        self.inner_log = []
         for i in range(self.n_inner_step):
             state_prev = state.copy()
             self._h2_flow_retraction_onto_manifold(state, state_prev, dt_i)
@@ -653,6 +705,10 @@ class ConstrainedLeapfrogIntegrator:
             rev_diff = onp.max(onp.abs(state_back.pos - state_prev.pos))  # mici.solvers.maximum_norm
             self.last_rev_diff = float(rev_diff)
             self.last_iters = (getattr(state, "last_iters", -1), getattr(state_back, "last_iters", -1))
+            # bookkeeping for the tests (not in mici): per inner step, the iteration counts and the (|c|, |δq|) the
+            # forward and the reverse solver stopped at
+            self.inner_log.append((self.last_iters, getattr(state, "last_residuals", None),
+                                   getattr(state_back, "last_residuals", None), float(rev_diff)))
             if rev_diff > self.reverse_check_tol:
                 raise NonReversibleStepError(
                     f"Non-reversible step. Distance between initial and forward-backward integrated positions = {rev_diff:.1e}.")
@@ -712,12 +768,14 @@ def find_initial_state_by_linear_interpolation(system, rng, generate_x_obs_seq_i
 
 
 def make_system(model, obs_interval, num_steps_per_obs, num_obs_per_subseq, y_seq, sigma=None,
-                use_gaussian_splitting=False):
+                use_gaussian_splitting=False, M_0=None):
     """Wiring of scripts/utils.py:254-270 for a model object of oracle.py.models.  sigma: None, a number, or "variable"
-    = the model's generate_σ_y with dim_u = dim_z + 1 (scripts/sir_model_chmc_experiment.py:44,58,77)."""
+    = the model's generate_σ_y with dim_u = dim_z + 1 (scripts/sir_model_chmc_experiment.py:44,58,77).
+    M_0: metric = blockdiag(M_0, I) (None: identity)."""
     variable = isinstance(sigma, str)
     return ConditionedDiffusionConstrainedSystem(
         obs_interval, num_steps_per_obs, num_obs_per_subseq, y_seq, model.dim_z + int(variable), model.dim_x, model.dim_v,
         model.forward_func, model.generate_x_0, model.generate_z, model.obs_func,
         generate_σ=model.generate_sigma_y if variable else sigma,
-        use_gaussian_splitting=use_gaussian_splitting, dim_v_0=model.dim_v_0)
+        use_gaussian_splitting=use_gaussian_splitting, dim_v_0=model.dim_v_0,
+        metric=None if M_0 is None else BlockDiagonalMetric(M_0))

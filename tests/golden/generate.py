@@ -33,7 +33,13 @@ CASES = [
     ("sir_varsigma_single_block", "sir", 5, 6, None, "variable", False, 0.25),
     ("sir_varsigma_partitioned", "sir", 6, 8, 2, "variable", False, 0.25),
     ("fhn_varsigma_gauss", "fhn", 6, 4, 2, "variable", True, 0.2),
+    # shapes of the kernel families the files above do not reach: one 16-row block (more than 8 rows), the forward-scan
+    # kernel (S % 8 == 0), and metric = blockdiag(M_0, I) (the file stores M_0)
+    ("sir_16row", "sir", 14, 8, 14, True, False, 0.25),
+    ("fhn_scan_s16", "fhn", 12, 16, 5, True, False, 0.2),
+    ("fhn_block_metric", "fhn", 6, 8, 2, True, False, 0.2),
 ]
+WITH_METRIC = {"fhn_block_metric"}
 TOLS = dict(constraint_tol=1e-9, position_tol=1e-8, max_iters=50)
 
 
@@ -81,9 +87,15 @@ def main():
         xo = sys0._generate_x_obs_seq(osys.T(q)).numpy()
         sig0 = float(np.exp(q[model.dim_z])) if var_sigma else sigma
         y = model.obs_func(osys.T(xo)).numpy() + (sig0 * q[-T:, None] if noisy else 0.0)
-        sysm = osys.make_system(model, oi, S, R, y, sigma=sigma, use_gaussian_splitting=gaussian)
+        M_0 = None
+        if name in WITH_METRIC:
+            a = rng.standard_normal((model.dim_z, model.dim_z))
+            M_0 = a @ a.T / model.dim_z + 0.5 * np.eye(model.dim_z)
+        sysm = osys.make_system(model, oi, S, R, y, sigma=sigma, use_gaussian_splitting=gaussian, M_0=M_0)
         out = dict(model=mname, T=T, S=S, R=-1 if R is None else R, noisy=noisy, gaussian=gaussian, obs_interval=oi,
                    sigma=-1.0 if sigma is None else (-2.0 if var_sigma else sigma), y=y[:, 0], q=q, x_obs=xo)  # -2: variable
+        if M_0 is not None:
+            out["M_0"] = M_0
         rmax = max(int(b.shape[-2]) for p in range(sysm.num_partition)
                    for b in sysm._jacob_constr_blocks(osys.T(q), osys.T(xo), p)[1])
         nv = model.dim_v_0 + T * S * model.dim_v

@@ -22,7 +22,7 @@ def load(name):
     cfg = dict(model=str(g["model"]), T=int(g["T"]), S=int(g["S"]), R=None if int(g["R"]) < 0 else int(g["R"]),
                sigma="variable" if float(g["sigma"]) == -2.0 else None if float(g["sigma"]) < 0 else float(g["sigma"]),
                gaussian=bool(g["gaussian"]),
-               obs_interval=float(g["obs_interval"]))
+               obs_interval=float(g["obs_interval"]), M_0=g.get("M_0"))  # M_0: metric = blockdiag(M_0, I), optional
     return g, cfg
 
 
@@ -37,6 +37,8 @@ def test_c_oracle_matches_golden(name):
     g, cfg = load(name)
     osys = c_oracle.OracleSystem(cfg["model"], cfg["obs_interval"], cfg["S"], cfg["R"], g["y"], sigma=cfg["sigma"],
                                  use_gaussian_splitting=cfg["gaussian"])
+    if cfg["M_0"] is not None:
+        osys.set_metric(cfg["M_0"])
     assert osys.num_partition == int(g["num_partition"]) and osys.rmax == int(g["rmax"])
     close(osys.generate_x_obs_seq(g["q"]), g["x_obs"], 1e-12, "x_obs_seq")
     for part in range(osys.num_partition):
@@ -72,6 +74,8 @@ def check_library(name):
     g, cfg = load(name)
     ctx = ChmcContext(cfg["model"], cfg["obs_interval"], cfg["S"], cfg["R"], g["y"], sigma=cfg["sigma"],
                       use_gaussian_splitting=cfg["gaussian"], num_chains=2)
+    if cfg["M_0"] is not None:
+        ctx.set_metric(cfg["M_0"])
     two = lambda a: np.stack([a, a])  # noqa: E731  two identical chains: also checks chain independence
     rm = int(g["rmax"])
     for part in range(ctx.num_partition):

@@ -467,7 +467,8 @@ def _step_every_chain_against_oracle(ctx, osys, q, p0, xo, part, dts, act, max_i
     """One batched leapfrog step from the given per-chain states against one oracle chain per chain.
     edge_ok: layouts whose forward scan is the time-parallel one (its constraint values agree with the sequential
     recursion to about 1e-12, not bitwise) may differ in a Newton iteration count where the oracle's residual lies within
-    1e-2 (relative) of a convergence tolerance at that count; every other layout gets no allowance."""
+    1e-2 (relative) of a convergence tolerance at that count -- that is only DIAGNOSED here (the failure message says
+    whether a differing count sat on such an edge): no chain of the full-size tests does, and the final assertion allows none."""
     from oracle import c_oracle
     B = len(q)
     res = ctx.leapfrog_step(dts, active=act, max_iters=max_iters)
@@ -499,7 +500,9 @@ def _step_every_chain_against_oracle(ctx, osys, q, p0, xo, part, dts, act, max_i
         assert np.abs(q1[c] - qo).max() <= ctol * max(1.0, np.abs(qo).max()), (part, c)
         assert np.abs(p1[c] - po).max() <= ctol * max(1.0, np.abs(po).max()), (part, c)
         n_ok += st == 0
-    assert len(edge) <= max(1, B // 30), edge  # tolerance-edge chains are rare
+    # measured on the MI355X over every full-size test that calls this (5 partitions x 72 chains, time-parallel-scan layout
+    # included): no chain took the tolerance-edge allowance, so none is granted
+    assert edge == [], (part, edge)
     return res, n_ok
 
 
@@ -562,6 +565,7 @@ _MFMA_SCRIPT = r"""
 import sys, numpy as np
 sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
 from helpers import check_ops_against_oracle
+import autodiff_checks as ac
 from oracle import c_oracle
 from manifold_mcmc_for_diffusions_amd.workload import SirWorkload
 B = 6
@@ -570,8 +574,12 @@ ctx = wl.ctx
 assert ctx.RM == 16 and ctx.K == [1]
 q, _, xo, _ = ctx.get_state()
 osys = c_oracle.OracleSystem("sir", 1.0, 200, 14, wl.y[:, 0], sigma=1.0)
-case = dict(osys=osys, q=q, x_obs=xo, B=B, rng=np.random.default_rng(5))
+case = dict(osys=osys, q=q, x_obs=xo, B=B, rng=np.random.default_rng(5), model="sir", obs_interval=1.0, S=200, R=14,
+            y=wl.y[:, 0], sigma=1.0, gaussian=False)
+ad = ac.submit_ops(case, [3], 6, want=())  # chain 3 judged by the autodiff oracle as well (a spawned worker)
 worst = check_ops_against_oracle(ctx, case, tol=1e-9)
+ad_worst = ac.check_ops(ctx, ad)  # chol_D (factor of the MFMA-built Gram), log_det, ...: 1e-9
+assert ad_worst["chol_D"] < 1e-9 and ad_worst["log_det"] < 1e-9
 ctx.set_state(q, case["rng"].standard_normal((B, ctx.Q)), xo, 0)
 ctx.project_onto_cotangent_space()
 _, p0, _, _ = ctx.get_state()

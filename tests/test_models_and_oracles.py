@@ -256,3 +256,77 @@ def test_oracle_projection_trace_matches_the_loop_condition():
         # the same trace judged with a tolerance placed on the deciding quantity is an edge
         k = it - 1
         assert _count_differs_on_tolerance_edge(ch, d, k, it, ctol=max(err[k - 1], 1e-300) * 1.001, ptol=1.0)
+
+
+@pytest.mark.parametrize("model,T,S,R,noisy", [("fhn", 6, 4, 2, True), ("fhn", 7, 5, 3, False), ("sir", 5, 6, None, True),
+                                               ("sir", 14, 8, 14, True)])  # (the last one: a 16-row block)
+def test_autodiff_oracle_block_metric_against_c_oracle_and_dense_algebra(model, T, S, R, noisy):
+    """metric = blockdiag(M_0, I) in the autodiff oracle (restated from sde/mici_extensions.py:279-315, 794-798, 1033-1041,
+    1105-1113, 1202-1259) against the C oracle's M_0 path and against dense algebra on J M^-1 J^T (J by jacrev)."""
+    case = make_case(model, T, S, R, noisy, B=2, seed=31, obs_interval=0.25 if model == "sir" else None)
+    osy, rng = case["osys"], case["rng"]
+    M0 = _spd(rng, 4)
+    ref = osys.make_system(omodels.MODELS[model], case["obs_interval"], S, R, case["y"][:, None], sigma=case["sigma"], M_0=M0)
+    osy.set_metric(M0)
+    Minv = np.eye(osy.Q)
+    Minv[:4, :4] = np.linalg.inv(M0)
+    q, xo = case["q"][1], case["x_obs"][1]
+    rel = lambda a, b: np.abs(np.asarray(a) - np.asarray(b)).max() / max(1.0, np.abs(b).max())  # noqa: E731
+    for part in range(osy.num_partition):
+        st = osys.ConditionedDiffusionHamiltonianState(q, xo, part)
+        Jd = torch.func.jacrev(lambda qq: ref._constr(qq, osys.T(xo), part))(osys.T(q)).numpy()
+        G = Jd @ Minv @ Jd.T
+        w, lam = rng.standard_normal(osy.Q), rng.standard_normal(G.shape[0])
+        jac, chol = ref.jacob_constr_blocks(st), ref.chol_gram_blocks(st)
+        cC, _, ld, grad = osy.gram_ops(q, xo, part)
+        _, _, Gil, nsc = osy.jacob_products(q, xo, part, w, lam)
+        assert rel(chol[0].numpy(), cC) < 1e-9
+        assert abs(ref.log_det_sqrt_gram(st) - ld) < 1e-10 * max(1.0, abs(ld))
+        assert abs(ref.log_det_sqrt_gram(st) - 0.5 * np.linalg.slogdet(G)[1]) < 1e-9
+        assert rel(ref.grad_log_det_sqrt_gram(st), grad) < 1e-8
+        r_gil = ref._lmult_by_inv_gram(*jac, *chol, osys.T(lam)).numpy()
+        assert rel(r_gil, Gil) < 1e-8
+        np.testing.assert_allclose(r_gil, np.linalg.solve(G, lam), rtol=1e-7, atol=1e-9 * np.abs(r_gil).max())
+        r_nsc = ref.normal_space_component(st, w)
+        assert rel(r_nsc, nsc) < 1e-8
+        np.testing.assert_allclose(r_nsc, Jd.T @ np.linalg.solve(G, Jd @ Minv @ w), rtol=1e-7, atol=1e-9)
+    # h2, dh2_dmom, sample_momentum (metric.sqrt @ n, projected with J M^-1) at the on-manifold point
+    q0, x0 = case["q"][0], case["x_obs"][0]
+    st0 = osys.ConditionedDiffusionHamiltonianState(q0, x0, 0)
+    st0.mom = ref.sample_momentum(st0, np.random.default_rng(3))
+    n = np.random.default_rng(3).standard_normal(osy.Q)
+    n[:4] = np.linalg.cholesky(M0) @ n[:4]
+    ch = c_oracle.OracleChain(osy)
+    ch.set(q0, n, x0, 0)
+    ch.project_mom()
+    assert rel(st0.mom, ch.get()[1]) < 1e-9
+    Jp = torch.func.jacrev(lambda qq: ref._constr(qq, osys.T(x0), 0))(osys.T(q0)).numpy()
+    assert np.abs(Jp @ Minv @ st0.mom).max() < 1e-9 * np.abs(st0.mom).max()
+    assert abs(ref.h2(st0) - 0.5 * st0.mom @ Minv @ st0.mom) < 1e-12 * max(1.0, ref.h2(st0))
+    np.testing.assert_allclose(ref.dh2_dmom(st0), Minv @ st0.mom, rtol=1e-13, atol=1e-14)
+    assert abs(ref.h(st0) - ch.hamiltonian()) < 1e-10 * max(1.0, abs(ref.h(st0)))
+    # both solvers: the retraction's position and multiplier term (delta_q = M^-1 delta_mu), then one whole step
+    dt = 0.02 if model == "sir" else 0.05
+    for newton, solver in ((True, osys.jitted_solve_projection_onto_manifold_newton),
+                           (False, osys.jitted_solve_projection_onto_manifold_quasi_newton)):
+        s = st0.copy()
+        ref.h2_flow(s, dt)
+        np.testing.assert_allclose(s.pos, q0 + dt * Minv @ st0.mom, rtol=1e-13, atol=1e-14)
+        qs, mom_before = s.pos.copy(), s.mom.copy()
+        solver(s, st0, dt, ref, constraint_tol=1e-9, position_tol=1e-8, max_iters=50)
+        stc, q1, mu, it, ndq, err = osy.project(newton, q0, qs, x0, 0, dt)
+        assert stc == 0 and it == s.last_iters
+        assert rel(s.pos, q1) < 1e-10 and rel(mom_before - s.mom, mu) < 1e-8
+        np.testing.assert_allclose(np.linalg.inv(Minv) @ (qs - s.pos), (mom_before - s.mom) * dt, rtol=1e-8, atol=1e-12)
+        integ = osys.ConstrainedLeapfrogIntegrator(ref, step_size=dt, projection_solver=solver,
+                                                   projection_solver_kwargs=dict(constraint_tol=1e-9, position_tol=1e-8))
+        s1 = integ.step(st0)
+        ch.set(q0, st0.mom, x0, 0)
+        stc, itf, itb, _ = ch.step(dt, newton=newton)
+        assert (stc, itf, itb) == (0,) + tuple(integ.last_iters)
+        q1, p1, _, _ = ch.get()
+        assert rel(s1.pos, q1) < 1e-10 and rel(s1.mom, p1) < 1e-10
+        assert abs(ref.h(s1) - ch.hamiltonian()) < 1e-10 * max(1.0, abs(ref.h(s1)))
+    osy.set_metric(None)
+    with pytest.raises(ValueError):  # sde/mici_extensions.py:293-300
+        osys.make_system(omodels.fhn, 0.2, 4, 2, np.zeros((6, 1)), sigma=0.1, use_gaussian_splitting=True, M_0=M0)
