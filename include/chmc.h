@@ -198,7 +198,8 @@ int chmc_switch_partition(chmc_ctx* ctx);
  * sequential recursion to about 1e-15 relative after its final sweep, not bitwise), never statuses.
  *   read by chmc_create:
  *   CHMC_COMPACT_ROWS=0     round 1's stored-rows kernel family everywhere (the A/B partner of the default)
- *   CHMC_GRAM_MFMA=1        fp64-MFMA Gram kernel for 16-row blocks (on the stored-rows Newton sweep)
+ *   CHMC_GRAM_MFMA=1        fp64-MFMA Gram kernel: 16-row blocks (on the stored-rows Newton sweep), and blocks of at most 8
+ *                           rows, for which it selects the stored-rows kernel family as CHMC_COMPACT_ROWS=0 does
  *   CHMC_PAR_SCAN=0/1       time-parallel forward scan off / forced (default: at most 4 blocks per chain, >= 1024 steps)
  *   CHMC_PAR_WAVES=1/2/4    wavefronts per (chain, block) of that scan (default: from the block length; also read by the
  *                           comparator target's scan at every call)
@@ -316,7 +317,8 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
 /* diagnostics of the kernel paths taken since creation (tests assert with them that an optional kernel family ran):
  *   out80[0]       blocks the time-parallel forward scan handed to its sequential fallback
  *   out80[1 .. 63] histogram of sweeps to convergence of the time-parallel scan (1 + sweeps + 16 (guess kind - 1)), [15] parked
- *   out80[64]      launches of the fp64-MFMA Gram kernel (v_mfma_f64_16x16x4_f64; 16-row blocks, CHMC_GRAM_MFMA=1)
+ *   out80[64]      launches of the fp64-MFMA Gram kernel (v_mfma_f64_16x16x4_f64; CHMC_GRAM_MFMA=1: 16-row blocks, and blocks
+ *                  of at most 8 rows on the stored-rows family)
  *   out80[65]      launches of the vector-FMA Gram kernel over stored rows (16-row blocks)
  *   out80[66]      launches of the per-chain retraction kernel (k_retract_chain: one 16-row block per chain)
  *   out80[67]      launches of the per-chain trajectory kernel (k_traj_chain: whole leapfrog steps of such a chain)

@@ -234,9 +234,12 @@ static void select_partition(chmc_ctx* c, int p) {
 //   stored rows (CHMC_COMPACT_ROWS=0)  round 1's kernels over Slots::Jv: k_rev_wave / k_rev_wave_ldsrows, k_gram_rows,
 //                               k_gld_fwd_wave + k_gld_bwd_wave(_ldsrows), k_jw_wave, KUpdate -- kept as the independent
 //                               second implementation the full-size A/B test compares against (tests/test_hip_parity.py)
-// and one optional kernel: CHMC_GRAM_MFMA=1 forms the Gram block of 16-row blocks on the matrix cores
-// (v_mfma_f64_16x16x4_f64, k_gram_rows_mfma) instead of with vector FMAs; it works on stored rows, so it also puts the
-// 16-row Newton sweep on the stored-rows kernels (measurements: DESIGN.md section 4; GPU test with the switch set).
+// and one optional kernel: CHMC_GRAM_MFMA=1 forms the Gram block on the matrix cores (v_mfma_f64_16x16x4_f64,
+// k_gram_rows_mfma) instead of with vector FMAs; it works on stored rows, so it also puts the 16-row Newton sweep on the
+// stored-rows kernels, and selects the whole stored-rows family for blocks of at most 8 rows (FitzHugh-Nagumo: the
+// sweeps k_rev_wave<.., GRAM = false> store the rows, the state's into Slots::Jv, the Newton iterate's into work.JvW, and
+// accumulate no Gram block; everything else is the CHMC_COMPACT_ROWS=0 set).  Measurements: DESIGN.md section 4,
+// profiles/mfma_gram_utilisation_fhn_s800.txt; GPU tests with the switch set.
 static bool compact_rows() {
   static const int v = getenv("CHMC_COMPACT_ROWS") ? atoi(getenv("CHMC_COMPACT_ROWS")) : 1;
   return v != 0;
@@ -245,6 +248,11 @@ static bool gram_mfma() {
   static const int v = getenv("CHMC_GRAM_MFMA") ? atoi(getenv("CHMC_GRAM_MFMA")) : 0;
   return v != 0;
 }
+// Blocks of at most 8 rows with CHMC_GRAM_MFMA=1: the stored-rows family (the MFMA kernel contracts rows in memory, and
+// the compact rows never store them), exactly as CHMC_COMPACT_ROWS=0 selects it
+static bool compact_family(int rmt) { return compact_rows() && !(gram_mfma() && rmt <= 8); }
+// ... whose sweeps then only store the rows (k_rev_wave<.., GRAM = false>) and leave the Gram block to k_gram_rows_mfma
+static bool gram_mfma8(const chmc_ctx* c) { return gram_mfma() && c->RMt <= 8 && c->sl.PB[0] == nullptr; }
 // Every kernel choice below follows from the LAYOUT (blocks per chain, block length, rows) -- never from the number of
 // chains in the context -- so a chain's bits do not depend on the shard it runs in: N ranks of B / N chains reproduce one
 // rank of B chains chain for chain (SURVEY 4 (viii); tests/test_hip_parity.py::test_results_do_not_depend_on_the_shard_size).
@@ -499,7 +507,7 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
     dev_zero(sl.Jv[s], sizeof(double) * B * RM * sy.NV);
     sl.PB[s] = sl.LF[s] = nullptr;
 #ifdef CHMC_WAVE_KERNELS
-    if (compact_rows()) {  // compact form of the stored rows for the Newton-loop passes (chmc_core.h, Slots)
+    if (compact_family(c->RMt)) {  // compact form of the stored rows for the Newton-loop passes (chmc_core.h, Slots)
       sl.PB[s] = alloc<double>(c, B * sy.T * sy.S * sy.X * sy.V);
       sl.LF[s] = alloc<double>(c, B * kmax * sy.NOBS * RM * sy.X);
       dev_zero(sl.PB[s], sizeof(double) * B * sy.T * sy.S * sy.X * sy.V);
@@ -523,7 +531,8 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
   w.Ew = alloc<double>(c, B * kmax * RM * U), w.Cb = alloc<double>(c, B * kmax * U * U);
   w.sb = alloc<double>(c, B * kmax * U), w.gup = alloc<double>(c, B * kmax * U);
   w.Dw = alloc<double>(c, B * kmax * RM * RM), w.JuL = alloc<double>(c, B * kmax * RM * U);
-  w.JvW = RM > 8 ? alloc<double>(c, B * RM * sy.NV) : nullptr;  // rows of the Newton iterate (16-row blocks)
+  // rows of the Newton iterate (16-row blocks; blocks of at most 8 rows with the MFMA Gram kernel)
+  w.JvW = (RM > 8 || gram_mfma()) ? alloc<double>(c, B * RM * sy.NV) : nullptr;
   if (w.JvW) dev_zero(w.JvW, sizeof(double) * B * RM * sy.NV);
   w.zbP = alloc<double>(c, B * kmax * RM * sy.Z), w.gMb = alloc<double>(c, B * kmax * RM * RM);
   w.gzd = alloc<double>(c, B * kmax * RM * sy.Z), w.gWu = alloc<double>(c, B * kmax * RM * U);
@@ -653,6 +662,13 @@ static void state_eval_core(chmc_ctx* c, int which, bool with_grad = true, int t
         if (rows_skipped(c)) {  // the state sweep at three wavefronts per SIMD (compact rows)
           lean_state = true;
           launch_blocks(k_newton_lean<M, RM, true, true>, (long)sy.B * sy.K, 64, 2, sy, c->sl, c->w, which, 0);
+        }
+      }
+      if constexpr (RM <= 8) {
+        if (gram_mfma8(c)) {  // store the rows, then the Gram block from the stored rows on the matrix cores
+          lean_state = true;
+          launch_wave(k_rev_wave<M, RM, 0, false>, (long)sy.B * sy.K, 2, sy, c->sl, c->w, which, 0);
+          launch_blocks(k_gram_rows_mfma<RM>, (long)sy.B * sy.K, 64, 2, sy, c->sl, c->w, which, 0, 0), c->diag[0]++;
         }
       }
       if (!lean_state) launch_wave(k_rev_wave<M, RM, 0>, (long)sy.B * sy.K, 2, sy, c->sl, c->w, which, 0);
@@ -896,6 +912,9 @@ static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel, co
           if (c->sl.PB[0]) {
             launch_blocks(k_newton_ivl<M>, (long)sy.B * sy.K * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
             launch_blocks(k_newton_comb<M, RM>, (long)sy.B * sy.K, 64, 1, sy, c->sl, c->w, prev, qsel);
+          } else if (gram_mfma8(c)) {  // the iterate's rows into work.JvW, Gram block against the stored rows by MFMA
+            launch_wave(k_rev_wave<M, RM, 1, false>, (long)sy.B * sy.K, 1, sy, c->sl, c->w, prev, qsel);
+            launch_blocks(k_gram_rows_mfma<RM>, (long)sy.B * sy.K, 64, 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[0]++;
           } else {
             launch_wave(k_rev_wave<M, RM, 1>, (long)sy.B * sy.K, 1, sy, c->sl, c->w, prev, qsel);
           }
@@ -1412,7 +1431,7 @@ extern "C" int chmc_switch_partition(chmc_ctx* ctx) {
 #ifdef CHMC_WAVE_KERNELS
   // the stored trajectories (valid for the partition we are leaving) seed a time-parallel pass over the whole chain
   // (the stored-rows family keeps round 1's sequential pass: the A/B test then covers both)
-  const bool par = compact_rows() && ctx->have_state;
+  const bool par = compact_family(ctx->RMt) && ctx->have_state;
   if (par) {
     const Sys& so = ctx->sy;
     CHMC_DISPATCH(ctx, { launch_blocks(k_xobs_par<M>, (long)so.B, 64, 0, so, ctx->sl, ctx->d_xobs); });

@@ -1869,9 +1869,11 @@ __global__ void __launch_bounds__(256) k_gram_rows(Sys sy, Slots sl, Work w, int
 
 // The same Gram block on the matrix cores: D (16 x 16) = Ja Jb^T as a chain of v_mfma_f64_16x16x4_f64, ONE wavefront
 // per (chain, block).  This is the dense J J^T contraction of compute_D_blocks (:765-792) that BASELINE.json's config 5
-// names; it only fits the hardware tile where a block has 16 row slots (the stored-rows path of the SIR single-block
-// layout) -- the 7-row FitzHugh-Nagumo blocks form their Gram in registers with the time index across the lanes, the
-// transpose of what the instruction wants.
+// names.  It needs the rows in memory: 16-row blocks (the stored-rows path of the SIR single-block layout) fill the
+// hardware tile; blocks of at most 8 rows (the 7-row FitzHugh-Nagumo blocks) use it on the stored-rows family only, with
+// the block's columns folded into the tile twice (below) -- their default kernels form the Gram in registers with the
+// time index across the lanes, the transpose of what the instruction wants, and never store the rows (DESIGN.md
+// section 4; profiles/mfma_gram_utilisation_fhn_s800.txt).
 //   operand layout (cdna_hip_programming.md section 3): lane l, r = l & 15, g = l >> 4 supplies A[i = r][k = g] and
 //   B[k = g][j = r]; result register m holds D[row = g + 4 m][col = r].
 // Columns are read the coalesced way (lane = column, 512 contiguous bytes per row and instruction, next tile's loads in
@@ -1880,9 +1882,9 @@ __global__ void __launch_bounds__(256) k_gram_rows(Sys sy, Slots sl, Work w, int
 typedef double v4d_t __attribute__((ext_vector_type(4)));
 template <int RM>
 __global__ void __launch_bounds__(64) k_gram_rows_mfma(Sys sy, Slots sl, Work w, int which, int newton, int qsel) {
-  static_assert(RM == 16, "the MFMA Gram kernel is the 16 x 16 x 4 fp64 tile");
+  static_assert(RM <= 8 || RM == 16, "the MFMA Gram kernel is the 16 x 16 x 4 fp64 tile: 16 rows, or at most 8 rows twice");
   constexpr int LDT = 66;
-  __shared__ double ta[RM * LDT], tb[RM * LDT];
+  __shared__ double ta[16 * LDT], tb[16 * LDT];
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x;
   if (wid >= sy.B * sy.K) return;
@@ -1896,6 +1898,66 @@ __global__ void __launch_bounds__(64) k_gram_rows_mfma(Sys sy, Slots sl, Work w,
   const double* Ja = (newton ? w.JvW : pick(sl.Jv, s)) + (size_t)c * RM * sy.NV + bd.col0;
   const int r = lane & 15, g = lane >> 4;
   v4d_t acc = {0.0, 0.0, 0.0, 0.0};
+  if constexpr (RM <= 8) {
+    // Blocks of at most 8 rows: the block's columns in two halves [0, h) and [h, ncols), operand rows 0-7 = the rows over
+    // the first half, rows 8-15 = the same rows over the second half (the shorter half and the rows RM .. 7 of either
+    // half are zero).  The two diagonal 8 x 8 quadrants of the tile are the two halves' shares of D, the off-diagonal
+    // quadrants (first half against second half) are discarded: 2 RM^2 of the tile's 256 products are useful.  A tile
+    // of the loop is 64 columns of EACH half: 16 MFMAs per 128 columns.
+    const int h = (bd.ncols + 1) >> 1;
+    for (int i = lane; i < 16 * LDT; i += 64) ta[i] = 0.0, tb[i] = 0.0;
+    double ra[2 * RM], rb[2 * RM];
+    auto fetch = [&](int k0) {
+      const int k = k0 + lane;
+      const bool in0 = k < h, in1 = h + k < bd.ncols;
+#pragma unroll
+      for (int i = 0; i < RM; ++i) {
+        ra[i] = in0 ? Ja[(size_t)i * sy.NV + k] : 0.0;
+        ra[RM + i] = in1 ? Ja[(size_t)i * sy.NV + h + k] : 0.0;
+      }
+#pragma unroll
+      for (int i = 0; i < 2 * RM; ++i) rb[i] = ra[i];  // state evaluation: Ja is Jb
+      if (newton) {
+#pragma unroll
+        for (int i = 0; i < RM; ++i) {
+          rb[i] = in0 ? Jb[(size_t)i * sy.NV + k] : 0.0;
+          rb[RM + i] = in1 ? Jb[(size_t)i * sy.NV + h + k] : 0.0;
+        }
+      }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < h; k0 += 64) {
+#pragma unroll
+      for (int i = 0; i < RM; ++i) {
+        ta[i * LDT + lane] = ra[i], tb[i * LDT + lane] = rb[i];
+        ta[(8 + i) * LDT + lane] = ra[RM + i], tb[(8 + i) * LDT + lane] = rb[RM + i];
+      }
+      if (k0 + 64 < h) fetch(k0 + 64);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int m = 0; m < 16; ++m)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ta[r * LDT + 4 * m + g], tb[r * LDT + 4 * m + g], acc, 0, 0, 0);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+    }
+    // D[g + 4 m][r] (m = 0, 1; r < 8) = quadrant (0, 0), here, + quadrant (1, 1): registers 2, 3 of lane r + 8
+    const double d0 = acc[0] + __shfl_down(acc[2], 8, 64), d1 = acc[1] + __shfl_down(acc[3], 8, 64);
+    const double sgb = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q) : 0.0;
+    const double s2 = sgb * (newton && sy.noisy ? sigma_at(sy, (qsel ? w.qb : pick(sl.q, s ^ 1)) + (size_t)c * sy.Q) : sgb);
+    double* Do = w.Dw + cb * RM * RM;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int gi = g + 4 * m, j = r;  // row of Ja, row of Jb
+      double v = m == 0 ? d0 : d1;
+      if (gi == j) {
+        if (sy.noisy && gi < bd.ny) v += s2;
+        if (gi >= bd.nrows) v = 1.0;
+      }
+      if (gi < RM && j < RM) Do[gi * RM + j] = v;
+    }
+    return;
+  }
   double ra[RM], rb[RM];
   auto fetch = [&](int k0) {
     const int k = k0 + lane;
