@@ -190,28 +190,13 @@ int chmc_switch_partition(chmc_ctx* ctx);
  * never writes the full rows of blocks with at most 8 rows.  The entry points below that return rows or multiply by them
  * rebuild the row-slot array first (one extra pass, only when called); results are the same to rounding.
  *
- * Environment switches -- EVERY variable the library reads; each is exercised by a GPU test.  Defaults are chosen from the
- * layout (blocks per chain, block length, rows) alone, never from the number of chains -- the one exception, the execution
- * model of single-block layouts (CHMC_RETRACT_KERNEL), chooses between bit-identical paths --, so a chain's results do not depend
- * on the shard it runs in (bitwise: tests/test_hip_parity.py::test_results_do_not_depend_on_the_shard_size).  Pinning a
- * switch to a non-default value changes bits at the rounding level (summation order; the time-parallel scan equals the
- * sequential recursion to about 1e-15 relative after its final sweep, not bitwise), never statuses.
- *   read by chmc_create:
- *   CHMC_COMPACT_ROWS=0     round 1's stored-rows kernel family everywhere (the A/B partner of the default)
- *   CHMC_GRAM_MFMA=1        fp64-MFMA Gram kernel: 16-row blocks (on the stored-rows Newton sweep), and blocks of at most 8
- *                           rows, for which it selects the stored-rows kernel family as CHMC_COMPACT_ROWS=0 does
- *   CHMC_PAR_SCAN=0/1       time-parallel forward scan off / forced (default: at most 4 blocks per chain, >= 1024 steps)
- *   CHMC_PAR_WAVES=1/2/4    wavefronts per (chain, block) of that scan (default: from the block length; also read by the
- *                           comparator target's scan at every call)
- *   CHMC_ROW_SPLIT=1/2/4    16-row state evaluation: 1 = stored-rows sweeps, otherwise interval-parallel (default: <= 4 blocks)
- *   CHMC_HALVES=2           two overlapped half-batches per step
- *   read at every call:
- *   CHMC_NO_FWD_SCAN=1      generic functor instead of the hand-scheduled forward scan
- *   CHMC_STEP_FUSIONS=0     the momentum correction and the reverse flow of a step as passes of their own instead of inside
- *                           the J p / J^T lambda passes (same bits)
- *   CHMC_RETRACT_KERNEL=0/1/2  one 16-row block per chain: batched launches / one workgroup of 8 wavefronts per chain / of 4
- *                           wavefronts (two chains per compute unit).  Default: 8 up to one chain per compute unit, 4 up to
- *                           four, batched beyond; all three give the same bits */
+ * Environment switches: the table of every variable the library reads, and when, is in csrc/chmc_plan.h (read_switches is
+ * the one place that reads them).  Defaults are chosen from the layout (blocks per chain, block length, rows) alone, never
+ * from the number of chains -- the one exception, the execution model of single-block layouts (CHMC_RETRACT_KERNEL), chooses
+ * between bit-identical paths --, so a chain's results do not depend on the shard it runs in (bitwise:
+ * tests/test_hip_parity.py::test_results_do_not_depend_on_the_shard_size).  Pinning a switch to a non-default value changes
+ * bits at the rounding level (summation order; the time-parallel scan equals the sequential recursion to about 1e-15
+ * relative after its final sweep, not bitwise), never statuses. */
 int chmc_constr(chmc_ctx* ctx, double* c);                                  /* :473-519, :1151-1155  [B][C] */
 /* :521-624, :1157-1161.  dc_du [B][C][U]; dc_dv [B][RM][NV] row-slot layout (slot i = row i of the block that
  * owns the column); dc/dn is sigma on observation rows (:601-608). */

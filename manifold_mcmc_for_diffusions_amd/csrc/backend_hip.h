@@ -337,23 +337,7 @@ __global__ void __launch_bounds__(256) k_colmax(F f, int ncol, int rev) {
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int i = 1; i < 4; ++i) v = sm[i] > v ? sm[i] : v;
-    if constexpr (F::kFinish) {
-      // Per-chain epilogue by the last workgroup of the chain (no fences: a workgroup-wide release flushes the XCD's L2,
-      // measured 13x slower).  Device-scope atomics are performed at the point of coherence, and one that RETURNS a value has
-      // been performed when the value arrives: the ticket is taken with an increment that depends on the value the maximum
-      // returned (its top bit, always 0), so every workgroup's maximum is in place before its ticket counts.  The
-      // workgroup that draws the last ticket reads the finished maximum back with an atomic and runs f.finish (the
-      // chain's other data were written by earlier kernels of the stream).
-      if (f.has_finish()) {
-        const unsigned long long old = v ? atomicMax(tgt, v) : 0ULL;
-        const unsigned t = atomicAdd(f.ticket(c), 1u + (unsigned)(old >> 63));
-        if (t == gridDim.x - 1) f.finish(c, atomicMax(tgt, 0ULL));
-      } else if (v) {
-        atomicMax(tgt, v);
-      }
-    } else {
-      if (v) atomicMax(tgt, v);
-    }
+    if (v) atomicMax(tgt, v);
   }
 }
 // One ticket word per poll slot: the check kernels of the two half-batches (CHMC_HALVES=2: slots 2 h + (round & 1)) run on

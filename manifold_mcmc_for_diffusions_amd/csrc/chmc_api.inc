@@ -12,6 +12,7 @@
 #include <cmath>
 #include <thread>
 #include "../../include/chmc.h"
+#include "chmc_plan.h"
 
 using namespace chmc;
 
@@ -55,11 +56,10 @@ struct chmc_ctx {
   double *d_qbak = nullptr, *d_pbak = nullptr;
   std::vector<void*> allocs;
   long long counters[8];
+  PlanInput plan_in{};  // layout and switches the kernel plan is decided from (chmc_plan.h)
+  KernelPlan plan{};    // which kernel runs for which pass; the per-partition part is plan.part[part]
   long long diag[16] = {0};  // launches by kernel family: [0] k_gram_rows_mfma, [1] k_gram_rows, [2] k_retract_chain, [3] k_traj_chain
   // two half-batches on two streams (chmc_leapfrog_step): chain ranges [hc0[h], hc0[h] + hB[h]) and their work orders
-  bool par_scan = false;           // forward scans by Newton on the trajectory (k_fwd_par): few, long blocks
-  int par_waves = 1;               // wavefronts per (chain, block) of that scan: 1, 2 or 4 (64 segments each)
-  int row_split_sel[2] = {1, 1};   // 16-row state evaluation: wavefronts the rows of a block are dealt out to, per partition
   int round = 0;                   // round of the current Newton loop
   int halves = 1;                  // 1: the step runs as one batch; 2: as two overlapped half-batches
   int hB[2] = {0, 0}, hc0[2] = {0, 0};
@@ -160,7 +160,7 @@ static void set_half(chmc_ctx* c, const ViewSave& f, int h) {
   CHMC_OFF(w.gMb, KM * RM * RM), CHMC_OFF(w.gzd, KM * RM * Z), CHMC_OFF(w.gWu, KM * RM * U);
   CHMC_OFF(w.gxdt, KM * RM * X), CHMC_OFF(w.sdt, 1), CHMC_OFF(w.cdt, 1), CHMC_OFF(w.err, 1), CHMC_OFF(w.ndq, 1);
   CHMC_OFF(w.rev, 1), CHMC_OFF(w.dt, 1), CHMC_OFF(w.part, (size_t)c->npart_sum * 2), CHMC_OFF(w.iters, 1);
-  CHMC_OFF(w.nw, 1), CHMC_OFF(w.ok, 1), CHMC_OFF(w.status, 1), CHMC_OFF(w.nstat, 1), CHMC_OFF(w.ticket, 1);
+  CHMC_OFF(w.nw, 1), CHMC_OFF(w.ok, 1), CHMC_OFF(w.status, 1), CHMC_OFF(w.nstat, 1);
   w.n_active = f.w.n_active + 4 * (1 + h);
   c->sy = sy, c->sl = sl, c->w = w;
   c->d_itf = f.d_itf + c0, c->d_itb = f.d_itb + c0, c->d_act = f.d_act + c0;
@@ -225,71 +225,13 @@ static void select_partition(chmc_ctx* c, int p) {
     }                                             \
   } while (0)
 
-// Kernel families.  The library has TWO complete sets of kernels for the passes over a point's Jacobian, selected once per
-// process; every other round-1 / round-2 variant has been removed (round 3):
-//   compact rows (default)      Slots::PB / LF; Newton sweep = k_newton_ivl + k_newton_comb (+ k_newton_fsm_wave), state sweep =
-//                               k_newton_lean<.., STATE>, grad-log-det = k_gld_fwd_wave<.., QX> + k_gld_bwd_lean, J w =
-//                               k_jw_pb, J^T lambda = KMuF + KUpdatePB; 16-row blocks: rows stored as well (state sweep
-//                               k_rev_wave_ldsrows + k_gram_rows), Newton sweep on the compact rows
-//   stored rows (CHMC_COMPACT_ROWS=0)  round 1's kernels over Slots::Jv: k_rev_wave / k_rev_wave_ldsrows, k_gram_rows,
-//                               k_gld_fwd_wave + k_gld_bwd_wave(_ldsrows), k_jw_wave, KUpdate -- kept as the independent
-//                               second implementation the full-size A/B test compares against (tests/test_hip_parity.py)
-// and one optional kernel: CHMC_GRAM_MFMA=1 forms the Gram block on the matrix cores (v_mfma_f64_16x16x4_f64,
-// k_gram_rows_mfma) instead of with vector FMAs; it works on stored rows, so it also puts the 16-row Newton sweep on the
-// stored-rows kernels, and selects the whole stored-rows family for blocks of at most 8 rows (FitzHugh-Nagumo: the
-// sweeps k_rev_wave<.., GRAM = false> store the rows, the state's into Slots::Jv, the Newton iterate's into work.JvW, and
-// accumulate no Gram block; everything else is the CHMC_COMPACT_ROWS=0 set).  Measurements: DESIGN.md section 4,
-// profiles/mfma_gram_utilisation_fhn_s800.txt; GPU tests with the switch set.
-static bool compact_rows() {
-  static const int v = getenv("CHMC_COMPACT_ROWS") ? atoi(getenv("CHMC_COMPACT_ROWS")) : 1;
-  return v != 0;
+// Kernel families, environment switches and the choice of a kernel per pass: chmc_plan.h.  chmc_create decides the plan, every
+// entry point refreshes the part that hangs on a per-call switch (CHMC_ENTER), the launch sites below switch on it.
+static const PartitionPlan& part_plan(const chmc_ctx* c) { return c->plan.part[c->part]; }
+static void refresh_plan(chmc_ctx* c) {
+  c->plan_in.call = read_switches();
+  c->plan = make_plan(c->plan_in);
 }
-static bool gram_mfma() {
-  static const int v = getenv("CHMC_GRAM_MFMA") ? atoi(getenv("CHMC_GRAM_MFMA")) : 0;
-  return v != 0;
-}
-// Blocks of at most 8 rows with CHMC_GRAM_MFMA=1: the stored-rows family (the MFMA kernel contracts rows in memory, and
-// the compact rows never store them), exactly as CHMC_COMPACT_ROWS=0 selects it
-static bool compact_family(int rmt) { return compact_rows() && !(gram_mfma() && rmt <= 8); }
-// ... whose sweeps then only store the rows (k_rev_wave<.., GRAM = false>) and leave the Gram block to k_gram_rows_mfma
-static bool gram_mfma8(const chmc_ctx* c) { return gram_mfma() && c->RMt <= 8 && c->sl.PB[0] == nullptr; }
-// Every kernel choice below follows from the LAYOUT (blocks per chain, block length, rows) -- never from the number of
-// chains in the context -- so a chain's bits do not depend on the shard it runs in: N ranks of B / N chains reproduce one
-// rank of B chains chain for chain (SURVEY 4 (viii); tests/test_hip_parity.py::test_results_do_not_depend_on_the_shard_size).
-//
-// Wavefronts per (chain, block) of the time-parallel scan, with at least 16 steps per segment.  Measured on boarding-school
-// SIR (2 800 steps), lock-step Newton loop of round 3, steps/s for 1 / 2 / 4 wavefronts per chain: 256 chains 32.6 k / 35.5 k /
-// 31.5 k, 512 chains 54.6 k / 54.7 k / -- (a sweep over 22 steps per lane takes 17.5 us, over 11 steps 11.3 us: the prefix
-// scan across the lanes and the workgroup barriers do not shrink with the segments).  CHMC_PAR_WAVES overrides (1, 2, 4).
-static int par_waves_for(long longest) {
-  const char* e = getenv("CHMC_PAR_WAVES");  // (read at every call: chmc_create and the comparator's scan)
-  const int v = e ? atoi(e) : 0;
-  if (v == 1 || v == 2 || v == 4) return v;
-  return longest >= 4096 ? 4 : longest >= 2048 ? 2 : 1;
-}
-// Few long blocks per chain (the SIR single-block layout: 1 x 2 800 steps): the time-parallel scan and the interval-parallel
-// 16-row state evaluation; many short blocks (FitzHugh-Nagumo: 20 x 2 000): lanes / wavefronts per block already fill the chip.
-static bool few_long_blocks(int nblocks_per_chain, int longest) { return nblocks_per_chain <= 4 && longest >= 1024; }
-// 16-row blocks, state evaluation: > 1 selects the interval-parallel sweeps on the compact rows (lean16: a wavefront per
-// observation interval; at most 4 blocks per chain), 1 the stored-rows sweeps with one wavefront per block (many blocks per
-// chain: those fill the chip by themselves).  CHMC_ROW_SPLIT overrides (1, 2, 4).
-static int row_split_choice(int env, int nblocks_per_chain) {
-  if (env == 1 || env == 2 || env == 4) return env;
-  return nblocks_per_chain <= 4 ? 4 : 1;
-}
-static int row_split_for(const chmc_ctx* c) { return c->row_split_sel[c->part]; }
-// One 16-row block per chain (the boarding-school SIR layout): the layouts of the per-chain kernels (chmc_retract.h).  Their
-// batched (lock-step) path runs the same per-chain arithmetic bit for bit: scans of 8 wavefronts = 512 segments per chain,
-// the workgroup-parallel combine with the 16-lane factorisations, J p over the wavefronts.
-static bool chain16_layout(int kmax, int rmt) { return kmax == 1 && rmt > 8; }
-#ifndef CHMC_CHAIN_WG4_MAX_PER_CU
-#define CHMC_CHAIN_WG4_MAX_PER_CU 4  // (chains per CU up to which two 4-wavefront workgroups per CU match or beat batched launches)
-#endif
-#ifndef CHMC_CHAIN_SCAN_WAVES
-#define CHMC_CHAIN_SCAN_WAVES 4  // (chmc_retract.h; repeated for the host emulation build, which has no wave kernels)
-#endif
-// 16-row blocks: Newton sweep on the compact rows (written by k_rev_wave_ldsrows beside the stored rows)
-static bool compact16(const chmc_ctx* c) { return c->sl.PB[0] != nullptr && !gram_mfma(); }
 #ifdef CHMC_WAVE_KERNELS
 #define CHMC_SOLVE_CHAIN(T1, T2, T3, T4, ...)                                                   \
   do {                                                                                          \
@@ -307,8 +249,8 @@ static bool compact16(const chmc_ctx* c) { return c->sl.PB[0] != nullptr && !gra
 // chains, S = 800: 439 against 392 us per scan.  The scan's time doubles from 80 to 160 wavefronts because it is then bound
 // by the memory system, not by two wavefronts sharing a SIMD: 10 240 lanes x 32 B per step in 128-byte lines that belong to
 // 64 different streams per wave instruction = 2.8-3.3 TB/s, DESIGN.md section 4.)
-// forward scan: hand-scheduled wave kernel when the steps per observation tile by 8, the generic functor otherwise
-// GSEL_: guess trajectory for the time-parallel scan (k_fwd_par; 0: none available -> sequential scan)
+// forward scan (KernelPlan::fwd); GSEL_: guess trajectory for the time-parallel scan (k_fwd_par; 0: none available ->
+// sequential scan, KernelPlan::fwd_cold)
 #define CHMC_FWD_PAR(W_, N_, ...)                                                        \
   do {                                                                                   \
     if ((W_) == 8)                                                                       \
@@ -323,12 +265,13 @@ static bool compact16(const chmc_ctx* c) { return c->sl.PB[0] != nullptr && !gra
 #define CHMC_FWD(WHICH_, QSEL_, USENW_, STORE_, GSEL_)                                                           \
   do {                                                                                                           \
     stagger_wait(); /* half-batches: this half's scan runs after the other half's latest one */                  \
-    if (c->par_scan && (GSEL_) != 0) {                                                                           \
+    const FwdScan fwd_ = (GSEL_) != 0 ? c->plan.fwd : c->plan.fwd_cold;                                          \
+    if (fwd_ == FwdPar) {                                                                                        \
       /* few long blocks: Newton on the trajectory, one wavefront per (chain, block); a scan that stores nothing */ \
       /* (quasi-Newton) iterates on the work trajectory */                                                       \
-      CHMC_FWD_PAR(c->par_waves, (long)sy.B * sy.K, sy, c->sl, c->w, WHICH_, QSEL_, USENW_,                      \
+      CHMC_FWD_PAR(c->plan.fwd_waves, (long)sy.B * sy.K, sy, c->sl, c->w, WHICH_, QSEL_, USENW_,                 \
                    (STORE_) ? (STORE_) : 2, GSEL_, c->round);                                                    \
-    } else if (sy.S % 8 == 0 && !getenv("CHMC_NO_FWD_SCAN")) {                                                   \
+    } else if (fwd_ == FwdWave) {                                                                                \
       if (STORE_)                                                                                                \
         launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B * sy.K + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sy, c->sl, c->w, WHICH_,   \
                       QSEL_, USENW_, STORE_);                                                                    \
@@ -460,32 +403,28 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
   }
   c->hB[0] = sy.B / 2, c->hB[1] = sy.B - sy.B / 2, c->hc0[0] = 0, c->hc0[1] = sy.B / 2;
   {
-    // Time-parallel forward scan: pays when a lane-per-block scan leaves the chip empty for a long recursion, i.e. for few
-    // long blocks per chain (the SIR single-block layout: 1 x 2 800 steps).  Decided from the layout alone: whatever the
-    // number of chains (1 024 blocks of 2 800 steps: 0.9 ms for the sequential scan on 16 wavefronts against three or four
-    // sweeps of 27 us per wavefront).  CHMC_PAR_SCAN=0 / 1 overrides.
-    int longest = 0;
+    PlanInput& in = c->plan_in;
+    in.rmt = c->RMt, in.num_partition = c->num_partition, in.K[0] = c->K[0], in.K[1] = c->K[c->num_partition - 1];
+    in.longest = 0;
     for (int p = 0; p < c->num_partition; ++p)
-      for (auto& bl : c->hblk[p]) longest = bl.nsteps > longest ? bl.nsteps : longest;
-    const char* e = getenv("CHMC_PAR_SCAN");
-    // (one 16-row block per chain on the compact rows: always, whatever the block length -- the per-chain kernels integrate
-    // that way, and the batched path of these layouts does the same arithmetic)
-    c->par_scan = e ? atoi(e) != 0
-                    : (few_long_blocks(kmax, longest) || (chain16_layout(kmax, c->RMt) && compact_rows() && !gram_mfma()));
-    c->par_waves = (chain16_layout(kmax, c->RMt) && !getenv("CHMC_PAR_WAVES")) ? CHMC_CHAIN_SCAN_WAVES : par_waves_for(longest);
-    for (int p = 0; p < c->num_partition; ++p)
-      c->row_split_sel[p] = row_split_choice(getenv("CHMC_ROW_SPLIT") ? atoi(getenv("CHMC_ROW_SPLIT")) : 0, c->K[p]);
+      for (auto& bl : c->hblk[p]) in.longest = bl.nsteps > in.longest ? bl.nsteps : in.longest;
+    in.chain_steps = sy.T * sy.S, in.s_tiles8 = sy.S % 8 == 0;
+    in.V = sy.V, in.even_dims = !((sy.Q | sy.U | sy.V0 | sy.NV) & 1), in.gaussian = sy.gaussian;
+#ifdef CHMC_WAVE_KERNELS
+    in.wave_kernels = true;
+#endif
+    in.sw = in.call = read_switches();
+    c->plan = make_plan(in);
   }
   {
     // CHMC_HALVES=2: run every leapfrog step as two overlapped half-batches.  Bitwise equal to the one-batch step, but
     // measured SLOWER at 256 chains per GPU (26.0 k against 28.4 k steps/s: the forward scan's trajectory stores stall
     // under the other half's memory traffic, DESIGN.md section 7) and equal at 512, so one batch is the default.
-    const char* e = getenv("CHMC_HALVES");
-    c->halves = (e && atoi(e) == 2 && sy.B >= 2) ? 2 : 1;
+    c->halves = (c->plan_in.sw.halves == 2 && sy.B >= 2) ? 2 : 1;
     // (One 16-row block per chain: the retraction runs per chain in its own workgroup (k_retract_chain), there is no
     // lock-step loop to overlap; one block per chain with the time-parallel scan: a handful of wavefronts per half-batch.
     // Always one batch.)
-    if (kmax == 1 && (c->par_scan || c->RMt > 8)) c->halves = 1;
+    if (kmax == 1 && (c->plan.par_scan || c->RMt > 8)) c->halves = 1;
   }
   c->d_y = alloc<double>(c, sy.T);
   h2d(c->d_y, cfg->y_seq, sizeof(double) * sy.T);
@@ -506,20 +445,19 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
     dev_zero(sl.grad[s], sizeof(double) * B * Q);
     dev_zero(sl.Jv[s], sizeof(double) * B * RM * sy.NV);
     sl.PB[s] = sl.LF[s] = nullptr;
-#ifdef CHMC_WAVE_KERNELS
-    if (compact_family(c->RMt)) {  // compact form of the stored rows for the Newton-loop passes (chmc_core.h, Slots)
+    if (c->plan.pb_allocated) {  // compact form of the stored rows for the Newton-loop passes (chmc_core.h, Slots)
       sl.PB[s] = alloc<double>(c, B * sy.T * sy.S * sy.X * sy.V);
       sl.LF[s] = alloc<double>(c, B * kmax * sy.NOBS * RM * sy.X);
       dev_zero(sl.PB[s], sizeof(double) * B * sy.T * sy.S * sy.X * sy.V);
       dev_zero(sl.LF[s], sizeof(double) * B * kmax * sy.NOBS * RM * sy.X);
     }
-#endif
   }
-  c->w.muF = sl.PB[0] ? alloc<double>(c, B * kmax * sy.NOBS * sy.X) : nullptr;
-  c->w.muF2 = sl.PB[0] ? alloc<double>(c, B * kmax * sy.NOBS * sy.X) : nullptr;
-  c->w.ivl = sl.PB[0] ? alloc<double>(c, B * kmax * sy.NOBS * (2 * sy.X * sy.X + sy.X * sy.Z)) : nullptr;
-  c->w.gcq = sl.PB[0] && RM > 8 ? alloc<double>(c, B * kmax * sy.NOBS * (2 * sy.X * sy.X + sy.X * sy.Z)) : nullptr;
-  c->w.gbw = sl.PB[0] && RM > 8 ? alloc<double>(c, B * kmax * sy.NOBS * (sy.X + 2 * sy.Z)) : nullptr;
+  const bool pb = c->plan.pb_allocated;
+  c->w.muF = pb ? alloc<double>(c, B * kmax * sy.NOBS * sy.X) : nullptr;
+  c->w.muF2 = pb ? alloc<double>(c, B * kmax * sy.NOBS * sy.X) : nullptr;
+  c->w.ivl = pb ? alloc<double>(c, B * kmax * sy.NOBS * (2 * sy.X * sy.X + sy.X * sy.Z)) : nullptr;
+  c->w.gcq = pb && RM > 8 ? alloc<double>(c, B * kmax * sy.NOBS * (2 * sy.X * sy.X + sy.X * sy.Z)) : nullptr;
+  c->w.gbw = pb && RM > 8 ? alloc<double>(c, B * kmax * sy.NOBS * (sy.X + 2 * sy.Z)) : nullptr;
   sl.cur = alloc<int>(c, B);
   dev_zero(sl.cur, sizeof(int) * B);
   Work& w = c->w;
@@ -532,7 +470,7 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
   w.sb = alloc<double>(c, B * kmax * U), w.gup = alloc<double>(c, B * kmax * U);
   w.Dw = alloc<double>(c, B * kmax * RM * RM), w.JuL = alloc<double>(c, B * kmax * RM * U);
   // rows of the Newton iterate (16-row blocks; blocks of at most 8 rows with the MFMA Gram kernel)
-  w.JvW = (RM > 8 || gram_mfma()) ? alloc<double>(c, B * RM * sy.NV) : nullptr;
+  w.JvW = (RM > 8 || c->plan.rows == RowsStoredMfma) ? alloc<double>(c, B * RM * sy.NV) : nullptr;
   if (w.JvW) dev_zero(w.JvW, sizeof(double) * B * RM * sy.NV);
   w.zbP = alloc<double>(c, B * kmax * RM * sy.Z), w.gMb = alloc<double>(c, B * kmax * RM * RM);
   w.gzd = alloc<double>(c, B * kmax * RM * sy.Z), w.gWu = alloc<double>(c, B * kmax * RM * U);
@@ -556,8 +494,6 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
     dev_zero(z, sizeof(double) * 256);
     w.zeros = z;
   }
-  w.ticket = alloc<unsigned>(c, B);
-  dev_zero(w.ticket, sizeof(unsigned) * B);
   w.nfallback = alloc<int>(c, 128);  // [0] sequential fallbacks; [1 + sweeps + 16 (gsel - 1)] histogram of sweeps to convergence;
   dev_zero(w.nfallback, sizeof(int) * 128);  // [48 .. 79] phase ticks of the per-chain kernels in the diagnostic build (CHMC_RETRACT_PROF)
   c->d_itf = w.status + B, c->d_itb = w.status + 2 * B, c->d_act = alloc<int>(c, B);
@@ -612,20 +548,11 @@ static void begin_all(chmc_ctx* c, const double* d_dt, const int* d_active, doub
 // of grad_log_det_sqrt_gram that fills all of the reference's state caches, :1173-1184)
 // traj_guess: 3 when work.trajw holds the trajectory of the retraction's last iterate towards this point (the
 // time-parallel scan then needs a single sweep), 0 when nothing close is known (sequential scan)
-// With the compact rows (blocks of at most 8 rows) the state sweep does not write the rows of the step columns at all:
-// the per-operator entry points that hand rows to the caller rebuild them on demand.
-// 16-row blocks that are few enough for the row split (row_split_for > 1): the state evaluation is the two-phase sweep
-// k_newton_ivl<STATE> + k_newton_comb<STATE> (interval-parallel, compact rows only) and the row-split grad-log-det sweeps;
-// larger batches keep the stored rows (k_rev_wave_ldsrows + k_gram_rows, one wavefront per block fills the chip there).
-static bool lean16(const chmc_ctx* c) {
-  return c->sy.RM > 8 && compact16(c) && row_split_for(c) > 1;
-}
-// the layouts of the per-chain kernels, on the kernel family they are built from
-static bool chain16(const chmc_ctx* c) { return chain16_layout(c->sy.Kmax, c->sy.RM) && compact16(c) && lean16(c); }
-static bool rows_skipped(const chmc_ctx* c) { return c->sl.PB[0] != nullptr && (c->sy.RM <= 8 || lean16(c)); }
+// With the compact rows the state sweeps that need no stored rows do not write the rows of the step columns at all
+// (PartitionPlan::rebuild_rows): the per-operator entry points that hand rows to the caller rebuild them on demand.
 static void ensure_rows(chmc_ctx* c) {
 #ifdef CHMC_WAVE_KERNELS
-  if (!rows_skipped(c) || c->rows_fresh) return;
+  if (!part_plan(c).rebuild_rows || c->rows_fresh) return;
   const Sys& sy = c->sy;
   CHMC_DISPATCH(c, {
     launch(KRowsFromPB<RM, M::X, M::V>{sy, c->sl}, (long)sy.B * sy.T * sy.S, 2);
@@ -637,45 +564,47 @@ static void ensure_rows(chmc_ctx* c) {
 }
 static void state_eval_core(chmc_ctx* c, int which, bool with_grad = true, int traj_guess = 0) {
   const Sys& sy = c->sy;
+  const PartitionPlan& pp = part_plan(c);
+  (void)pp;
   c->rows_fresh = false;
   CHMC_DISPATCH(c, {
 #ifdef CHMC_WAVE_KERNELS
     CHMC_FWD(which, 0, 0, 1, traj_guess);
+    const long nbk = (long)sy.B * sy.K;
     if constexpr (RM > 8) {
-      if (lean16(c)) {  // few long 16-row blocks: interval-parallel sums, then one combine per block (compact rows only)
-        launch_blocks(k_newton_ivl<M, true>, (long)sy.B * sy.K * sy.NOBS, 64, 2, sy, c->sl, c->w, which, 0);
-        if (chain16(c))  // one block per chain: the per-chain kernels' combine (all threads) + 16-lane Cholesky, E, C_b
+      switch (pp.state) {
+        case StateIvlComb:  // few long 16-row blocks: interval-parallel sums, then one combine per block (compact rows only)
+          launch_blocks(k_newton_ivl<M, true>, nbk * sy.NOBS, 64, 2, sy, c->sl, c->w, which, 0);
+          launch_blocks(k_newton_comb<M, RM, true>, nbk, 64, 2, sy, c->sl, c->w, which, 0);
+          break;
+        case StateIvlCombWg:  // one block per chain: the per-chain kernels' combine (all threads) + 16-lane Cholesky, E, C_b
+          launch_blocks(k_newton_ivl<M, true>, nbk * sy.NOBS, 64, 2, sy, c->sl, c->w, which, 0);
           launch_blocks(k_newton_comb_wg<M, RM, CHMC_RETRACT_WAVES, true>, (long)sy.B, 64 * CHMC_RETRACT_WAVES, 2, sy, c->sl,
                         c->w, which, 0);
-        else
-          launch_blocks(k_newton_comb<M, RM, true>, (long)sy.B * sy.K, 64, 2, sy, c->sl, c->w, which, 0);
-      } else {  // 16-row blocks: store the rows, then the Gram block from the stored rows
-        launch_blocks(k_rev_wave_ldsrows<M, RM, 0>, (long)sy.B * sy.K, 64, 2, sy, c->sl, c->w, which, 0);
-        if (gram_mfma())
-          launch_blocks(k_gram_rows_mfma<RM>, (long)sy.B * sy.K, 64, 2, sy, c->sl, c->w, which, 0, 0), c->diag[0]++;
-        else
-          launch_wave(k_gram_rows<RM, 4>, (long)sy.B * sy.K * (RM / 4), 2, sy, c->sl, c->w, which, 0, 0), c->diag[1]++;
+          break;
+        case StateLdsrowsGramMfma:  // store the rows, then the Gram block from the stored rows
+          launch_blocks(k_rev_wave_ldsrows<M, RM, 0>, nbk, 64, 2, sy, c->sl, c->w, which, 0);
+          launch_blocks(k_gram_rows_mfma<RM>, nbk, 64, 2, sy, c->sl, c->w, which, 0, 0), c->diag[0]++;
+          break;
+        default:  // StateLdsrowsGram
+          launch_blocks(k_rev_wave_ldsrows<M, RM, 0>, nbk, 64, 2, sy, c->sl, c->w, which, 0);
+          launch_wave(k_gram_rows<RM, 4>, nbk * (RM / 4), 2, sy, c->sl, c->w, which, 0, 0), c->diag[1]++;
       }
     } else {
-      bool lean_state = false;
-      if constexpr (RM <= 8) {
-        if (rows_skipped(c)) {  // the state sweep at three wavefronts per SIMD (compact rows)
-          lean_state = true;
-          launch_blocks(k_newton_lean<M, RM, true, true>, (long)sy.B * sy.K, 64, 2, sy, c->sl, c->w, which, 0);
-        }
+      switch (pp.state) {
+        case StateLean:  // the state sweep at three wavefronts per SIMD (compact rows)
+          launch_blocks(k_newton_lean<M, RM, true, true>, nbk, 64, 2, sy, c->sl, c->w, which, 0);
+          break;
+        case StateRevStoreGramMfma:  // store the rows, then the Gram block from the stored rows on the matrix cores
+          launch_wave(k_rev_wave<M, RM, 0, false>, nbk, 2, sy, c->sl, c->w, which, 0);
+          launch_blocks(k_gram_rows_mfma<RM>, nbk, 64, 2, sy, c->sl, c->w, which, 0, 0), c->diag[0]++;
+          break;
+        default:  // StateRevWave
+          launch_wave(k_rev_wave<M, RM, 0>, nbk, 2, sy, c->sl, c->w, which, 0);
       }
-      if constexpr (RM <= 8) {
-        if (gram_mfma8(c)) {  // store the rows, then the Gram block from the stored rows on the matrix cores
-          lean_state = true;
-          launch_wave(k_rev_wave<M, RM, 0, false>, (long)sy.B * sy.K, 2, sy, c->sl, c->w, which, 0);
-          launch_blocks(k_gram_rows_mfma<RM>, (long)sy.B * sy.K, 64, 2, sy, c->sl, c->w, which, 0, 0), c->diag[0]++;
-        }
-      }
-      if (!lean_state) launch_wave(k_rev_wave<M, RM, 0>, (long)sy.B * sy.K, 2, sy, c->sl, c->w, which, 0);
     }
-    bool factored = false;
-    if constexpr (RM > 8) factored = chain16(c);  // (k_newton_comb_wg<.., STATE> has factored the block)
-    if (!factored) launch(KStateFactor<M, RM>{sy, c->sl, c->w, which}, (long)sy.B * sy.K, 9);
+    if (pp.state != StateIvlCombWg)  // (k_newton_comb_wg<.., STATE> has factored the block)
+      launch(KStateFactor<M, RM>{sy, c->sl, c->w, which}, nbk, 9);
 #else
     launch(KStateBlk<M, RM>{sy, c->sl, c->w, which}, (long)sy.B * sy.K, 2);
 #endif
@@ -686,41 +615,39 @@ static void state_eval_core(chmc_ctx* c, int which, bool with_grad = true, int t
       launch_blocks(k_gld_prep_wave<M, RM>, ((long)sy.B * sy.K + 3) / 4, 64, 9, sy, c->sl, c->w, which);
     else
       launch(KGldPrep<M, RM>{sy, c->sl, c->w, which}, (long)sy.B * sy.K, 9);
-    bool gld_pb = false;
-    if constexpr (RM <= 8) {
-      if (c->sl.PB[0]) {  // row-free backward sweep on Qx written by the forward sweep
-        gld_pb = true;
-        // forward sweep on X pseudo-rows (Qx directly; the row tangents only at the interval boundaries, from the state
-        // sweep's interval sums in work.ivl)
-        launch_wave(k_gld_fwd_qx<M, RM>, (long)sy.B * sy.K, 3, sy, c->sl, c->w, which);
-        launch_blocks(k_gld_bwd_lean<M, RM>, (long)sy.B * sy.K, 64, 3, sy, c->sl, c->w, which);
-      }
-    }
-    if (!gld_pb) {
-      bool fwd_done = false;
-      if constexpr (RM > 8) {
-        if (lean16(c)) {
-          // few long 16-row blocks: the row-free sweeps, every observation interval on its own wavefront
-          const long nbk = (long)sy.B * sy.K, niv = nbk * sy.NOBS;
+    switch (pp.gld) {
+      case GldQxLean:  // blocks of at most 8 rows: row-free backward sweep on Qx written by the forward sweep
+        if constexpr (RM <= 8) {
+          // forward sweep on X pseudo-rows (Qx directly; the row tangents only at the interval boundaries, from the state
+          // sweep's interval sums in work.ivl)
+          launch_wave(k_gld_fwd_qx<M, RM>, nbk, 3, sy, c->sl, c->w, which);
+          launch_blocks(k_gld_bwd_lean<M, RM>, nbk, 64, 3, sy, c->sl, c->w, which);
+        }
+        break;
+      case GldIvl:  // few long 16-row blocks: the row-free sweeps, every observation interval on its own wavefront
+        if constexpr (RM > 8) {
+          const long niv = nbk * sy.NOBS;
           launch_wave(k_gld_ivl_prologue<M, RM>, nbk, 3, sy, c->sl, c->w, which);
           launch_wave(k_gld_fwd_ivl<M, RM>, niv, 3, sy, c->sl, c->w, which);
           launch_wave(k_gld_bwd_ivl<M, RM, 0>, niv, 3, sy, c->sl, c->w, which);
           launch_wave(k_gld_bwd_ivl<M, RM, 1>, niv, 3, sy, c->sl, c->w, which);
           launch_blocks(k_gld_ivl_finish<M, RM>, (nbk + 63) / 64, 64, 3, sy, c->sl, c->w, which);
-          launch(KGldChain<M>{sy, c->sl, c->w, which}, sy.B);
-          break;
         }
-        if (compact16(c)) {  // 16-row blocks, large batches: the weights from the compact rows (DPP affine scan)
-          fwd_done = true;
-          launch_wave(k_gld_fwd_wave<M, RM, true, false>, (long)sy.B * sy.K, 3, sy, c->sl, c->w, which);
+        break;
+      case GldCompactFwdStored:  // 16-row blocks, large batches: the weights from the compact rows (DPP affine scan)
+        if constexpr (RM > 8) {
+          launch_wave(k_gld_fwd_wave<M, RM, true, false>, nbk, 3, sy, c->sl, c->w, which);
+          launch_wave(k_gld_bwd_wave_ldsrows<M, RM>, nbk, 3, sy, c->sl, c->w, which);
         }
-      }
-      if (!fwd_done) launch_wave(k_gld_fwd_wave<M, RM>, (long)sy.B * sy.K, 3, sy, c->sl, c->w, which);
-      if constexpr (RM > 8) {
-        launch_wave(k_gld_bwd_wave_ldsrows<M, RM>, (long)sy.B * sy.K, 3, sy, c->sl, c->w, which);
-      } else {
-        launch_wave(k_gld_bwd_wave<M, RM>, (long)sy.B * sy.K, 3, sy, c->sl, c->w, which);
-      }
+        break;
+      case GldStored:
+        launch_wave(k_gld_fwd_wave<M, RM>, nbk, 3, sy, c->sl, c->w, which);
+        if constexpr (RM > 8) {
+          launch_wave(k_gld_bwd_wave_ldsrows<M, RM>, nbk, 3, sy, c->sl, c->w, which);
+        } else {
+          launch_wave(k_gld_bwd_wave<M, RM>, nbk, 3, sy, c->sl, c->w, which);
+        }
+        break;
     }
 #else
     launch(KGldBlk<M, RM>{sy, c->sl, c->w, which}, (long)sy.B * sy.K, 3);
@@ -743,28 +670,8 @@ static void state_eval(chmc_ctx* c, int which) {
   project_momentum(c, which, 4, 3);
 }
 // P(q) applied in place to the slot's momentum and to pg (initialised to dh1_dpos) in one pass over the Jacobian rows
-// Element-wise passes of a step folded into their neighbours on the compact rows (CHMC_STEP_FUSIONS=0: as passes of their
-// own; the same bits):
-//  * the momentum correction of a step (KMomFixInitPg) rides in the J p pass that follows it (k_jw_pb<.., FIX>): blocks with
-//    at most 8 rows, two noise increments per step and even dimensions (16-byte pairs of p and pg);
-//  * the reverse flow of the reversibility check (KFlow) rides in the J^T lambda pass that precedes it (KUpdatePB<.., 3> with
-//    flow_rev; the u-part by a KFlow launch over the U leading columns).
-static bool step_fusions(const chmc_ctx* c) {
-#ifdef CHMC_WAVE_KERNELS
-  const char* e = getenv("CHMC_STEP_FUSIONS");
-  return c->sl.PB[0] != nullptr && !(e && atoi(e) == 0);
-#else
-  (void)c;
-  return false;
-#endif
-}
-static bool mom_fix_in_jw(const chmc_ctx* c) {
-  const Sys& sy = c->sy;
-  return step_fusions(c) && c->RMt <= 8 && sy.V == 2 && !((sy.Q | sy.U | sy.V0 | sy.NV) & 1);
-}
-// (standard splitting only: hipcc contracts the rotation q cos - p sin of the Gaussian splitting differently inside the column
-// pass -- equal to rounding, not bitwise; the switch must not change a bit)
-static bool rev_flow_in_update(const chmc_ctx* c) { return step_fusions(c) && c->RMt <= 8 && !c->sy.gaussian; }
+// fix_in_jw / flow_rev: the step's momentum correction / reverse flow ride in this pass (KernelPlan::mom_fix_in_jp,
+// rev_flow_in_update)
 static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool init_pg, bool fix_in_jw = false,
                                                 bool flow_rev = false) {
   const Sys& sy = c->sy;
@@ -773,28 +680,26 @@ static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool ini
   CHMC_DISPATCH(c, {
     // J p -> cpad, J pg -> cpad2 from one read of the compact rows (16-row blocks: PB / LF are written beside the stored
     // rows; 9 instead of 48 doubles per step) or of the stored rows
-    const bool compact = RM <= 8 ? c->sl.PB[0] != nullptr : compact16(c);
-    bool jw_done = false;
-    if constexpr (RM > 8) {
-      if (chain16(c)) {  // one block per chain: the interval sums over the wavefronts of a workgroup (k_traj_chain's form)
-        jw_done = true;
-        launch_blocks(k_jw_pb_wg<RM, M::X, M::V, CHMC_RETRACT_WAVES>, (long)sy.B, 64 * CHMC_RETRACT_WAVES, 6, sy, c->sl, c->w,
-                      which);
-      }
-    }
-    if (jw_done) {
-    } else if (compact) {
-      bool fused = false;
-      if constexpr (RM <= 8 && M::V == 2) {
-        if (fix_in_jw) {
-          fused = true;
-          launch_wave(k_jw_pb<RM, M::X, M::V, true, true>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, 256);
+    const bool compact = c->plan.rows == RowsCompact;
+    switch (part_plan(c).jp) {
+      case JpPbWg:  // one block per chain: the interval sums over the wavefronts of a workgroup (k_traj_chain's form)
+        if constexpr (RM > 8)
+          launch_blocks(k_jw_pb_wg<RM, M::X, M::V, CHMC_RETRACT_WAVES>, (long)sy.B, 64 * CHMC_RETRACT_WAVES, 6, sy, c->sl, c->w,
+                        which);
+        break;
+      case JpPb:
+        if constexpr (RM <= 8 && M::V == 2) {
+          if (fix_in_jw) {
+            launch_wave(k_jw_pb<RM, M::X, M::V, true, true>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, 256);
+            break;
+          }
         }
-      }
-      if (!fused) launch_wave(k_jw_pb<RM, M::X, M::V, true>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, 256);
+        launch_wave(k_jw_pb<RM, M::X, M::V, true>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, 256);
+        break;
+      case JpWave:
+        launch_wave(k_jw_wave<RM, true>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, 256);
+        break;
     }
-    else
-      launch_wave(k_jw_wave<RM, true>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, 256);
     // two Woodbury solves on views of the work arrays instead of copies between them: the first writes the multipliers of
     // p straight into lampad2, the second takes J pg from cpad2
     Work w1 = c->w, w2 = c->w;
@@ -806,7 +711,7 @@ static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool ini
     CHMC_SOLVE_CHAIN(M, RM, 1, 1, sy, c->sl, w2, which, 0, 3);  // multipliers of pg (and its u columns) -> lampad
     if (compact && flow_rev) {
       launch(KMuF<RM, M::X, 3>{sy, c->sl, c->w, which}, (long)sy.B * sy.K * sy.NOBS * M::X, 5);
-      launch_colmax(KUpdatePB<RM, M::X, M::V, 3, 1>{sy, c->sl, c->w, which, 0, 0, CheckArgs{}, 1},
+      launch_colmax(KUpdatePB<RM, M::X, M::V, 3, 1>{sy, c->sl, c->w, which, 0, 0, 1},
                     sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0), sy.B, 4);
     } else if (compact) {
       CHMC_UPDATE_PB(3, which, 0, 0);
@@ -825,9 +730,8 @@ static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool ini
 static void project_momentum(chmc_ctx* c, int which, int vsel, int psel) {
   const Sys& sy = c->sy;
   CHMC_DISPATCH(c, {
-    bool compact = false;
+    const bool compact = c->plan.rows == RowsCompact;
 #ifdef CHMC_WAVE_KERNELS
-    compact = RM <= 8 ? c->sl.PB[0] != nullptr : compact16(c);
     if (compact)
       launch_wave(k_jw_pb<RM, M::X, M::V>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, vsel | 256);
     else
@@ -865,81 +769,76 @@ static void iteration_scan(chmc_ctx* c, int newton, int prev, int qsel, int fwd_
 }
 // iteration_after_scan: Jacobian sweep of the iterate against the previous point's rows, block factorisations, Woodbury
 // solve, J^T lambda update of the iterate (masked by work.nw == 1)
-// chk: KCheck's arguments when the convergence check rides on the update pass (update_fuses_check), null otherwise
-// Measured and rejected (round 3): with the check on the update pass a Newton round is 5 launches instead of 6 (66.8 per
-// step), but the last-workgroup protocol costs every one of the 80 000 workgroups of a launch two RETURNING atomics: update
-// 116 -> 177 us per launch, 44.8 k -> 41.9 k steps/s (with __threadfence() instead of the dependent ticket: 1 255 us per
-// launch, the release flushes the XCD's L2).  The code path stays compiled for the record (CheckArgs, k_colmax's kFinish
-// branch) and is switched off here.
-static bool update_fuses_check(const chmc_ctx* c) {
-  (void)c;
-  return false;
-}
-static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel, const CheckArgs* chk = nullptr) {
+// (Tried and rejected, round 3: KCheck riding on the update pass through a last-workgroup ticket -- 5 launches per round instead
+// of 6, but update 116 -> 177 us per launch and 44.8 k -> 41.9 k steps/s; that code was removed, see docs/history.md.)
+static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel) {
   const Sys& sy = c->sy;
-#ifdef CHMC_WAVE_KERNELS
-  // Newton iteration on the compact rows with at most 64 blocks of at most 8 rows per chain: k_newton_fsm_wave
-  const bool fused = newton && sy.RM <= 8 && sy.K <= 64 && c->sl.PB[0] != nullptr;
-  // ... 16-row blocks, one block per chain (the SIR single-block layout): k_newton_factor_wave<.., FUSE>
-  const bool fused16 = newton && sy.RM > 8 && sy.K == 1 && compact16(c);
-#else
-  const bool fused = false, fused16 = false;
-#endif
+  const NewtonSweep sweep = part_plan(c).newton;
+  // (these sweeps go on to factor the blocks, solve the chain's core system and form lambda and mu_F)
+  const bool solved = newton && (sweep == NewtonIvlFsm || sweep == Newton16IvlCombFactor || sweep == Newton16IvlCombWg);
   CHMC_DISPATCH(c, {
     if (newton) {
 #ifdef CHMC_WAVE_KERNELS
+      const long nbk = (long)sy.B * sy.K;
       if constexpr (RM > 8) {
-        if (compact16(c)) {  // two-phase sweep on the compact rows: interval-parallel sums, then one combine per block
-          launch_blocks(k_newton_ivl<M>, (long)sy.B * sy.K * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
-          if (fused16 && chain16(c))  // (the per-chain kernels' combine + LU on 16 lanes: the same bits as k_retract_chain)
+        switch (sweep) {
+          // two-phase sweep on the compact rows: interval-parallel sums, then one combine per block
+          case Newton16IvlCombWg:  // (the per-chain kernels' combine + LU on 16 lanes: the same bits as k_retract_chain)
+            launch_blocks(k_newton_ivl<M>, nbk * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
             launch_blocks(k_newton_comb_wg<M, RM, CHMC_RETRACT_WAVES, false>, (long)sy.B, 64 * CHMC_RETRACT_WAVES, 1, sy,
                           c->sl, c->w, prev, qsel);
-          else if (fused16)  // ... whose launch goes on to factor the block, solve the chain's core system and form lambda, mu_F
-            launch_blocks(k_newton_comb<M, RM, false, true>, (long)sy.B * sy.K, 64, 1, sy, c->sl, c->w, prev, qsel);
-          else
-            launch_blocks(k_newton_comb<M, RM>, (long)sy.B * sy.K, 64, 1, sy, c->sl, c->w, prev, qsel);
-        } else {
-          launch_blocks(k_rev_wave_ldsrows<M, RM, 1>, (long)sy.B * sy.K, 64, 1, sy, c->sl, c->w, prev, qsel);
-          if (gram_mfma())
-            launch_blocks(k_gram_rows_mfma<RM>, (long)sy.B * sy.K, 64, 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[0]++;
-          else
-            launch_wave(k_gram_rows<RM, 4>, (long)sy.B * sy.K * (RM / 4), 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[1]++;
+            break;
+          case Newton16IvlCombFactor:  // one block per chain (the SIR single-block layout)
+            launch_blocks(k_newton_ivl<M>, nbk * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
+            launch_blocks(k_newton_comb<M, RM, false, true>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
+            break;
+          case Newton16IvlComb:
+            launch_blocks(k_newton_ivl<M>, nbk * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
+            launch_blocks(k_newton_comb<M, RM>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
+            break;
+          case Newton16LdsrowsGramMfma:
+            launch_blocks(k_rev_wave_ldsrows<M, RM, 1>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
+            launch_blocks(k_gram_rows_mfma<RM>, nbk, 64, 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[0]++;
+            break;
+          default:  // Newton16LdsrowsGram
+            launch_blocks(k_rev_wave_ldsrows<M, RM, 1>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
+            launch_wave(k_gram_rows<RM, 4>, nbk * (RM / 4), 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[1]++;
         }
+        // rows over 16 lanes (a 16 x 16 matrix per lane lives in scratch memory)
+        if (!solved) launch_blocks(k_newton_factor_wave<M, RM>, (nbk + 3) / 4, 64, 9, sy, c->sl, c->w, prev, qsel);
       } else {
-        if constexpr (RM <= 8) {
+        switch (sweep) {
           // two phases (interval-parallel sums + per-block combine): 25 600 seven-tile wavefronts balance better over the
           // SIMDs than 5 120 thirty-five-tile ones and the hot loop has no per-interval flush
-          if (c->sl.PB[0]) {
-            launch_blocks(k_newton_ivl<M>, (long)sy.B * sy.K * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
-            launch_blocks(k_newton_comb<M, RM>, (long)sy.B * sy.K, 64, 1, sy, c->sl, c->w, prev, qsel);
-          } else if (gram_mfma8(c)) {  // the iterate's rows into work.JvW, Gram block against the stored rows by MFMA
-            launch_wave(k_rev_wave<M, RM, 1, false>, (long)sy.B * sy.K, 1, sy, c->sl, c->w, prev, qsel);
-            launch_blocks(k_gram_rows_mfma<RM>, (long)sy.B * sy.K, 64, 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[0]++;
-          } else {
-            launch_wave(k_rev_wave<M, RM, 1>, (long)sy.B * sy.K, 1, sy, c->sl, c->w, prev, qsel);
-          }
+          case NewtonIvlFsm:
+          case NewtonIvlComb:
+            launch_blocks(k_newton_ivl<M>, nbk * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
+            launch_blocks(k_newton_comb<M, RM>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
+            break;
+          case NewtonRevStoreGramMfma:  // the iterate's rows into work.JvW, Gram block against the stored rows by MFMA
+            launch_wave(k_rev_wave<M, RM, 1, false>, nbk, 1, sy, c->sl, c->w, prev, qsel);
+            launch_blocks(k_gram_rows_mfma<RM>, nbk, 64, 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[0]++;
+            break;
+          default:  // NewtonRevWave
+            launch_wave(k_rev_wave<M, RM, 1>, nbk, 1, sy, c->sl, c->w, prev, qsel);
         }
-      }
-      if constexpr (RM > 8) {  // 16-row blocks: rows over 16 lanes (a 16 x 16 matrix per lane lives in scratch memory)
-        if (!fused16)  // (one block per chain: k_newton_comb<.., FACTOR> above has done it)
-          launch_blocks(k_newton_factor_wave<M, RM>, ((long)sy.B * sy.K + 3) / 4, 64, 9, sy, c->sl, c->w, prev, qsel);
-      } else if (fused) {  // block LU, Woodbury solve, u-columns and mu_F in one launch (wave per chain)
-        launch_blocks(k_newton_fsm_wave<M, RM>, (long)sy.B, 64, 5, sy, c->sl, c->w, prev, qsel);
-      } else {
-        launch(KNewtonFactor<M, RM>{sy, c->sl, c->w, prev}, (long)sy.B * sy.K, 9);
+        if (solved)  // block LU, Woodbury solve, u-columns and mu_F in one launch (wave per chain)
+          launch_blocks(k_newton_fsm_wave<M, RM>, (long)sy.B, 64, 5, sy, c->sl, c->w, prev, qsel);
+        else
+          launch(KNewtonFactor<M, RM>{sy, c->sl, c->w, prev}, nbk, 9);
       }
 #else
       launch(KNewtonBlk<M, RM>{sy, c->sl, c->w, prev, qsel}, (long)sy.B * sy.K, 1);
 #endif
-      if (!fused && !fused16) CHMC_SOLVE_CHAIN(M, RM, 0, 0, sy, c->sl, c->w, prev, qsel, 0);
+      if (!solved) CHMC_SOLVE_CHAIN(M, RM, 0, 0, sy, c->sl, c->w, prev, qsel, 0);
     } else {
       launch(KSymBlk<M, RM>{sy, c->sl, c->w, prev, 1}, (long)sy.B * sy.K, 9);
       CHMC_SOLVE_CHAIN(M, RM, 1, 0, sy, c->sl, c->w, prev, qsel, 0);
     }
 #ifdef CHMC_WAVE_KERNELS
-    if (RM <= 8 ? c->sl.PB[0] != nullptr : compact16(c)) {
-      if (!fused && !fused16) launch(KMuF<RM, M::X, 0>{sy, c->sl, c->w, prev}, (long)sy.B * sy.K * sy.NOBS * M::X, 5);
-      launch_colmax(KUpdatePB<RM, M::X, M::V, 0, 1>{sy, c->sl, c->w, prev, qsel, 0, chk ? *chk : CheckArgs{}},
+    if (c->plan.rows == RowsCompact) {
+      if (!solved) launch(KMuF<RM, M::X, 0>{sy, c->sl, c->w, prev}, (long)sy.B * sy.K * sy.NOBS * M::X, 5);
+      launch_colmax(KUpdatePB<RM, M::X, M::V, 0, 1>{sy, c->sl, c->w, prev, qsel, 0},
                     sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0), sy.B, 4);
     } else
 #endif
@@ -953,47 +852,31 @@ static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel, co
 // half-batches advance in lock step on the host, each on its own stream: iteration k of half 0 is enqueued, then
 // iteration k of half 1, then the read-backs are examined.
 // count_dir: -1 none, 0 / 1: add every chain's iteration count of this loop to the step's forward / reverse counter
-// (d_itf / d_itb; KAddIters, or the fused check of the update pass)
+// (d_itf / d_itb; KAddIters)
 // One 16-row block per chain on the compact rows (the SIR single-block layout): the whole Newton retraction of a chain in one
 // launch, one workgroup per chain (k_retract_chain, chmc_retract.h) -- no rounds, no read-backs, every chain iterates exactly
 // as long as it needs.  The batched path of these layouts does the same per-chain arithmetic bit for bit (k_fwd_par with the
 // same segmentation, k_newton_comb_wg, k_jw_pb_wg: tests/test_hip_parity.py::test_per_chain_kernels_equal_the_batched_path_
 // bitwise), so which of the two runs is a pure scheduling decision:
-// Wavefronts per chain of the per-chain kernels (0: the batched path).  8 while every chain has a CU to itself (two wavefronts
-// per SIMD work on ONE chain); 4 up to four chains per CU: two workgroups -- two chains -- then share a CU (one wavefront per
-// SIMD each, the same 256 registers; 75 KB of LDS each), and each chain's phases fill the other's barrier and latency gaps;
-// batched launches with 3 - 4 wavefronts per SIMD beyond that.  The arithmetic does not depend on the number of wavefronts
-// (every sum is formed by one thread or one wavefront in a fixed order; the scan has its 256 segments on four wavefronts
-// either way), nor on the execution model (tests/test_hip_parity.py::test_per_chain_kernels_equal_the_batched_path_bitwise).
-// Boarding-school SIR, steps/s by chains per GPU (8 wavefronts | 4 wavefronts | batched), profiles/r04c_bench_sir_*:
-//   256: 84.0 k | 75.9 k | 69.0 k     512: 97.1 k | 121.7 k | 103.3 k     1 024: 99.2 k | 122.8 k | 120.2 k     2 048: 106.7 k |
-//   137.7 k | 140.2 k.   CHMC_RETRACT_KERNEL=0 / 1 / 2 forces batched / 8 / 4 (read at every call).
+// chain_kernel_waves (chmc_plan.h).
 static int retract_waves(const chmc_ctx* c, int newton, const void* views) {
-#ifdef CHMC_WAVE_KERNELS
-  const char* e = getenv("CHMC_RETRACT_KERNEL");
-  int want = e ? atoi(e) : (c->sy.B <= c->num_cus ? 1 : (c->sy.B <= CHMC_CHAIN_WG4_MAX_PER_CU * c->num_cus ? 2 : 0));
-  if (!(newton && !views && c->sy.K == 1 && c->sy.RM > 8 && compact16(c))) want = 0;
-  return want == 1 ? CHMC_RETRACT_WAVES : want == 2 ? 4 : 0;
-#else
-  (void)c, (void)newton, (void)views;
-  return 0;
-#endif
+  return chain_kernel_waves(c->plan, part_plan(c).retract_chain, c->sy.B, c->num_cus, newton != 0, views != nullptr);
 }
-static bool retract_kernel(const chmc_ctx* c, int newton, const void* views) { return retract_waves(c, newton, views) != 0; }
 // ... and whole leapfrog steps -- whole trajectories -- of a chain in one launch (k_traj_chain): the same layouts with the
-// interval-parallel 16-row state evaluation (lean16), one inner h2-flow step, momenta known to be tangent, one batch.
-static bool traj_kernel(const chmc_ctx* c, int n_inner, int newton) {
-  return retract_kernel(c, newton, nullptr) && lean16(c) && n_inner == 1 && c->mom_tangent && c->halves == 1;
+// interval-parallel 16-row state evaluation, one inner h2-flow step, momenta known to be tangent, one batch.
+static int traj_waves(const chmc_ctx* c, int n_inner, int newton) {
+  const bool eligible = part_plan(c).traj_chain && n_inner == 1 && c->mom_tangent && c->halves == 1;
+  return chain_kernel_waves(c->plan, eligible, c->sy.B, c->num_cus, newton != 0, false);
 }
 static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ctol, double ptol, double dtol,
                           int max_iters, const ViewSave* views = nullptr, int count_dir = -1) {
   const Sys& sy = c->sy;
 #ifdef CHMC_WAVE_KERNELS
-  if (retract_kernel(c, newton, views)) {
+  if (const int waves = retract_waves(c, newton, views)) {
     int* iters_dst = count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf);
     CHMC_DISPATCH(c, {
       if constexpr (RM == 16) {
-        if (retract_waves(c, newton, views) == 4)
+        if (waves == 4)
           launch_blocks(k_retract_chain<M, RM, 4>, (long)sy.B, 256, 1, sy, c->sl, c->w, prev, qsel, ctol, ptol, dtol, max_iters,
                         iters_dst);
         else
@@ -1019,31 +902,22 @@ static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ct
   // sits the round out (mask 2, k_fwd_par) and its scan goes on in the next round's launch.  Rounds are therefore not
   // iterations: the loop gets up to 64 / CHMC_PAR_MAXS_ROUND + 1 rounds per iteration (KCheck enforces max_iters per chain).
 #ifdef CHMC_WAVE_KERNELS
-  const bool carry = c->par_scan && sy.K == 1;
+  const bool carry = c->plan.par_scan && sy.K == 1;
 #else
   const bool carry = false;
 #endif
   const int max_rounds = carry ? 12 * (max_iters + 1) : max_iters;
-  const bool fused_check = update_fuses_check(c);
   auto iteration = [&](int poll_slot) {  // poll_slot >= 0: the round's count of active chains goes to that pinned slot
     iteration_scan(c, newton, prev, qsel, fwd_guess, 1);
-    if (fused_check) {  // the last workgroup of a chain's update pass runs KCheck (+ KAddIters) for it
-      dev_zero(c->w.n_active, sizeof(int));
-      const CheckArgs chk{ctol, ptol, dtol, max_iters, 1, count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf)};
-      iteration_after_scan(c, newton, prev, qsel, &chk);
-    } else {
-      iteration_after_scan(c, newton, prev, qsel);
-      // (KCheck also adds a finished loop's iteration count to the step's counter -- KAddIters folded in -- and clears the
-      // next round's counter: no memset between the rounds)
-      const KCheck chk{c->w, ctol, ptol, dtol, max_iters, sy.B, count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf),
-                       c->round & 3};
-      // (the count reaches the pinned poll slot from the check's last workgroup: no copy packet behind it; A/B on one box,
-      // three interleaved runs each: configs[1] 46.3-46.8 k -> 46.7-47.1 k steps/s, SIR unchanged)
-      if (poll_slot >= 0) launch_publish(chk, sy.B, c->w.n_active + (c->round & 3), poll_slot);
-      else launch(chk, sy.B);
-      return;
-    }
-    if (poll_slot >= 0) poll_begin(poll_slot, c->w.n_active + (c->round & 3));
+    iteration_after_scan(c, newton, prev, qsel);
+    // (KCheck also adds a finished loop's iteration count to the step's counter -- KAddIters folded in -- and clears the
+    // next round's counter: no memset between the rounds)
+    const KCheck chk{c->w, ctol, ptol, dtol, max_iters, sy.B, count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf),
+                     c->round & 3};
+    // (the count reaches the pinned poll slot from the check's last workgroup: no copy packet behind it; A/B on one box,
+    // three interleaved runs each: configs[1] 46.3-46.8 k -> 46.7-47.1 k steps/s, SIR unchanged)
+    if (poll_slot >= 0) launch_publish(chk, sy.B, c->w.n_active + (c->round & 3), poll_slot);
+    else launch(chk, sy.B);
   };
   // Every kernel of an iteration is masked per chain (work.nw), so an iteration enqueued for chains that have all
   // finished is a handful of empty launches.  The host therefore never waits for the active count of iteration
@@ -1113,6 +987,7 @@ static int check_ctx(const chmc_ctx* c, const char* fn) {
 }
 #define CHMC_ENTER(fn)                 \
   if (check_ctx(ctx, fn)) return -1;   \
+  refresh_plan(ctx);                   \
   use_stream(-1);                      \
   if (dev_set(ctx->cfg.device)) return fail(std::string(fn) + ": " + g_err);
 #define CHMC_LEAVE(fn)                                                 \
@@ -1431,7 +1306,7 @@ extern "C" int chmc_switch_partition(chmc_ctx* ctx) {
 #ifdef CHMC_WAVE_KERNELS
   // the stored trajectories (valid for the partition we are leaving) seed a time-parallel pass over the whole chain
   // (the stored-rows family keeps round 1's sequential pass: the A/B test then covers both)
-  const bool par = compact_family(ctx->RMt) && ctx->have_state;
+  const bool par = ctx->plan.pb_allocated && ctx->have_state;
   if (par) {
     const Sys& so = ctx->sy;
     CHMC_DISPATCH(ctx, { launch_blocks(k_xobs_par<M>, (long)so.B, 64, 0, so, ctx->sl, ctx->d_xobs); });
@@ -1647,9 +1522,8 @@ static int nld_core(chmc_ctx* ctx, int use_gaussian_splitting, double* grad_dev)
   // for the 2 800 steps of the boarding-school SIR chains, 2.8 ms for 40 000 FitzHugh-Nagumo steps) -- for up to 1 024 chains
   // the time-parallel scan (multiple shooting over 64 segments, k_fwd_par) does it in a few sweeps, seeded with the work
   // trajectory of the previous call (the Adam-based initial-state finder and the HMC comparator evaluate nearby points
-  // call after call; a useless guess only costs sweeps).
-  const char* par_env = getenv("CHMC_PAR_SCAN");  // (as in chmc_create: 0 / 1 fixes the choice)
-  const bool par = par_env ? atoi(par_env) != 0 : few_long_blocks(1, sy.T * sy.S);
+  // call after call; a useless guess only costs sweeps).  KernelPlan::nld, from this call's CHMC_PAR_SCAN / CHMC_PAR_WAVES.
+  const bool par = ctx->plan.nld == FwdPar;
   if (par && !ctx->d_order_ident) {
     std::vector<int> id(sy.B);
     for (int i = 0; i < sy.B; ++i) id[i] = i;
@@ -1662,8 +1536,8 @@ static int nld_core(chmc_ctx* ctx, int use_gaussian_splitting, double* grad_dev)
     if (par) {
       Sys sp = sf;
       sp.order = ctx->d_order_ident;
-      CHMC_FWD_PAR(par_waves_for(sy.T * sy.S), (long)sy.B, sp, ctx->sl, ctx->w, 0, 1, 0, 2, 1, 0);
-    } else if (sy.S % 8 == 0)
+      CHMC_FWD_PAR(ctx->plan.nld_waves, (long)sy.B, sp, ctx->sl, ctx->w, 0, 1, 0, 2, 1, 0);
+    } else if (ctx->plan.nld == FwdWave)
       launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sf, ctx->sl, ctx->w, 0, 1, 0, 2);
     else
       launch(KFullScan<M>{sy, ctx->w.qb, ctx->w.trajw, QH}, sy.B, 7);
@@ -1821,7 +1695,7 @@ struct KInnerRestore {  // failed chains that had completed inner steps: back to
 // chmc_leapfrog_step in two parts: step_enqueue puts the whole step on the stream (the Newton loops wait for their
 // active-chain counts only), step_finish fetches the per-chain outputs.  `active_dev`: a device-resident mask used
 // instead of the host array (chmc_tree_step: the chains of a trajectory tree that are still running).
-// n_steps_host / n_steps_all / want_n_done: the per-chain trajectory kernel (traj_kernel) takes that many steps per chain in
+// n_steps_host / n_steps_all / want_n_done: the per-chain trajectory kernel (traj_waves) takes that many steps per chain in
 // the one launch and leaves the steps done in ctx->d_ndone; every other path takes ONE step and ignores them.
 static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, const int* active_dev, int n_inner, int newton,
                         double ctol, double ptol, double dtol, int max_iters, double rev_tol,
@@ -1859,14 +1733,14 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
     ctx->d_ncommit = alloc<int>(ctx, sy.B);
   }
 #ifdef CHMC_WAVE_KERNELS
-  if (traj_kernel(ctx, n_inner, newton)) {
+  if (const int waves = traj_waves(ctx, n_inner, newton)) {
     if (!ctx->d_nsteps) ctx->d_nsteps = alloc<int>(ctx, sy.B), ctx->d_ndone = alloc<int>(ctx, sy.B);
     if (n_steps_host) h2d(ctx->d_nsteps, n_steps_host, sizeof(int) * sy.B);
     begin_all(ctx, d_dt ? ctx->w.err : nullptr, d_active ? ctx->d_act : nullptr, 1.0);
     dev_zero(ctx->d_itf, sizeof(int) * sy.B), dev_zero(ctx->d_itb, sizeof(int) * sy.B);
     CHMC_DISPATCH(ctx, {
       if constexpr (RM == 16) {
-        if (retract_waves(ctx, newton, nullptr) == 4)
+        if (waves == 4)
           launch_blocks(k_traj_chain<M, RM, 4>, (long)sy.B, 256, 1, sy, ctx->sl, ctx->w,
                         n_steps_host ? ctx->d_nsteps : nullptr, n_steps_all, ctol, ptol, dtol, max_iters, rev_tol, ctx->d_itf,
                         ctx->d_itb, want_n_done ? ctx->d_ndone : nullptr);
@@ -1934,12 +1808,12 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
       enter(h);
       state_eval_core(ctx, 1, last, 3);  // J, factors, log det at the new point; on the last inner step dh1_dpos as well
       // momentum correction; pg <- dh1_dpos (for the step columns inside the J p pass where that is possible)
-      const bool fix_in_jw = last && mom_fix_in_jw(ctx);
+      const bool fix_in_jw = last && ctx->plan.mom_fix_in_jp;
       if (fix_in_jw)
         launch_rows(KMomFixEdges{KMomFixInitPg{sy, ctx->sl, ctx->w, 1}}, sy.U + sy.V0 + (sy.Q - sy.U - sy.NV), sy.B, 8);
       else
         launch_rows(KMomFixInitPg{sy, ctx->sl, ctx->w, 1}, sy.Q, sy.B, 8);
-      const bool flow_in_update = last && rev_flow_in_update(ctx);
+      const bool flow_in_update = last && ctx->plan.rev_flow_in_update;
       if (last)  // P p and pg = P dh1_dpos, one pass over the new Jacobian rows
         project_momentum_and_kick_direction(ctx, 1, false, fix_in_jw, flow_in_update);
       else
@@ -2040,7 +1914,7 @@ extern "C" int chmc_leapfrog_steps(chmc_ctx* ctx, const double* dt, const int* a
   const Sys& sy = ctx->sy;
   const int B = sy.B;
 #ifdef CHMC_WAVE_KERNELS
-  if (traj_kernel(ctx, n_inner, newton)) {
+  if (traj_waves(ctx, n_inner, newton)) {
     // one launch: every chain walks its own steps in its own workgroup (k_traj_chain) and stops at its first failed step
     int longest = n_steps_all;
     if (n_steps) {

@@ -159,8 +159,8 @@ struct Work {
                     //     slot: no memset between the rounds); per view: [batch | half 0 | half 1] x 4
   double* gcq;      // [B][Kmax][NOBS][2 X X + X Z] interval-parallel grad-log-det: C1 | C2 | Q0 of every interval (few long blocks)
   double* gbw;      // [B][Kmax][NOBS][X + 2 Z]     its backward sweep: x-bar handed on | z-bar sums of the two phases
-  unsigned* ticket; // [B] workgroups of a column-max launch that have finished a chain (the last one runs the launch's
-                    //     per-chain epilogue: KUpdatePB's fused convergence check)
+  unsigned* ticket; // unused (null) since the fused convergence check of KUpdatePB was removed; the slot stays so that the
+                    //     argument block of every kernel keeps its layout
   const double* zeros;  // [256] zeros (stand-in source for loads of structurally zero Jacobian entries)
   int* nfallback;   // [1] blocks the time-parallel forward scan handed to its sequential fallback (diagnostic)
 };
@@ -1457,7 +1457,7 @@ CHMC_HD inline void stv2(double* p, double2_ v, bool wide, bool two) {
 }
 template <int RM, int TGT, int VEC>
 struct KUpdate {
-  static constexpr bool kFinish = false;
+  static constexpr bool kFinish = false;  // column-max trait read by the emulation backend: no per-chain epilogue
   Sys sy;
   Slots sl;
   Work w;
@@ -1635,27 +1635,17 @@ struct KMuF {
     if (TGT == 3) w.muF2[(cb * sy.NOBS + m) * X + a] = t2;
   }
 };
-struct CheckArgs {  // KCheck's arguments riding on the Newton update pass (do_check == 0: no fused check)
-  double ctol, ptol, dtol;
-  int max_iters, do_check;
-  int* iters_dst;  // the step's iteration counter of this retraction direction (KAddIters), or null
-};
 template <int RM, int X, int V, int TGT, int NS = 1>
 struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: both lie in the same observation interval)
-  // TGT 0 with chk.do_check: the LAST workgroup to finish a chain's columns (ticket counter) runs KCheck for that chain --
-  // the lax.while_loop condition needs max |delta q|, which is complete exactly then -- and adds the finished loop's
-  // iteration count to the step's counter (KAddIters): two launches of every Newton round less.
-  static constexpr bool kFinish = TGT == 0;
+  static constexpr bool kFinish = false;  // (as KUpdate; the fused convergence check that set it for TGT 0 is gone)
   Sys sy;
   Slots sl;
   Work w;
   int which, qsel, psel;
-  CheckArgs chk;
   // TGT 3 with flow_rev: the reverse flow of the step's reversibility check (KFlow{1, 1, 0, -1}: work.qb = h2_flow(q, p, -dt))
   // for the columns of this pass, from the momentum it has just projected (the u-part: a KFlow launch over U columns;
   // standard splitting only)
   int flow_rev = 0;
-  CHMC_HD bool has_finish() const { return TGT == 0 && chk.do_check != 0; }
   CHMC_HD void rev_flow2(int c, int s, size_t i, double px, double py) const {  // KFlow's expressions, a 16-byte pair
     const double2_ q0 = ld2_stream(pick(sl.q, s) + i);
     const double dt = -1.0 * w.dt[c];
@@ -1666,23 +1656,6 @@ struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: bo
   CHMC_HD void rev_flow1(int c, int s, size_t i, double px) const {  // ... one component
     const double dt = -1.0 * w.dt[c];
     w.qb[i] = pick(sl.q, s)[i] + dt * px;
-  }
-  CHMC_HD unsigned* ticket(int c) const { return w.ticket + c; }
-  CHMC_HD void finish(int c, unsigned long long ndq_bits) const {
-    w.ticket[c] = 0u;
-    const int i = ++w.iters[c];
-    const double err = w.err[c], ndq = bitsd(ndq_bits);
-    const bool diverged = (err > chk.dtol) || (err != err);
-    const bool converged = (err < chk.ctol) && (ndq < chk.ptol);
-    if (i >= chk.max_iters || diverged || converged) {
-      w.nw[c] = 0;
-      const int st = converged ? 0 : (diverged ? 2 : 1);
-      w.nstat[c] = st;
-      if (st) w.ok[c] = 0, w.status[c] = st;
-      if (chk.iters_dst) chk.iters_dst[c] += i;
-    } else {
-      atomic_add_i32(w.n_active, 1);
-    }
   }
   CHMC_HD bool active(int c) const {
     int p_ = 0, q_ = 0;

@@ -629,7 +629,7 @@ __device__ __forceinline__ void retract_chain_body(const Sys& sy, const Slots& s
     if (tid == 0) err0 = w.err[cu], nb0 = w.ndq[cu];  // (left by the combine step; in flight under the update pass)
     unsigned long long r = 0ULL;
     {
-      const KUpdatePB<RM, X, V, 0, 1> upd{sy, sl, w, prev, qsel, 0, CheckArgs{}};
+      const KUpdatePB<RM, X, V, 0, 1> upd{sy, sl, w, prev, qsel, 0};
       for (int idx = tid; idx < ncol; idx += 64 * NW) {
         const unsigned long long v = upd(cu, idx);
         r = v > r ? v : r;
@@ -863,7 +863,7 @@ __global__ void __launch_bounds__(64 * NW, 2)
     wg_phase_sync();
     const int c12 = opaque_u(c);
     {
-      const KUpdatePB<RM, X, V, 3, 1> up3{sy, sl, w, 1, 0, 0, CheckArgs{}};
+      const KUpdatePB<RM, X, V, 3, 1> up3{sy, sl, w, 1, 0, 0};
       for (int idx = tid; idx < ncol; idx += NT) (void)up3(c12, idx);
     }
     wg_phase_sync();
