@@ -307,7 +307,11 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *   out80[65]      launches of the vector-FMA Gram kernel over stored rows (16-row blocks)
  *   out80[66]      launches of the per-chain retraction kernel (k_retract_chain: one 16-row block per chain)
  *   out80[67]      launches of the per-chain trajectory kernel (k_traj_chain: whole leapfrog steps of such a chain)
- *   out80[68 .. 79] reserved (0)
+ *   out80[68]      launches of k_newton_fsm_wave (blocks of at most 8 rows, at most 64 blocks per chain: block LU, Woodbury
+ *                  solve and mu_F of a Newton round in one launch, a wavefront per chain)
+ *   out80[69]      launches of KNewtonFactor for blocks of at most 8 rows (the unfused Newton round: more than 64 blocks per
+ *                  chain, or the stored-rows families; the chain solve and mu_F follow as launches of their own)
+ *   out80[70 .. 79] reserved (0)
  * Synchronises the context's stream. */
 int chmc_get_diagnostics(chmc_ctx* ctx, long long* out80);
 

@@ -58,7 +58,8 @@ struct chmc_ctx {
   long long counters[8];
   PlanInput plan_in{};  // layout and switches the kernel plan is decided from (chmc_plan.h)
   KernelPlan plan{};    // which kernel runs for which pass; the per-partition part is plan.part[part]
-  long long diag[16] = {0};  // launches by kernel family: [0] k_gram_rows_mfma, [1] k_gram_rows, [2] k_retract_chain, [3] k_traj_chain
+  long long diag[16] = {0};  // launches by kernel family: [0] k_gram_rows_mfma, [1] k_gram_rows, [2] k_retract_chain, [3] k_traj_chain,
+                              // [4] k_newton_fsm_wave, [5] KNewtonFactor (blocks of at most 8 rows)
   // two half-batches on two streams (chmc_leapfrog_step): chain ranges [hc0[h], hc0[h] + hB[h]) and their work orders
   int round = 0;                   // round of the current Newton loop
   int halves = 1;                  // 1: the step runs as one batch; 2: as two overlapped half-batches
@@ -823,9 +824,9 @@ static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel) {
             launch_wave(k_rev_wave<M, RM, 1>, nbk, 1, sy, c->sl, c->w, prev, qsel);
         }
         if (solved)  // block LU, Woodbury solve, u-columns and mu_F in one launch (wave per chain)
-          launch_blocks(k_newton_fsm_wave<M, RM>, (long)sy.B, 64, 5, sy, c->sl, c->w, prev, qsel);
+          launch_blocks(k_newton_fsm_wave<M, RM>, (long)sy.B, 64, 5, sy, c->sl, c->w, prev, qsel), c->diag[4]++;
         else
-          launch(KNewtonFactor<M, RM>{sy, c->sl, c->w, prev}, nbk, 9);
+          launch(KNewtonFactor<M, RM>{sy, c->sl, c->w, prev}, nbk, 9), c->diag[5]++;
       }
 #else
       launch(KNewtonBlk<M, RM>{sy, c->sl, c->w, prev, qsel}, (long)sy.B * sy.K, 1);

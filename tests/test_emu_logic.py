@@ -40,6 +40,7 @@ CASES = [
     ("sir", 14, 6, 14, True, False),
     ("fhn_nb", 7, 5, 3, False, True),  # the notebook's model: noiseless observations, Gaussian splitting
     ("fhn_nb", 6, 4, 2, True, False),
+    ("fhn", 128, 4, 2, True, False),  # K = [64, 65]: Kmax-strided per-block arrays with K[0] != K[1], past 64 blocks
 ]
 
 

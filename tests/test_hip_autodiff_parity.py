@@ -15,10 +15,13 @@ Seeds / step sizes: every step case below passes the edge condition with the see
 Seeds that were replaced: fhn_noisy_s16 106 -> 206 (chain 64, quasi-Newton: reverse |c| 9.92e-10 at the stop) and
 metric_fhn_nb_6_4_2 125 -> 425 (125: chain 2, quasi-Newton, forward |c| 9.93e-10; 225 and 325: a chain whose
 step does not succeed in either oracle); sir_two_16row_blocks 105 -> 205 (seed 105
-puts a perturbed state where a 16-row Gram block is numerically singular: the autodiff oracle's Cholesky refuses it).
+puts a perturbed state where a 16-row Gram block is numerically singular: the autodiff oracle's Cholesky refuses it);
+fhn_k65_rm7 111 -> 211 (chain 2, quasi-Newton: reverse |c| 9.96e-10 at the stop).  fhn_k65_rm7 is the 325-observation
+layout (K = [65, 66], 7 row slots), not the smaller stand-in: its test_references_agree case takes 60 to 100 s here on
+16 threads.
 
 Wall time of this module on the MI355X host: 111 s for the gpu tests (full-size SIR 42 s, full-size FHN 23 s; the whole
-`-m gpu` run 266 s); test_references_agree takes about 170 s on the CPU.  Measured distances: tests/golden/README.md."""
+`-m gpu` run 266 s); test_references_agree took about 170 s on the CPU before the four layout-edge cases and takes 330 s with them.  Measured distances: tests/golden/README.md."""
 import numpy as np
 import pytest
 import autodiff_checks as ac
@@ -29,10 +32,10 @@ REF_TOL = 1e-10  # reference vs reference: a tenth of the tightest GPU bound
 EDGE = 1e-2
 
 
-def distinct_on_manifold_chains(model, T, S, R, B, seed, obs_interval=None, var_sigma=False):
+def distinct_on_manifold_chains(model, T, S, R, B, seed, obs_interval=None, var_sigma=False, gaussian=False):
     """test_hip_parity._distinct_on_manifold_chains, also for variable observation noise (sigma_c = exp(u_c[dim_z]))."""
     from manifold_mcmc_for_diffusions_amd import example_models as em
-    case = make_case(model, T, S, R, True, B=B, seed=seed, obs_interval=obs_interval, var_sigma=var_sigma)
+    case = make_case(model, T, S, R, True, B=B, seed=seed, obs_interval=obs_interval, var_sigma=var_sigma, gaussian=gaussian)
     m, q, xo, y = em.MODELS[model], case["q"], case["x_obs"], case["y"]
     sigma = np.exp(q[:, m.dim_z])[:, None] if var_sigma else case["sigma"]
     q[:, -T:] = (y[None, :] - m.obs_func(xo)[..., 0]) / sigma
@@ -57,7 +60,7 @@ def spread_chains_by_stepping(ctx, case, part, rng, n_pre=2):
 # name: model, T, S, R, noisy, gaussian, var_sigma, B, chains, step variants (newton, n_inner, project), seed, h
 NQ = [(True, 1, True), (False, 1, True)]
 SIR16_STEPS = [(True, 1, True), (False, 1, True), (True, 2, True), (False, 2, True)]
-C37, C70 = [0, 1, 17, 31, 33, 36], [0, 1, 31, 63, 64, 69]
+C37, C70, C5 = [0, 1, 17, 31, 33, 36], [0, 1, 31, 63, 64, 69], [0, 1, 2, 3, 4]
 MID = {
     "sir16_s8": ("sir", 14, 8, 14, True, False, False, 37, C37, SIR16_STEPS, 101, 0.02),
     "sir16_s16": ("sir", 14, 16, 14, True, False, False, 37, C37, SIR16_STEPS, 102, 0.02),
@@ -68,6 +71,12 @@ MID = {
     "fhn_noiseless_gauss_s8": ("fhn", 7, 8, 3, False, True, False, 70, C70, NQ, 107, 0.05),
     "fhn_nb_noiseless_gauss_s8": ("fhn_nb", 7, 8, 3, False, True, False, 70, C70, NQ, 108, 0.05),
     "fhn_noisy_s40": ("fhn", 20, 40, 5, True, False, False, 70, C70, NQ, 109, 0.05),
+    # the layout edges of tests/test_hip_layout_edges.py, every chain judged: 64 | 65 blocks per chain (the fused and the
+    # unfused Newton round in one context), 65 | 66 blocks of 7 row slots, S = 64 (a full last tile), 16 rows with S = 65
+    "fhn_k64_65": ("fhn", 128, 4, 2, True, False, False, 5, C5, NQ, 110, 0.05),
+    "fhn_k65_rm7": ("fhn", 325, 8, 5, True, False, False, 5, C5, NQ, 211, 0.05),
+    "fhn_s64": ("fhn", 4, 64, 2, True, False, False, 5, C5, NQ, 112, 0.05),
+    "sir16_s65": ("sir", 14, 65, 14, True, False, False, 5, C5, NQ, 113, 0.02),
 }
 # M_0 != I: the parameter list of test_hip_parity.test_block_metric plus one 16-row case
 METRIC = [("fhn", 6, 4, 2, True, 120), ("fhn", 12, 16, 5, True, 121), ("fhn", 7, 8, 3, False, 122), ("sir", 6, 8, 2, True, 123),
@@ -220,7 +229,8 @@ def test_sixteen_row_kernels(name):
     """SIR T = 14, R = 14 (one 16-row block per chain: k_traj_chain, k_retract_chain, k_fwd_par, k_newton_ivl /
     k_newton_comb_wg, state_factor16 / newton_factor16, k_gld_ivl_*), S = 8 and 16, fixed and variable sigma, 37 distinct
     chains of which 6 are judged (first, last, two past index 32): every operator; steps with Newton and quasi-Newton,
-    n_inner_step 1 and 2, +dt and -dt."""
+    n_inner_step 1 and 2, +dt and -dt.  sir16_s65: S = 65 (the 64-lane tile of an interval one lane over), 5 chains, all
+    judged, n_inner_step 1."""
     ctx, traj = _gpu_case(name, MID[name])
     assert ctx.RM == 16 and ctx.K == [1]
     assert traj == 1  # k_traj_chain did the Newton, n_inner_step = 1 step
@@ -236,12 +246,31 @@ def test_two_sixteen_row_blocks_both_partitions():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", [n for n in MID if n.startswith("fhn")])
+@pytest.mark.parametrize("name", [n for n in MID if n.startswith("fhn") and not n.startswith("fhn_k")])
 def test_forward_scan_kernel(name):
     """S % 8 == 0 (k_fwd_scan), 70 distinct chains (more than one wavefront of chains) of which 6 are judged: every
-    operator in both partitions, steps with both solvers; fhn_noisy_s16 also from an unprojected momentum."""
+    operator in both partitions, steps with both solvers; fhn_noisy_s16 also from an unprojected momentum.  fhn_s64:
+    S = 64 (the last tile of an interval exactly full), 5 chains, all judged."""
     ctx, _ = _gpu_case(name, MID[name])
     assert ctx.S % 8 == 0 and ctx.num_partition == 2
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [n for n in MID if n.startswith("fhn_k")])
+def test_block_count_boundary(name):
+    """64 | 65 and 65 | 66 blocks per chain (tests/test_hip_layout_edges.py) judged by the oracle that shares no model code:
+    every operator in both partitions (past 64 blocks lmult_by_inv_gram and normal_space_component solve with
+    KSolveChain), Newton and quasi-Newton steps in partition 0, all 5 distinct chains.  The launch counters say which
+    Newton round ran: k_newton_fsm_wave (out80[68]) with 64 blocks, KNewtonFactor (out80[69]) with 65."""
+    ctx, _ = _gpu_case(name, MID[name])
+    d = ctx.diagnostics()
+    print(f"  K={ctx.K}: out80[68] = {d['newton_fsm_launches']}, out80[69] = {d['newton_factor8_launches']}")
+    assert ctx.K == {"fhn_k64_65": [64, 65], "fhn_k65_rm7": [65, 66]}[name]
+    if ctx.K[0] <= 64:  # (the steps of a case run in partition 0)
+        assert d["newton_fsm_launches"] > 0 and d["newton_factor8_launches"] == 0, d
+    else:
+        assert d["newton_fsm_launches"] == 0 and d["newton_factor8_launches"] > 0, d
     ctx.close()
 
 

@@ -72,6 +72,10 @@ LAYOUTS = {
     "sir_16rows_4blocks": layout("sir", 30, 8, 10, True, chains=8),
     "fhn_varsig": layout("fhn", 12, 10, 5, True, varsig=True, chains=4),
     "sir_varsig": layout("sir", 14, 6, 14, True, varsig=True, chains=3),
+    # 64 blocks per chain and beyond (tests/test_hip_layout_edges.py runs them on the GPU)
+    "fhn_k64_65": layout("fhn", 128, 4, 2, True, chains=5),
+    "fhn_k65_66_rm7": layout("fhn", 325, 8, 5, True, chains=5),
+    "sir_k66_67": layout("sir", 132, 4, 2, True, chains=5),
 }
 
 SWITCHES = [{}, {"CHMC_COMPACT_ROWS": "0"}, {"CHMC_GRAM_MFMA": "1"}, {"CHMC_PAR_SCAN": "0"}, {"CHMC_PAR_SCAN": "1"},
@@ -164,6 +168,7 @@ def _plan(fwd, fwd_waves, nld, nld_waves, mom_fix, rev_flow, *parts, par_scan=Fa
 
 
 _FHN = _part("lean", "ivl+comb,fsm", "qx+lean", "k_jw_pb", True)
+_COMB = _part("lean", "ivl+comb,factor,solve", "qx+lean", "k_jw_pb", True)  # more than 64 blocks per chain: the unfused round
 _SIR1 = dict(par_scan=True, fwd_cold="k_fwd_scan")
 DEFAULT_PLANS = {  # no switch set: every layout is on the compact rows
     "configs0_fhn_noisy_S50": _plan("KFwd", 1, "k_fwd_par", 4, True, True, _FHN, _FHN),
@@ -189,6 +194,9 @@ DEFAULT_PLANS = {  # no switch set: every layout is on the compact rows
     "fhn_varsig": _plan("KFwd", 1, "KFwd", 1, False, True, _FHN, _FHN),
     "sir_varsig": _plan("k_fwd_par", 4, "KFwd", 1, False, False,
                         _part("ivl+comb_wg", "ivl+comb_wg", "ivl", "k_jw_pb_wg", True, 8, 8), par_scan=True, fwd_cold="KFwd"),
+    "fhn_k64_65": _plan("KFwd", 1, "KFwd", 1, True, True, _FHN, _COMB),
+    "fhn_k65_66_rm7": _plan("k_fwd_scan", 1, "k_fwd_par", 2, False, True, _COMB, _COMB),
+    "sir_k66_67": _plan("KFwd", 1, "KFwd", 1, False, True, _COMB, _COMB),
 }
 
 _CHILD = r"""
@@ -239,6 +247,9 @@ def test_layout_integers():
     assert LAYOUTS["sir_partitioned_8rows"]["K"] == [3, 4] and LAYOUTS["sir_partitioned_8rows"]["rmt"] == 8
     assert LAYOUTS["sir_16rows_7blocks"]["K"] == [6, 7] and LAYOUTS["sir_16rows_4blocks"]["K"] == [3, 4]
     assert LAYOUTS["fhn_varsig"]["rmt"] == 8 and not LAYOUTS["fhn_varsig"]["even"]
+    assert LAYOUTS["fhn_k64_65"]["K"] == [64, 65] and LAYOUTS["fhn_k64_65"]["rmt"] == 8
+    assert LAYOUTS["fhn_k65_66_rm7"]["K"] == [65, 66] and LAYOUTS["fhn_k65_66_rm7"]["rmt"] == 7
+    assert LAYOUTS["sir_k66_67"]["K"] == [66, 67] and LAYOUTS["sir_k66_67"]["rmt"] == 8
 
 
 def test_default_plans_by_hand(probe):
@@ -246,6 +257,9 @@ def test_default_plans_by_hand(probe):
     assert set(got) == set(DEFAULT_PLANS)
     for name in LAYOUTS:
         assert got[name] == DEFAULT_PLANS[name], name
+    # K = [64, 65]: the wavefront-per-chain round (NewtonIvlFsm) holds one block per lane, so 64 blocks are its last layout
+    # and the 65 blocks of the other partition take the unfused round (NewtonIvlComb) -- in the same context
+    assert [pp["newton"] for pp in got["fhn_k64_65"]["part"]] == ["ivl+comb,fsm", "ivl+comb,factor,solve"]
 
 
 @pytest.mark.parametrize("env", SWITCHES + [{"CHMC_COMPACT_ROWS": "0", "CHMC_GRAM_MFMA": "1"}, {"CHMC_RETRACT_KERNEL": "0"},

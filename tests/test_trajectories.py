@@ -76,6 +76,7 @@ CASES = [
     ("fhn", 6, 4, 2, True, False), ("fhn", 7, 5, 3, False, False), ("fhn", 6, 4, 2, True, True),
     ("fhn", 12, 10, 5, False, True), ("sir", 5, 6, None, True, False), ("sir", 6, 8, 2, True, False),
     ("sir", 14, 6, 14, True, False),
+    ("fhn", 128, 4, 2, True, False),  # K = [64, 65]: per-block arrays strided by Kmax = 65, K[0] != K[1]
 ]
 
 

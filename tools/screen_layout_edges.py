@@ -1,0 +1,86 @@
+"""CPU screening of the cases of tests/test_hip_layout_edges.py: runs the module's run_case on the TEST-ONLY emulation
+build with every C-oracle step traced, and reports per case whether
+  * every oracle step ended with status 0, and in how many iterations,
+  * any retraction residual (|c| against constraint_tol 1e-9, |dq| against position_tol 1e-8) of any iteration of any chain
+    lies within 1e-2 relative of its tolerance -- the condition of test_hip_autodiff_parity.reference_side under which
+    "equal iteration counts" is a fair demand on the library.
+A seed that fails is replaced in the test module and noted there.
+
+    python tools/screen_layout_edges.py [case id | case id:seed to try ...]"""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import ctypes  # noqa: E402
+import subprocess  # noqa: E402
+import numpy as np  # noqa: E402
+from oracle import c_oracle  # noqa: E402
+from manifold_mcmc_for_diffusions_amd import _lib  # noqa: E402
+import test_hip_layout_edges as le  # noqa: E402
+from helpers import make_ctx  # noqa: E402
+
+EDGE = 1e-2
+
+
+def use_emulation_build():
+    emu = os.path.join(ROOT, "tests", "emu")
+    so = os.path.join(emu, "libchmc_emu.so")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-I.", "-o", so, "chmc_emu.cpp"], cwd=emu)
+    _lib._LIB = _lib._bind(ctypes.CDLL(so))
+    assert _lib.lib().chmc_backend() == b"emu:host-TEST-ONLY"
+
+
+def main(names):
+    use_emulation_build()
+    log = []
+    plain_step = c_oracle.OracleChain.step
+
+    def traced_step(self, dt, **kw):
+        out = plain_step(self, dt, **kw)
+        near = []
+        for d in (0, 1):
+            err, ndq = self.trace(d)
+            near += [(d, float(e), float(n)) for e, n in zip(err, ndq)
+                     if abs(e - 1e-9) <= EDGE * 1e-9 or abs(n - 1e-8) <= EDGE * 1e-8]
+        log.append((out[0], out[1], out[2], near))
+        return out
+
+    c_oracle.OracleChain.step = traced_step
+    bad = []
+    for name in names:
+        name, _, seed = name.partition(":")
+        cfg = le.CASES[name][:12] + (int(seed) if seed else le.CASES[name][12],)
+        del log[:]
+        t0 = time.time()
+        case = le.build_case(cfg)
+        ctx = make_ctx(case)
+        try:
+            le.run_case(ctx, case, cfg, on_device=False)
+            err = None
+        except AssertionError as e:  # (the emulation build's own mismatch, if any, is reported and the screening goes on)
+            err = str(e)[:300]
+        n_case = len(log)
+        if err is None and name in ("fhn_128_4_2_k64_65", "fhn_130_4_2_k65_66"):  # the other tests on these two cases
+            if name == "fhn_128_4_2_k64_65":
+                le.switch_body(ctx, case, cfg, on_device=False)
+                assert all(st == 0 for st, _, _, _ in log[n_case:])
+            for newton in (True, False):
+                le.masked_body(ctx, case, cfg, newton)  # (one chain fails by design)
+        ctx.close()
+        iters = [i for _, f, b, _ in log for i in (f, b)]
+        statuses = sorted({st for st, _, _, _ in log[:n_case]})
+        near = [n for _, _, _, ns in log for n in ns]
+        ok = statuses == [0] and not near and err is None
+        print(f"SCREEN {name}: seed {cfg[12]} steps {len(log)} statuses {statuses} iterations {min(iters)}..{max(iters)} "
+              f"near-edge {near} {'' if err is None else 'ASSERT ' + err} {time.time() - t0:.1f} s {'ok' if ok else 'REPLACE'}",
+              flush=True)
+        if not ok:
+            bad.append(name)
+    print("failed:", bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:] or list(le.CASES)))
