@@ -59,50 +59,85 @@ def make_ctx(case, **kw):
                        use_gaussian_splitting=case["gaussian"], num_chains=case["B"], **kw)
 
 
+def _upd(worst, k, a, b):
+    scale = max(1.0, float(np.max(np.abs(b))))
+    worst[k] = max(worst.get(k, 0.0), float(np.max(np.abs(a - b))) / scale)
+
+
+def _ops_at_point(ctx, osys, q, xo, part, rng, worst):
+    """Every per-op entry point of the C ABI at the context's current state, which the caller says is (q, xo, part)."""
+    B = ctx.B
+
+    def upd(k, a, b):
+        _upd(worst, k, a, b)
+
+    c_h = ctx.constr()
+    du_h, dv_h = ctx.jacob_constr_blocks()
+    cC, cD = ctx.chol_gram_blocks()
+    ld = ctx.log_det_sqrt_gram()
+    g = ctx.grad_log_det_sqrt_gram()
+    w = rng.standard_normal((B, ctx.Q))
+    lam = rng.standard_normal((B, ctx.dim_c))
+    Jw, JTl = ctx.lmult_by_jacob_constr(w), ctx.rmult_by_jacob_constr(lam)
+    Gil, nsc = ctx.lmult_by_inv_gram(lam), ctx.normal_space_component(w)
+    for c in range(B):
+        c_o, du_o, dv_o = osys.jacob_constr_blocks(q[c], xo[c], part)
+        cCo, cDo, ldo, go = osys.gram_ops(q[c], xo[c], part)
+        Jwo, JTlo, Gilo, nsco = osys.jacob_products(q[c], xo[c], part, w[c], lam[c])
+        rm = osys.rmax
+        upd("constr", c_h[c], c_o)
+        upd("dc_du", du_h[c], du_o)
+        upd("dc_dv", dv_h[c][:rm], dv_o)
+        if ctx.RM > rm:
+            upd("dc_dv_pad", dv_h[c][rm:], np.zeros_like(dv_h[c][rm:]))
+        upd("chol_C", cC[c], cCo)
+        for b in range(ctx.num_blocks):
+            r = osys.block_info(part, b)["nrows"]
+            upd("chol_D", cD[c][b][:r, :r], cDo[b][:r, :r])
+        upd("log_det", np.array([ld[c]]), np.array([ldo]))
+        upd("grad_log_det", g[c], go)
+        upd("lmult_jacob", Jw[c], Jwo)
+        upd("rmult_jacob", JTl[c], JTlo)
+        upd("inv_gram", Gil[c], Gilo)
+        upd("normal_space", nsc[c], nsco)
+
+
 def check_ops_against_oracle(ctx, case, tol=1e-10):
     """Every per-op entry point of the C ABI against the C oracle, for every partition; returns max rel errors."""
     osys, q, xo, B = case["osys"], case["q"], case["x_obs"], case["B"]
     rng = case["rng"]
     worst = {}
-
-    def upd(k, a, b):
-        scale = max(1.0, float(np.max(np.abs(b))))
-        worst[k] = max(worst.get(k, 0.0), float(np.max(np.abs(a - b))) / scale)
-
     for part in range(ctx.num_partition):
         p = rng.standard_normal((B, ctx.Q))
         ctx.set_state(q, p, xo, part)
-        c_h = ctx.constr()
-        du_h, dv_h = ctx.jacob_constr_blocks()
-        cC, cD = ctx.chol_gram_blocks()
-        ld = ctx.log_det_sqrt_gram()
-        g = ctx.grad_log_det_sqrt_gram()
-        w = rng.standard_normal((B, ctx.Q))
-        lam = rng.standard_normal((B, ctx.dim_c))
-        Jw, JTl = ctx.lmult_by_jacob_constr(w), ctx.rmult_by_jacob_constr(lam)
-        Gil, nsc = ctx.lmult_by_inv_gram(lam), ctx.normal_space_component(w)
-        for c in range(B):
-            c_o, du_o, dv_o = osys.jacob_constr_blocks(q[c], xo[c], part)
-            cCo, cDo, ldo, go = osys.gram_ops(q[c], xo[c], part)
-            Jwo, JTlo, Gilo, nsco = osys.jacob_products(q[c], xo[c], part, w[c], lam[c])
-            rm = osys.rmax
-            upd("constr", c_h[c], c_o)
-            upd("dc_du", du_h[c], du_o)
-            upd("dc_dv", dv_h[c][:rm], dv_o)
-            if ctx.RM > rm:
-                upd("dc_dv_pad", dv_h[c][rm:], np.zeros_like(dv_h[c][rm:]))
-            upd("chol_C", cC[c], cCo)
-            for b in range(ctx.num_blocks):
-                r = osys.block_info(part, b)["nrows"]
-                upd("chol_D", cD[c][b][:r, :r], cDo[b][:r, :r])
-            upd("log_det", np.array([ld[c]]), np.array([ldo]))
-            upd("grad_log_det", g[c], go)
-            upd("lmult_jacob", Jw[c], Jwo)
-            upd("rmult_jacob", JTl[c], JTlo)
-            upd("inv_gram", Gil[c], Gilo)
-            upd("normal_space", nsc[c], nsco)
+        _ops_at_point(ctx, osys, q, xo, part, rng, worst)
     bad = {k: v for k, v in worst.items() if not v < tol}
     assert not bad, f"op parity failures (rel err): {bad}; all: {worst}"
+    return worst
+
+
+def check_ops_at_current_state(ctx, osys, tol=1e-10, x_obs_current=True, rng=None):
+    """The body of check_ops_against_oracle WITHOUT its set_state: the state caches the context holds right now (after a
+    restore, a tree, a partition switch) are judged at the point the context reports.  Reads (q, p, x_obs, partition) back
+    with get_state(); every per-op entry point, chain by chain, against the C oracle at those points; hamiltonian()
+    against OracleChain.hamiltonian() of a chain set to the reported (q, p); the reported x_obs_seq against
+    osys.generate_x_obs_seq(q).  The library refreshes x_obs_seq in set_state and in switch_partition only (as the oracle's
+    chain does): `x_obs_current` says, for all chains or per chain, whether the position has moved since; for a chain that
+    has, the conditioned entries of x_obs_seq are still judged, through `constr`.  osys carries the context's metric."""
+    q, p, xo, part = ctx.get_state()
+    assert (ctx.M_0 is None) == (getattr(osys, "M0", None) is None), "oracle and context must have the same metric"
+    worst = {}
+    _ops_at_point(ctx, osys, q, xo, part, np.random.default_rng(0) if rng is None else rng, worst)
+    h = ctx.hamiltonian()
+    current = np.broadcast_to(np.asarray(x_obs_current, dtype=bool), (ctx.B,))
+    for c in range(ctx.B):
+        ch = c_oracle.OracleChain(osys)
+        ch.set(q[c], p[c], xo[c], part)
+        _upd(worst, "hamiltonian", np.array([h[c, 0]]), np.array([ch.hamiltonian()]))
+        if current[c]:
+            _upd(worst, "x_obs_seq", xo[c], osys.generate_x_obs_seq(q[c]))
+    bad = {k: v for k, v in worst.items() if not v < tol}
+    assert not bad, f"op parity failures at the current state (rel err): {bad}; all: {worst}"
     return worst
 
 
@@ -337,3 +372,152 @@ def check_late_inner_failure(ctx, case, dts, n_inner=2):
         assert np.abs(q2[c] - qo).max() <= 1e-9 * max(1.0, np.abs(qo).max())
         assert np.abs(p2[c] - po).max() <= 1e-8 * max(1.0, np.abs(po).max())
     return c_late
+
+
+_SOLVER_TO_ORACLE = {"max_iters": "max_iters", "reverse_check_tol": "rev_tol", "constraint_tol": "ctol", "position_tol": "ptol",
+                     "divergence_tol": "dtol", "newton": "newton", "n_inner_step": "n_inner"}
+
+
+def oracle_tree_transition(osys, q, p, x_obs, part, draw, eps, depth, max_delta_h, solver=None, W=None, extra=True):
+    """One dynamic (no-U-turn, multinomial) transition of ONE chain, every leaf an OracleChain.step and every Hamiltonian an
+    OracleChain.hamiltonian(): tests/test_dynamic.py::_reference_transition without the library.  `draw(kind, depth, leaf)`
+    hands out the chain's keyed uniforms (dynamic.TreeUniforms), `solver` is DynamicTransition's dict (its n_inner_step is
+    the oracle's n_inner), `W` the inverse of the block metric M_0 (None: identity), applied to the oracle with
+    osys.set_metric for the duration of the call unless osys already carries that metric.
+
+    Returns a dict: `q` the selected position, `n_step`, `sum_acc` = sum of min(1, exp(h0 - h)) over the leaves, `depth`
+    (doublings completed), `moved`, `logw` (the tree's log weight), `offset` (signed leaf index of the selected position
+    along the trajectory, 0 = the start), `event` -- what ended the tree: ("subtree",) a span criterion inside the new
+    sub-tree, ("extra",) one of the additional sub-tree checks while every plain span criterion of that leaf passed,
+    ("tree",) the whole-tree criterion, ("max_depth",), ("error", status, leaves taken before, doubling, leaf in it),
+    ("diverged", leaves taken before, doubling, leaf in it) --, `dirs` (direction per doubling, True = forward),
+    `edge_switches` (doublings that extend the tree from the edge the state is not sitting on), `leaves` (every
+    (doubling, leaf) the integrator was run for), `dh` (h - h0 of every leaf that was integrated without error), `ck_end`
+    (checkpoint slot: (momentum, leaves from the start) that the additional checks' buffer holds after the transition) and
+    `margins`, the smallest margin of every kind of decision taken:
+      direction / leaf / accept   |u - probability| of the draws
+      criterion                   |value| / (|dh_dmom(edge)|_2 |rho|_2) of every criterion value
+      delta_h                     |dh - max_delta_h| / max(1, |max_delta_h|)
+      constraint_tol, position_tol  relative distance of every retraction residual (OracleChain.trace: every iteration of
+                                  both retractions of the last inner step of every leaf) from its tolerance
+      reverse_check               relative distance of the step's reversibility error from reverse_check_tol."""
+    from oracle import c_oracle as co
+    from manifold_mcmc_for_diffusions_amd.dynamic import _ckpt_range
+    solver = dict(solver or {})
+    okw = {_SOLVER_TO_ORACLE[k]: v for k, v in solver.items()}
+    ctol, ptol, rtol = okw.get("ctol", 1e-9), okw.get("ptol", 1e-8), okw.get("rev_tol", 2e-8)
+    margins = {}
+
+    def note(kind, v):
+        if v == v:  # (a residual that is NaN is on no side of a tolerance)
+            margins[kind] = min(margins.get(kind, np.inf), float(v))
+
+    def vel(pp):  # dh_dmom = metric.inv @ mom
+        if W is None:
+            return pp
+        v = pp.copy()
+        v[:W.shape[0]] = W @ pp[:W.shape[0]]
+        return v
+
+    def crit(edge, rho):
+        v = vel(edge)
+        val = float(v @ rho)
+        note("criterion", abs(val) / (np.linalg.norm(v) * np.linalg.norm(rho)))
+        return val < 0
+
+    had = getattr(osys, "M0", None)
+    if W is not None and not (had is not None and np.allclose(np.linalg.inv(had), W, rtol=1e-13, atol=0)):
+        osys.set_metric(np.linalg.inv(W))
+    elif W is None and had is not None:
+        osys.set_metric(None)
+    try:
+        neg, pos = co.OracleChain(osys), co.OracleChain(osys)
+        neg.set(q, p, x_obs, part), pos.set(q, p, x_obs, part)
+        h0 = pos.hamiltonian()
+        out = dict(q=np.array(q, copy=True), n_step=0, sum_acc=0.0, depth=0, moved=False, logw=-h0, offset=0, event=("max_depth",),
+                   dirs=[], edge_switches=[], leaves=[], dh=[], margins=margins, h0=h0, ck_end={})
+        sum_mom = np.array(p, copy=True)
+        p_neg, p_pos = sum_mom.copy(), sum_mom.copy()
+        n_neg = n_pos = 0   # leaves on either side of the start
+        at_neg = at_pos = True
+        for d in range(depth):
+            u = draw(0, d, 0)
+            note("direction", abs(u - 0.5))
+            fwd = bool(u < 0.5)
+            out["dirs"].append(fwd)
+            if not (at_pos if fwd else at_neg):
+                out["edge_switches"].append(d)
+            at_pos, at_neg = fwd, not fwd
+            ch = pos if fwd else neg
+            leaves, sub_logw, sub_prop, sub_off = [], -np.inf, None, 0
+            ended = None
+            for k in range(1 << d):
+                out["leaves"].append((d, k))
+                st, _, _, rev = ch.step((1.0 if fwd else -1.0) * eps, **okw)
+                for direction in (0, 1):
+                    err, ndq = ch.trace(direction)
+                    for e, n in zip(err, ndq):
+                        note("constraint_tol", abs(e - ctol) / ctol), note("position_tol", abs(n - ptol) / ptol)
+                if st in (0, 3):
+                    note("reverse_check", abs(rev - rtol) / rtol)
+                if st != 0:
+                    ended = ("error", st, out["n_step"], d, k)
+                    break
+                h = ch.hamiltonian()
+                out["dh"].append(h - h0)
+                note("delta_h", abs(h - h0 - max_delta_h) / max(1.0, abs(max_delta_h)))
+                if not (h - h0 <= max_delta_h):
+                    ended = ("diverged", out["n_step"], d, k)
+                    break
+                q2, p2, _, _ = ch.get()
+                out["n_step"] += 1
+                out["sum_acc"] += min(1.0, np.exp(min(0.0, h0 - h)))
+                off = (n_pos + k + 1) if fwd else -(n_neg + k + 1)
+                leaves.append(p2)
+                new = np.logaddexp(sub_logw, -h)
+                prob = np.exp(-h - new)
+                u = draw(2, d, k)
+                note("leaf", abs(u - prob))
+                if u < prob:
+                    sub_prop, sub_off = q2, off
+                sub_logw = new
+                if extra and k % 2 == 1:  # KTreeLeaf / KTreeLeafFinish: the last leaf of the left half of the next larger span
+                    out["ck_end"][_ckpt_range(k)[0]] = (p2, abs(off))
+                plain = more = False
+                j = 1
+                while (k + 1) % (1 << j) == 0 and j <= d:  # aligned spans of 2^j leaves that end at this leaf
+                    a = k + 1 - (1 << j)
+                    span = np.sum(leaves[a:k + 1], axis=0)
+                    plain |= crit(leaves[a], span) | crit(leaves[k], span)
+                    if extra and j >= 2:  # the additional checks across the two halves of the span
+                        m = a + (1 << (j - 1)) - 1
+                        rho1 = np.sum(leaves[a:m + 1], axis=0) + leaves[m + 1]
+                        rho2 = np.sum(leaves[m + 1:k + 1], axis=0) + leaves[m]
+                        more |= crit(leaves[a], rho1) | crit(leaves[m + 1], rho1)
+                        more |= crit(leaves[m], rho2) | crit(leaves[k], rho2)
+                    j += 1
+                if plain or more:
+                    ended = ("subtree",) if plain else ("extra",)
+                    break
+            if ended:
+                out["event"] = ended
+                break
+            prob = np.exp(min(0.0, sub_logw - out["logw"]))
+            u = draw(1, d, 0)
+            note("accept", abs(u - prob))
+            if u < prob:
+                out["q"], out["offset"], out["moved"] = sub_prop, sub_off, True
+            out["logw"] = float(np.logaddexp(out["logw"], sub_logw))
+            out["depth"] = d + 1
+            sum_mom = sum_mom + np.sum(leaves, axis=0)
+            if fwd:
+                p_pos, n_pos = leaves[-1], n_pos + (1 << d)
+            else:
+                p_neg, n_neg = leaves[-1], n_neg + (1 << d)
+            if crit(p_neg, sum_mom) | crit(p_pos, sum_mom):
+                out["event"] = ("tree",)
+                break
+        return out
+    finally:
+        if getattr(osys, "M0", None) is not had:
+            osys.set_metric(had)
