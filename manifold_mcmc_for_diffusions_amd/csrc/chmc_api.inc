@@ -11,8 +11,10 @@
 #include <cstdlib>
 #include <cmath>
 #include <thread>
+#include <type_traits>
 #include "../../include/chmc.h"
 #include "chmc_plan.h"
+#include "chmc_layout.h"
 
 using namespace chmc;
 
@@ -23,24 +25,20 @@ static int fail(const std::string& m) {
 }
 #include CHMC_BACKEND_HEADER
 
-struct chmc_ctx {
+struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to kernels one by one: chmc_layout.h
   // Streams, poll slots and events of the backend are thread_local: a context belongs to the host thread that created it
   // (SURVEY 8b "one ctx per (device, stream); not re-entrant"); every entry point checks that instead of running on another
   // thread's (missing) streams.
   std::thread::id owner = std::this_thread::get_id();
   chmc_config cfg;
   int model, RMt, part, num_partition, npart_sum;
-  Sys sy;
   int K[2], C[2];
   std::vector<BlockDesc> hblk[2];
   BlockDesc* d_blk[2];
   int* d_obs2blk[2];
   int* d_order[2];  // wave -> (chain, block) work order of the wave-per-block kernels, longest blocks first
-  double *d_y, *d_xobs, *d_ham;
-  Slots sl;
-  Work w;
-  int *d_itf, *d_itb, *d_act;
-  unsigned long long* d_out = nullptr;  // [rev | status | iters_fwd | iters_bwd]
+  double *d_y, *d_ham;
+  unsigned long long* d_out = nullptr;  // [rev | status | iters_fwd | iters_bwd] x B (alias_step_outputs)
   BlockDesc* d_blk_full = nullptr;       // one block spanning all observations (chmc_neg_log_dens_and_grad)
   int* d_order_ident = nullptr;          // identity work order [B] for that one-block-per-chain layout
   bool mom_tangent = false;  // every chain's momentum is known to lie in the cotangent space of its current point
@@ -53,7 +51,6 @@ struct chmc_ctx {
   bool have_tree = false;
   bool rows_fresh = false;  // Slots::Jv holds the full rows of the current states (see ensure_rows)
   std::vector<unsigned char> h_out;
-  double *d_qbak = nullptr, *d_pbak = nullptr;
   std::vector<void*> allocs;
   long long counters[8];
   PlanInput plan_in{};  // layout and switches the kernel plan is decided from (chmc_plan.h)
@@ -67,11 +64,8 @@ struct chmc_ctx {
   int* d_order_half[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [partition][half]
   void* comm = nullptr;                     // RCCL communicator of chmc_comm_init (ncclComm_t)
   int comm_rank = 0, comm_world = 1;
-  double *d_q0 = nullptr, *d_p0 = nullptr;  // n_inner_step > 1: the step's start state (restored when a later inner step fails)
-  int* d_ncommit = nullptr;                 // [B] inner steps a chain has completed in the current step
   int last_n_inner = 1;
   int proj_rounds[2] = {0, 0}, proj_stable[2] = {0, 0};  // rounds the last forward / reverse retraction needed; how often in a row
-  int *d_nsteps = nullptr, *d_ndone = nullptr;  // [B] per-chain trajectory lengths / steps done (k_traj_chain)
   int num_cus = 256;                            // compute units of the device (per-chain kernels: up to 2 chains per CU)
   std::vector<double> last_dt;     // last uploaded step sizes
   std::vector<int> last_active;
@@ -83,6 +77,37 @@ static T_* alloc(chmc_ctx* c, size_t n) {
   T_* p = (T_*)dev_alloc(n * sizeof(T_));
   c->allocs.push_back(p);
   return p;
+}
+// chmc_create: every array of the list (chmc_layout.h) that this context has from the start
+static void alloc_chain_arrays(chmc_ctx* c) {
+  const size_t B = c->sy.B;
+  for_each_chain_array(*c, c->plan, c->npart_sum, [&](auto*& p, size_t per_chain, int kind, size_t slack) {
+    using T_ = std::remove_reference_t<decltype(*p)>;
+    p = nullptr;
+    if (kind & (kLazy | kAbsent)) return;
+    p = alloc<T_>(c, B * per_chain + slack);
+    if (kind & kZeroed) dev_zero(p, sizeof(T_) * (B * per_chain + slack));
+  });
+}
+// ... and one that is allocated on first use (whole-batch view only)
+template <class T_>
+static void ensure_array(chmc_ctx* c, T_*& want) {
+  if (want) return;
+  const size_t B = c->sy.B;
+  for_each_chain_array(*c, c->plan, c->npart_sum, [&](auto*& p, size_t per_chain, int, size_t slack) {
+    if ((void*)&p == (void*)&want) want = alloc<T_>(c, B * per_chain + slack);
+  });
+}
+
+// wave -> (chain, block) work order of `chains` chains, longest blocks first, on the device (`slack` spare entries)
+static int* upload_work_order(chmc_ctx* c, const std::vector<BlockDesc>& blk, int chains, int slack) {
+  const int K = (int)blk.size();
+  std::vector<int> order((size_t)chains * K);
+  for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return blk[a % K].nsteps > blk[b % K].nsteps; });
+  int* d = alloc<int>(c, order.size() + slack);
+  if (!order.empty()) h2d(d, order.data(), sizeof(int) * order.size());
+  return d;
 }
 
 // block shape tables (sde/mici_extensions.py:321-351; rows :406-411)
@@ -122,50 +147,21 @@ static void build_partition(chmc_ctx* c, int p, int init) {
 // A half-batch "view": the same structures with every per-chain array advanced to the half's first chain and B = the
 // half's chain count.  Every array is chain-major, so a kernel launched on a view works on that chain range only and
 // the two halves of a step touch disjoint memory (their active-chain counters included).
-struct ViewSave {
-  Sys sy;
-  Slots sl;
-  Work w;
-  int *d_itf, *d_itb, *d_act;
-};
-static ViewSave save_view(const chmc_ctx* c) { return ViewSave{c->sy, c->sl, c->w, c->d_itf, c->d_itb, c->d_act}; }
-static void restore_view(chmc_ctx* c, const ViewSave& f) {
-  c->sy = f.sy, c->sl = f.sl, c->w = f.w, c->d_itf = f.d_itf, c->d_itb = f.d_itb, c->d_act = f.d_act;
-}
+using ViewSave = ChainView;
+static ViewSave save_view(const chmc_ctx* c) { return *c; }
+static void restore_view(chmc_ctx* c, const ViewSave& f) { static_cast<ChainView&>(*c) = f; }
 static void set_half(chmc_ctx* c, const ViewSave& f, int h) {
   const size_t c0 = (size_t)c->hc0[h];
-  Sys sy = f.sy;
-  Slots sl = f.sl;
-  Work w = f.w;
-  const size_t Q = sy.Q, KM = sy.Kmax, RM = sy.RM, U = sy.U, X = sy.X, Z = sy.Z, TRJ = sy.TRJ, NV = sy.NV;
-  sy.B = c->hB[h];
-  sy.xobs += c0 * sy.T * X;
-  sy.order = c->d_order_half[c->part][h];
-#define CHMC_OFF(p, stride) ((p) ? (void)((p) += c0 * (size_t)(stride)) : (void)0)
-  for (int s = 0; s < 2; ++s) {
-    CHMC_OFF(sl.q[s], Q), CHMC_OFF(sl.p[s], Q), CHMC_OFF(sl.grad[s], Q), CHMC_OFF(sl.pg[s], Q);
-    CHMC_OFF(sl.traj[s], TRJ), CHMC_OFF(sl.JuP[s], KM * RM * U), CHMC_OFF(sl.E[s], KM * RM * U);
-    CHMC_OFF(sl.Jv[s], RM * NV), CHMC_OFF(sl.facD[s], KM * RM * RM), CHMC_OFF(sl.facC[s], U * U);
-    CHMC_OFF(sl.Cinv[s], U * U), CHMC_OFF(sl.ldb[s], KM), CHMC_OFF(sl.logdet[s], 1);
-    CHMC_OFF(sl.PB[s], (size_t)sy.T * sy.S * X * sy.V), CHMC_OFF(sl.LF[s], KM * sy.NOBS * RM * X);
-  }
-  CHMC_OFF(w.muF, KM * sy.NOBS * X), CHMC_OFF(w.muF2, KM * sy.NOBS * X);
-  CHMC_OFF(w.ivl, KM * sy.NOBS * (2 * X * X + X * Z));
-  CHMC_OFF(w.gcq, KM * sy.NOBS * (2 * X * X + X * Z)), CHMC_OFF(w.gbw, KM * sy.NOBS * (X + 2 * Z));
-  CHMC_OFF(sl.cur, 1);
-  CHMC_OFF(w.trajw, TRJ), CHMC_OFF(w.cpad, KM * RM), CHMC_OFF(w.cpad2, KM * RM), CHMC_OFF(w.lampad2, KM * RM);
-  CHMC_OFF(w.tpad, KM * RM), CHMC_OFF(w.lampad, KM * RM), CHMC_OFF(w.Ew, KM * RM * U), CHMC_OFF(w.Cb, KM * U * U);
-  CHMC_OFF(w.sb, KM * U), CHMC_OFF(w.mu, Q), CHMC_OFF(w.qb, Q), CHMC_OFF(w.pb, Q), CHMC_OFF(w.vin, Q);
-  CHMC_OFF(w.Xd, (size_t)sy.T * sy.S * RM * X), CHMC_OFF(w.gup, KM * U), CHMC_OFF(w.JvW, RM * NV);
-  CHMC_OFF(w.Dw, KM * RM * RM), CHMC_OFF(w.JuL, KM * RM * U), CHMC_OFF(w.zbP, KM * RM * Z);
-  CHMC_OFF(w.gMb, KM * RM * RM), CHMC_OFF(w.gzd, KM * RM * Z), CHMC_OFF(w.gWu, KM * RM * U);
-  CHMC_OFF(w.gxdt, KM * RM * X), CHMC_OFF(w.sdt, 1), CHMC_OFF(w.cdt, 1), CHMC_OFF(w.err, 1), CHMC_OFF(w.ndq, 1);
-  CHMC_OFF(w.rev, 1), CHMC_OFF(w.dt, 1), CHMC_OFF(w.part, (size_t)c->npart_sum * 2), CHMC_OFF(w.iters, 1);
-  CHMC_OFF(w.nw, 1), CHMC_OFF(w.ok, 1), CHMC_OFF(w.status, 1), CHMC_OFF(w.nstat, 1);
-  w.n_active = f.w.n_active + 4 * (1 + h);
-  c->sy = sy, c->sl = sl, c->w = w;
-  c->d_itf = f.d_itf + c0, c->d_itb = f.d_itb + c0, c->d_act = f.d_act + c0;
-#undef CHMC_OFF
+  ChainView& v = *c;
+  v = f;
+  for_each_chain_array(v, c->plan, c->npart_sum, [&](auto*& p, size_t per_chain, int, size_t) {
+    if (p) p += c0 * per_chain;
+  });
+  alias_step_outputs(v, c->d_out, f.sy.B, c0);
+  v.sy.B = c->hB[h];
+  v.sy.xobs = v.d_xobs;
+  v.sy.order = c->d_order_half[c->part][h];
+  v.w.n_active = f.w.n_active + 4 * (1 + h);
   use_stream(h);
 }
 
@@ -369,7 +365,8 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
   c->RMt = rmax <= 8 ? 8 : 16;
   if (fhn && !sy.varsig && (rmax == 6 || (rmax == 7 && cfg->model == CHMC_MODEL_FHN))) c->RMt = rmax;  // R = 5 with noisy (7) / noiseless (6) observations (BASELINE configs 1-3, 5): exact row count, no padded slot
   sy.RM = c->RMt, sy.Kmax = kmax, sy.TRJ = (sy.T * sy.S + CHMC_TPAD * kmax) * sy.X;
-  const size_t B = sy.B, Q = sy.Q, RM = sy.RM, U = sy.U;
+  const size_t B = sy.B;
+  c->hB[0] = sy.B / 2, c->hB[1] = sy.B - sy.B / 2, c->hc0[0] = 0, c->hc0[1] = sy.B / 2;
   for (int p = 0; p < c->num_partition; ++p) {
     c->d_blk[p] = alloc<BlockDesc>(c, c->K[p]);
     h2d(c->d_blk[p], c->hblk[p].data(), sizeof(BlockDesc) * c->K[p]);
@@ -383,26 +380,10 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
     // short first / last sub-sequences of partition 1 land anywhere and the last round runs a few long blocks on an
     // otherwise idle chip (partition-1 steps were 7 % slower than partition-0 steps for the same total work).
     // Longest-processing-time-first puts the short blocks at the end, where they fill the tail.
-    const int K = c->K[p];
-    std::vector<int> order((size_t)sy.B * K);
-    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b2) {
-      return c->hblk[p][a % K].nsteps > c->hblk[p][b2 % K].nsteps;
-    });
-    c->d_order[p] = alloc<int>(c, order.size());
-    h2d(c->d_order[p], order.data(), sizeof(int) * order.size());
-    for (int h = 0; h < 2; ++h) {  // the same list schedule for the chains of one half-batch
-      const int Bh = h == 0 ? sy.B / 2 : sy.B - sy.B / 2;
-      std::vector<int> oh((size_t)Bh * K);
-      for (size_t i = 0; i < oh.size(); ++i) oh[i] = (int)i;
-      std::stable_sort(oh.begin(), oh.end(), [&](int a, int b2) {
-        return c->hblk[p][a % K].nsteps > c->hblk[p][b2 % K].nsteps;
-      });
-      c->d_order_half[p][h] = alloc<int>(c, oh.size() + 1);
-      if (!oh.empty()) h2d(c->d_order_half[p][h], oh.data(), sizeof(int) * oh.size());
-    }
+    c->d_order[p] = upload_work_order(c, c->hblk[p], sy.B, 0);
+    // the same list schedule for the chains of one half-batch
+    for (int h = 0; h < 2; ++h) c->d_order_half[p][h] = upload_work_order(c, c->hblk[p], c->hB[h], 1);
   }
-  c->hB[0] = sy.B / 2, c->hB[1] = sy.B - sy.B / 2, c->hc0[0] = 0, c->hc0[1] = sy.B / 2;
   {
     PlanInput& in = c->plan_in;
     in.rmt = c->RMt, in.num_partition = c->num_partition, in.K[0] = c->K[0], in.K[1] = c->K[c->num_partition - 1];
@@ -429,67 +410,13 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
   }
   c->d_y = alloc<double>(c, sy.T);
   h2d(c->d_y, cfg->y_seq, sizeof(double) * sy.T);
-  c->d_xobs = alloc<double>(c, B * sy.T * sy.X);
-  dev_zero(c->d_xobs, sizeof(double) * B * sy.T * sy.X);
-  sy.y = c->d_y, sy.xobs = c->d_xobs;
-  Slots& sl = c->sl;
-  for (int s = 0; s < 2; ++s) {
-    sl.q[s] = alloc<double>(c, B * Q + CHMC_Q_PAD), sl.p[s] = alloc<double>(c, B * Q), sl.grad[s] = alloc<double>(c, B * Q);
-    sl.pg[s] = alloc<double>(c, B * Q);
-    sl.traj[s] = alloc<double>(c, B * sy.TRJ);
-    sl.JuP[s] = alloc<double>(c, B * kmax * RM * U), sl.E[s] = alloc<double>(c, B * kmax * RM * U);
-    sl.Jv[s] = alloc<double>(c, B * RM * sy.NV);
-    sl.facD[s] = alloc<double>(c, B * kmax * RM * RM);
-    sl.facC[s] = alloc<double>(c, B * U * U), sl.Cinv[s] = alloc<double>(c, B * U * U);
-    sl.ldb[s] = alloc<double>(c, B * kmax), sl.logdet[s] = alloc<double>(c, B);
-    dev_zero(sl.q[s], sizeof(double) * (B * Q + CHMC_Q_PAD)), dev_zero(sl.p[s], sizeof(double) * B * Q);
-    dev_zero(sl.grad[s], sizeof(double) * B * Q);
-    dev_zero(sl.Jv[s], sizeof(double) * B * RM * sy.NV);
-    sl.PB[s] = sl.LF[s] = nullptr;
-    if (c->plan.pb_allocated) {  // compact form of the stored rows for the Newton-loop passes (chmc_core.h, Slots)
-      sl.PB[s] = alloc<double>(c, B * sy.T * sy.S * sy.X * sy.V);
-      sl.LF[s] = alloc<double>(c, B * kmax * sy.NOBS * RM * sy.X);
-      dev_zero(sl.PB[s], sizeof(double) * B * sy.T * sy.S * sy.X * sy.V);
-      dev_zero(sl.LF[s], sizeof(double) * B * kmax * sy.NOBS * RM * sy.X);
-    }
-  }
-  const bool pb = c->plan.pb_allocated;
-  c->w.muF = pb ? alloc<double>(c, B * kmax * sy.NOBS * sy.X) : nullptr;
-  c->w.muF2 = pb ? alloc<double>(c, B * kmax * sy.NOBS * sy.X) : nullptr;
-  c->w.ivl = pb ? alloc<double>(c, B * kmax * sy.NOBS * (2 * sy.X * sy.X + sy.X * sy.Z)) : nullptr;
-  c->w.gcq = pb && RM > 8 ? alloc<double>(c, B * kmax * sy.NOBS * (2 * sy.X * sy.X + sy.X * sy.Z)) : nullptr;
-  c->w.gbw = pb && RM > 8 ? alloc<double>(c, B * kmax * sy.NOBS * (sy.X + 2 * sy.Z)) : nullptr;
-  sl.cur = alloc<int>(c, B);
-  dev_zero(sl.cur, sizeof(int) * B);
-  Work& w = c->w;
   c->npart_sum = rowsum_groups(sy.Q);
-  w.trajw = alloc<double>(c, B * sy.TRJ);
-  w.cpad = alloc<double>(c, B * kmax * RM), w.tpad = alloc<double>(c, B * kmax * RM);
-  w.lampad = alloc<double>(c, B * kmax * RM);
-  w.cpad2 = alloc<double>(c, B * kmax * RM), w.lampad2 = alloc<double>(c, B * kmax * RM);
-  w.Ew = alloc<double>(c, B * kmax * RM * U), w.Cb = alloc<double>(c, B * kmax * U * U);
-  w.sb = alloc<double>(c, B * kmax * U), w.gup = alloc<double>(c, B * kmax * U);
-  w.Dw = alloc<double>(c, B * kmax * RM * RM), w.JuL = alloc<double>(c, B * kmax * RM * U);
-  // rows of the Newton iterate (16-row blocks; blocks of at most 8 rows with the MFMA Gram kernel)
-  w.JvW = (RM > 8 || c->plan.rows == RowsStoredMfma) ? alloc<double>(c, B * RM * sy.NV) : nullptr;
-  if (w.JvW) dev_zero(w.JvW, sizeof(double) * B * RM * sy.NV);
-  w.zbP = alloc<double>(c, B * kmax * RM * sy.Z), w.gMb = alloc<double>(c, B * kmax * RM * RM);
-  w.gzd = alloc<double>(c, B * kmax * RM * sy.Z), w.gWu = alloc<double>(c, B * kmax * RM * U);
-  w.gxdt = alloc<double>(c, B * kmax * RM * sy.X);
-  w.sdt = alloc<double>(c, B), w.cdt = alloc<double>(c, B);
-  dev_zero(w.sdt, sizeof(double) * B), dev_zero(w.cdt, sizeof(double) * B);
-  w.mu = alloc<double>(c, B * Q), w.qb = alloc<double>(c, B * Q + CHMC_Q_PAD), w.pb = alloc<double>(c, B * Q);
-  dev_zero(w.qb, sizeof(double) * (B * Q + CHMC_Q_PAD));
-  w.vin = alloc<double>(c, B * Q);
-  w.Xd = alloc<double>(c, B * sy.T * sy.S * RM * sy.X);
-  w.err = alloc<double>(c, B), w.dt = alloc<double>(c, B);
-  // per-step outputs of chmc_leapfrog_step live in one allocation so that they cross PCIe in a single copy:
-  // [rev (8 B) | status | iters_fwd | iters_bwd] x B
-  c->d_out = alloc<unsigned long long>(c, B + (3 * B * sizeof(int) + 7) / 8);
-  w.ndq = alloc<unsigned long long>(c, B), w.rev = c->d_out;
-  w.part = alloc<double>(c, B * c->npart_sum * 2);
-  w.iters = alloc<int>(c, B), w.nw = alloc<int>(c, B), w.ok = alloc<int>(c, B);
-  w.status = reinterpret_cast<int*>(c->d_out + B), w.nstat = alloc<int>(c, B), w.n_active = alloc<int>(c, 12);  // [batch | half 0 | half 1] x 4 round slots
+  alloc_chain_arrays(c);  // every per-chain array: chmc_layout.h
+  sy.y = c->d_y, sy.xobs = c->d_xobs;
+  c->d_out = alloc<unsigned long long>(c, step_outputs_words(B));
+  alias_step_outputs(*c, c->d_out, B, 0);
+  Work& w = c->w;
+  w.n_active = alloc<int>(c, 12);  // [batch | half 0 | half 1] x 4 round slots
   {
     double* z = alloc<double>(c, 256);
     dev_zero(z, sizeof(double) * 256);
@@ -497,12 +424,7 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
   }
   w.nfallback = alloc<int>(c, 128);  // [0] sequential fallbacks; [1 + sweeps + 16 (gsel - 1)] histogram of sweeps to convergence;
   dev_zero(w.nfallback, sizeof(int) * 128);  // [48 .. 79] phase ticks of the per-chain kernels in the diagnostic build (CHMC_RETRACT_PROF)
-  c->d_itf = w.status + B, c->d_itb = w.status + 2 * B, c->d_act = alloc<int>(c, B);
   c->d_ham = alloc<double>(c, B * 4);  // [B][3] Hamiltonian terms; chmc_adam_objective_device: values [B] + statistics [B][3]
-  dev_zero(w.cpad, sizeof(double) * B * kmax * RM);
-  dev_zero(w.lampad, sizeof(double) * B * kmax * RM);
-  dev_zero(w.cpad2, sizeof(double) * B * kmax * RM), dev_zero(w.lampad2, sizeof(double) * B * kmax * RM);
-  dev_zero(w.dt, sizeof(double) * B);
   select_partition(c, 0);
   if (dev_sync()) {
     std::string e = g_err;
@@ -1217,10 +1139,7 @@ struct KSnapshot {
 extern "C" int chmc_snapshot(chmc_ctx* ctx) {
   CHMC_ENTER("chmc_snapshot")
   const Sys& sy = ctx->sy;
-  if (!ctx->d_qbak) {
-    ctx->d_qbak = alloc<double>(ctx, (size_t)sy.B * sy.Q);
-    ctx->d_pbak = alloc<double>(ctx, (size_t)sy.B * sy.Q);
-  }
+  ensure_array(ctx, ctx->d_qbak), ensure_array(ctx, ctx->d_pbak);
   launch(KSnapshot{sy, ctx->sl, ctx->d_qbak, ctx->d_pbak, 0, nullptr}, (long)sy.B * sy.Q, 8);
   ctx->snap_tangent = ctx->mom_tangent;
   CHMC_LEAVE("chmc_snapshot")
@@ -1728,14 +1647,10 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
   } else {
     ctx->last_active_null = true;
   }
-  if (n_inner > 1 && !ctx->d_q0) {
-    ctx->d_q0 = alloc<double>(ctx, (size_t)sy.B * sy.Q);
-    ctx->d_p0 = alloc<double>(ctx, (size_t)sy.B * sy.Q);
-    ctx->d_ncommit = alloc<int>(ctx, sy.B);
-  }
+  if (n_inner > 1) ensure_array(ctx, ctx->d_q0), ensure_array(ctx, ctx->d_p0), ensure_array(ctx, ctx->d_ncommit);
 #ifdef CHMC_WAVE_KERNELS
   if (const int waves = traj_waves(ctx, n_inner, newton)) {
-    if (!ctx->d_nsteps) ctx->d_nsteps = alloc<int>(ctx, sy.B), ctx->d_ndone = alloc<int>(ctx, sy.B);
+    ensure_array(ctx, ctx->d_nsteps), ensure_array(ctx, ctx->d_ndone);
     if (n_steps_host) h2d(ctx->d_nsteps, n_steps_host, sizeof(int) * sy.B);
     begin_all(ctx, d_dt ? ctx->w.err : nullptr, d_active ? ctx->d_act : nullptr, 1.0);
     dev_zero(ctx->d_itf, sizeof(int) * sy.B), dev_zero(ctx->d_itb, sizeof(int) * sy.B);
@@ -1773,16 +1688,15 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
   const double kick = 0.5 * n_inner;
   auto enter = [&](int h) {
     if (two) set_half(ctx, full, h);
-    return (size_t)(two ? ctx->hc0[h] : 0);
   };
   if (two) streams_fork();
   for (int h = 0; h < nh; ++h) {
-    const size_t c0 = enter(h);
+    enter(h);
     begin_all(ctx, d_dt ? ctx->w.err : nullptr, d_active ? ctx->d_act : nullptr, 1.0 / n_inner);
     dev_zero(ctx->d_itf, sizeof(int) * sy.B), dev_zero(ctx->d_itb, sizeof(int) * sy.B);
     if (n_inner > 1) {
-      dev_zero(ctx->d_ncommit + c0, sizeof(int) * sy.B);
-      launch(KGatherState{sy, ctx->sl, ctx->d_q0 + c0 * sy.Q, ctx->d_p0 + c0 * sy.Q}, (long)sy.B * sy.Q, 8);
+      dev_zero(ctx->d_ncommit, sizeof(int) * sy.B);
+      launch(KGatherState{sy, ctx->sl, ctx->d_q0, ctx->d_p0}, (long)sy.B * sy.Q, 8);
     }
   }
   for (int i = 0; i < n_inner; ++i) {
@@ -1825,7 +1739,7 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
     }
     run_projection(ctx, newton, 1, 1, ctol, ptol, dtol, max_iters, two ? &full : nullptr, 1);
     for (int h = 0; h < nh; ++h) {
-      const size_t c0 = enter(h);
+      enter(h);
       launch_colmax(KRevDiff{sy, ctx->sl, ctx->w}, (sy.Q + 1) / 2, sy.B, 8);
       launch(KRevCheck{ctx->w, rev_tol}, sy.B);
       if (last) {
@@ -1833,7 +1747,7 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
         if (!skip_end_kick) launch_rows(KKickPg{sy, ctx->sl, ctx->w, 1, 0, kick}, sy.Q, sy.B, 8);
         launch(KCommit{ctx->sl, ctx->w}, sy.B);
       } else {
-        launch(KCommitInner{ctx->sl, ctx->w, ctx->d_ncommit + c0}, sy.B);
+        launch(KCommitInner{ctx->sl, ctx->w, ctx->d_ncommit}, sy.B);
       }
     }
   }

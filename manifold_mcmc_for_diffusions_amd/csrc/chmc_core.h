@@ -89,6 +89,8 @@ CHMC_HD inline double metric_mul_u(const Sys& sy, const double* vu, int a) {
   return t;
 }
 
+// Slots and Work: the shapes in the comments repeat chmc_layout.h, the ONE place that sizes, allocates and offsets these
+// arrays (for_each_chain_array); an array added here gets its entry there.
 struct Slots {
   double* q[2];
   double* p[2];
@@ -150,8 +152,6 @@ struct Work {
   int* iters;       // [B]
   int* nw;          // [B] Newton loop: 0 finished, 1 iterating, 2 the time-parallel forward scan of the current iterate has
                     //     not settled yet: the chain sits this round out and its scan goes on in the next (k_fwd_par, K = 1)
-                    //     forward-retraction mask in `nw`; one merged scan serves both groups, each chain with its own
-                    //     (slot, iterate) selection.  Null outside the engine.
   int* ok;          // [B] chain still good in this step
   int* status;      // [B]
   int* nstat;       // [B] status of last projection
@@ -162,7 +162,7 @@ struct Work {
   unsigned* ticket; // unused (null) since the fused convergence check of KUpdatePB was removed; the slot stays so that the
                     //     argument block of every kernel keeps its layout
   const double* zeros;  // [256] zeros (stand-in source for loads of structurally zero Jacobian entries)
-  int* nfallback;   // [1] blocks the time-parallel forward scan handed to its sequential fallback (diagnostic)
+  int* nfallback;   // [128] diagnostics; [0]: blocks the time-parallel forward scan handed to its sequential fallback
 };
 
 // slot selection as an explicit select: indexing the by-value kernel-argument pointer pairs with a run-time slot

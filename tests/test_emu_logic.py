@@ -231,6 +231,16 @@ def test_half_batches_equal_one_batch(emu_lib, monkeypatch, model, T, S, R, nois
         halves_vs_single_batch(case, monkeypatch, part=part, newton=newton, masked=(1, 6), failing=(2, 4))
 
 
+def test_half_batches_equal_one_batch_sixteen_row_blocks(emu_lib, monkeypatch):
+    """The same with 16-row blocks, K = [2, 3] (SIR, 13 observations per sub-sequence, interval 0.1): the views of every array
+    with RM = 16 row slots per block.  (One 16-row block per chain always runs as one batch.)"""
+    from helpers import halves_vs_single_batch
+    case = make_case("sir", 26, 24, 13, True, B=7, seed=81, obs_interval=0.1)
+    for part in range(2):
+        a = halves_vs_single_batch(case, monkeypatch, part=part, masked=(1, 6), failing=(2, 4))
+        assert a[2][0]["status"].tolist() == [0, -1, 2, 0, 2, 0, -1]  # masked, diverged, the others accepted
+
+
 @pytest.mark.parametrize("model,T,S,R,noisy,gaussian,newton,n_inner", [
     ("fhn", 6, 4, 2, True, False, True, 2), ("fhn", 7, 5, 3, False, True, True, 3), ("fhn", 12, 10, 5, True, False, False, 2),
     ("sir", 6, 8, 2, True, False, True, 2)])

@@ -743,9 +743,52 @@ def test_inner_steps_with_half_batches(monkeypatch):
             assert np.array_equal(a[k], b[k]), k
 
 
+@pytest.mark.parametrize("row_split", [None, "1"])
+def test_half_batches_sixteen_row_blocks(monkeypatch, row_split):
+    """Half-batch views of the arrays that only 16-row layouts with several blocks per chain have (one 16-row block per chain
+    always runs as one batch): SIR (26, 24, 13) at 0.1, K = [2, 3], 7 chains (3 / 4), both partitions, bitwise against the
+    one-batch step.  Default switches: the interval-parallel sweeps (work.gcq, gbw, ivl, Slots::PB, LF with 16 row slots);
+    CHMC_ROW_SPLIT=1: the stored-rows 16-row sweeps (work.JvW and Slots::Jv with 16 row slots)."""
+    from helpers import halves_vs_single_batch
+    if row_split:
+        monkeypatch.setenv("CHMC_ROW_SPLIT", row_split)
+    case = make_case("sir", 26, 24, 13, True, B=7, seed=81, obs_interval=0.1)
+    for part in range(2):
+        halves_vs_single_batch(case, monkeypatch, part=part, masked=(1, 6), failing=(2, 4))
+
+
+_HALVES_FAMILY_SCRIPT = r"""
+import os, sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+from helpers import make_case, make_ctx, halves_vs_single_batch
+class Env:  # (halves_vs_single_batch sets CHMC_HALVES for its two runs)
+    setenv = staticmethod(os.environ.__setitem__)
+case = make_case("fhn", 12, 16, 5, True, B=7, seed=81)
+ctx = make_ctx(case)
+assert ctx.L.chmc_backend() == b"hip:gfx950"
+ctx.close()
+for part in range(2):
+    halves_vs_single_batch(case, Env, part=part, masked=(1, 6), failing=(2, 4))
+print("HALVES_FAMILY_OK")
+"""
+
+
+def test_half_batches_stored_row_families():
+    """The same for the two row families that are latched per process, a child process each: CHMC_COMPACT_ROWS=0 (every pass
+    over Slots::Jv) and CHMC_GRAM_MFMA=1 (work.JvW with blocks of at most 8 rows) on FHN (12, 16, 5, noisy), 7 chains, both
+    partitions.  One child at a time, each under a time limit; nothing is started after a failure."""
+    import subprocess
+    for env in ({"CHMC_COMPACT_ROWS": "0"}, {"CHMC_GRAM_MFMA": "1"}):
+        script = _HALVES_FAMILY_SCRIPT.format(root=ROOT, tests=os.path.join(ROOT, "tests"))
+        r = subprocess.run([sys.executable, "-c", script], env={**os.environ, **env}, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, (env, r.stdout[-3000:] + r.stderr[-3000:])
+        assert "HALVES_FAMILY_OK" in r.stdout
+
+
 # variable observation noise: sigma = generate_σ_y(u) = exp(u[dim_z]), dim_u = dim_z + 1
 # (sde/mici_extensions.py:353-358, 559-569, 601-608; scripts/sir_model_chmc_experiment.py:44,58,77)
-VS_CASES = [("sir", 5, 6, None, False), ("sir", 6, 8, 2, False), ("sir", 6, 16, 2, False), ("fhn", 6, 8, 2, False),
+VS_CASES =[("sir", 5, 6, None, False), ("sir", 6, 8, 2, False), ("sir", 6, 16, 2, False), ("fhn", 6, 8, 2, False),
             ("fhn", 7, 5, 3, True), ("sir", 14, 8, 14, False)]
 
 
