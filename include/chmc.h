@@ -311,7 +311,12 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *                  solve and mu_F of a Newton round in one launch, a wavefront per chain)
  *   out80[69]      launches of KNewtonFactor for blocks of at most 8 rows (the unfused Newton round: more than 64 blocks per
  *                  chain, or the stored-rows families; the chain solve and mu_F follow as launches of their own)
- *   out80[70 .. 79] reserved (0)
+ *   out80[70]      rounds of the lock-step Newton loops whose forward scan served two problems at once: the reverse
+ *                  retraction of a trajectory's step and the forward retraction of its next step (one merged scan launch;
+ *                  CHMC_PAIR_RETRACT=0 switches the pairing off)
+ *   out80[71]      forward-scan launches of the lock-step Newton loops (a merged launch counts once)
+ *   out80[72]      rounds those loops enqueued, counted per problem: with the hand-scheduled scan, [71] = [72] - [70]
+ *   out80[73 .. 79] reserved (0)
  * Synchronises the context's stream. */
 int chmc_get_diagnostics(chmc_ctx* ctx, long long* out80);
 

@@ -411,7 +411,8 @@ class ChmcContext:
         v = np.array(out[:], dtype=np.int64)
         return dict(par_scan=v[:64], gram_mfma_launches=int(v[64]), gram_valu_launches=int(v[65]),
                     retract_kernel_launches=int(v[66]), traj_kernel_launches=int(v[67]),
-                    newton_fsm_launches=int(v[68]), newton_factor8_launches=int(v[69]), extra=v[68:80])
+                    newton_fsm_launches=int(v[68]), newton_factor8_launches=int(v[69]), pair_scan_rounds=int(v[70]),
+                    newton_scan_launches=int(v[71]), newton_rounds=int(v[72]), extra=v[68:80])
 
     def counters(self):
         out = (C.c_longlong * 8)()

@@ -56,7 +56,16 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   PlanInput plan_in{};  // layout and switches the kernel plan is decided from (chmc_plan.h)
   KernelPlan plan{};    // which kernel runs for which pass; the per-partition part is plan.part[part]
   long long diag[16] = {0};  // launches by kernel family: [0] k_gram_rows_mfma, [1] k_gram_rows, [2] k_retract_chain, [3] k_traj_chain,
-                              // [4] k_newton_fsm_wave, [5] KNewtonFactor (blocks of at most 8 rows)
+                              // [4] k_newton_fsm_wave, [5] KNewtonFactor (blocks of at most 8 rows), [6] rounds whose forward scan
+                              // served two problems (one k_fwd_scan<.., PAIR> launch), [7] forward-scan launches of the
+                              // lock-step Newton loops, [8] rounds enqueued by them, per problem
+  // Paired retractions (KernelPlan::pair_retractions): the second problem of run_projection_pair -- the forward retraction of
+  // the NEXT step -- works in a Work of its own: every array a round's kernels, KNewtonBegin, KCheck or KNewtonEnd write
+  // (pair_alloc), everything they only read shared with `w`.  Whole batch only, allocated on first use.
+  Work pw{};
+  int* d_itf_next = nullptr;  // [B] its iteration counts: the next step's iters_fwd
+  bool have_pair = false;
+  bool pair_ready = false;    // the last step ran that loop: the next step of the trajectory adopts its result
   // two half-batches on two streams (chmc_leapfrog_step): chain ranges [hc0[h], hc0[h] + hB[h]) and their work orders
   int round = 0;                   // round of the current Newton loop
   int halves = 1;                  // 1: the step runs as one batch; 2: as two overlapped half-batches
@@ -66,6 +75,7 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   int comm_rank = 0, comm_world = 1;
   int last_n_inner = 1;
   int proj_rounds[2] = {0, 0}, proj_stable[2] = {0, 0};  // rounds the last forward / reverse retraction needed; how often in a row
+                                                          // (by problem, whichever loop it ran in)
   int num_cus = 256;                            // compute units of the device (per-chain kernels: up to 2 chains per CU)
   std::vector<double> last_dt;     // last uploaded step sizes
   std::vector<int> last_active;
@@ -271,18 +281,40 @@ static void refresh_plan(chmc_ctx* c) {
     } else if (fwd_ == FwdWave) {                                                                                \
       if (STORE_)                                                                                                \
         launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B * sy.K + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sy, c->sl, c->w, WHICH_,   \
-                      QSEL_, USENW_, STORE_);                                                                    \
+                      QSEL_, USENW_, STORE_, c->w, 0, 0);                                                        \
       else                                                                                                       \
         launch_blocks(k_fwd_scan<M, RM, false>, ((long)sy.B * sy.K + 63) / 64, 64, 7, sy, c->sl, c->w, WHICH_,   \
-                      QSEL_, USENW_, STORE_);                                                                    \
+                      QSEL_, USENW_, STORE_, c->w, 0, 0);                                                        \
     } else {                                                                                                     \
       launch(KFwd<M, RM>{sy, c->sl, c->w, WHICH_, QSEL_, USENW_, STORE_}, (long)sy.B * sy.K, 7);                 \
     }                                                                                                            \
     stagger_record();                                                                                            \
   } while (0)
+// ... of the chains in the Newton loops of two problems, c->w and W1_, with the same (WHICH_, QSEL_): ONE launch of twice the
+// workgroups (the lock-step round path never scans in parallel in time: KernelPlan::pair_retractions)
+#define CHMC_FWD_PAIR(W1_, WHICH_, QSEL_, STORE_)                                                                \
+  do {                                                                                                           \
+    const long wg_ = ((long)sy.B * sy.K + 63) / 64;                                                              \
+    if (c->plan.fwd_cold == FwdWave) {                                                                           \
+      if (STORE_)                                                                                                \
+        launch_blocks(k_fwd_scan<M, RM, true, true>, 2 * wg_, 64 * (1 + CHMC_SCAN_HELPERS), 7, sy, c->sl, c->w, WHICH_, QSEL_, 1, \
+                      STORE_, W1_, WHICH_, QSEL_);                                                               \
+      else                                                                                                       \
+        launch_blocks(k_fwd_scan<M, RM, false, true>, 2 * wg_, 64, 7, sy, c->sl, c->w, WHICH_, QSEL_, 1, STORE_, W1_, WHICH_,     \
+                      QSEL_);                                                                                    \
+    } else {                                                                                                     \
+      launch(KFwd<M, RM>{sy, c->sl, c->w, WHICH_, QSEL_, 1, STORE_}, (long)sy.B * sy.K, 7);                      \
+      launch(KFwd<M, RM>{sy, c->sl, W1_, WHICH_, QSEL_, 1, STORE_}, (long)sy.B * sy.K, 7);                       \
+    }                                                                                                            \
+  } while (0)
 #else
 #define CHMC_FWD(WHICH_, QSEL_, USENW_, STORE_, GSEL_) \
   launch(KFwd<M, RM>{sy, c->sl, c->w, WHICH_, QSEL_, USENW_, STORE_}, (long)sy.B * sy.K, 7)
+#define CHMC_FWD_PAIR(W1_, WHICH_, QSEL_, STORE_)                                             \
+  do { /* (the host emulation: two functor launches in place of the merged one) */           \
+    launch(KFwd<M, RM>{sy, c->sl, c->w, WHICH_, QSEL_, 1, STORE_}, (long)sy.B * sy.K, 7);     \
+    launch(KFwd<M, RM>{sy, c->sl, W1_, WHICH_, QSEL_, 1, STORE_}, (long)sy.B * sy.K, 7);      \
+  } while (0)
 #endif
 
 // J^T lambda from the compact rows (KMuF + KUpdatePB).  One step per work item: two (KUpdatePB<..., NS = 2>) measured
@@ -595,8 +627,9 @@ static void state_eval(chmc_ctx* c, int which) {
 // P(q) applied in place to the slot's momentum and to pg (initialised to dh1_dpos) in one pass over the Jacobian rows
 // fix_in_jw / flow_rev: the step's momentum correction / reverse flow ride in this pass (KernelPlan::mom_fix_in_jp,
 // rev_flow_in_update)
+// fwd_qb: with flow_rev, the forward-flowed point of the next step as well (KUpdatePB::fwd_qb, paired retractions)
 static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool init_pg, bool fix_in_jw = false,
-                                                bool flow_rev = false) {
+                                                bool flow_rev = false, double* fwd_qb = nullptr, double fwd_hfrac = 0.0) {
   const Sys& sy = c->sy;
   if (init_pg) launch(KInitPg{sy, c->sl, c->w, which}, (long)sy.B * sy.Q, 8);
 #ifdef CHMC_WAVE_KERNELS
@@ -634,7 +667,7 @@ static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool ini
     CHMC_SOLVE_CHAIN(M, RM, 1, 1, sy, c->sl, w2, which, 0, 3);  // multipliers of pg (and its u columns) -> lampad
     if (compact && flow_rev) {
       launch(KMuF<RM, M::X, 3>{sy, c->sl, c->w, which}, (long)sy.B * sy.K * sy.NOBS * M::X, 5);
-      launch_colmax(KUpdatePB<RM, M::X, M::V, 3, 1>{sy, c->sl, c->w, which, 0, 0, 1},
+      launch_colmax(KUpdatePB<RM, M::X, M::V, 3, 1>{sy, c->sl, c->w, which, 0, 0, 1, fwd_qb, fwd_hfrac},
                     sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0), sy.B, 4);
     } else if (compact) {
       CHMC_UPDATE_PB(3, which, 0, 0);
@@ -643,7 +676,7 @@ static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool ini
     }
   });
 #else
-  (void)fix_in_jw, (void)flow_rev;
+  (void)fix_in_jw, (void)flow_rev, (void)fwd_qb, (void)fwd_hfrac;
   project_momentum(c, which, 0, 0);
   project_momentum(c, which, 4, 3);
 #endif
@@ -682,13 +715,37 @@ static void iteration_scan(chmc_ctx* c, int newton, int prev, int qsel, int fwd_
     if (newton) {
 #ifdef CHMC_WAVE_KERNELS
       CHMC_FWD(prev ^ 1, qsel, use_nw, 2, fwd_guess);
+      c->diag[7]++;
 #else
       (void)fwd_guess, (void)use_nw;  // (host emulation: KNewtonBlk integrates the iterate itself)
 #endif
     } else {
       CHMC_FWD(prev ^ 1, qsel, use_nw, 0, fwd_guess);
+      c->diag[7]++;
     }
   });
+}
+// ... of the iterates of two problems with the same (prev, qsel), c->w and w1, in one launch
+static void iteration_scan_pair(chmc_ctx* c, int newton, int prev, int qsel, const Work& w1) {
+  const Sys& sy = c->sy;
+  CHMC_DISPATCH(c, {
+    if (newton) {
+#ifdef CHMC_WAVE_KERNELS
+      CHMC_FWD_PAIR(w1, prev ^ 1, qsel, 2);
+      c->diag[7] += c->plan.fwd_cold == FwdWave ? 1 : 2;
+#else
+      (void)w1;
+#endif
+    } else {
+      CHMC_FWD_PAIR(w1, prev ^ 1, qsel, 0);
+#ifdef CHMC_WAVE_KERNELS
+      c->diag[7] += c->plan.fwd_cold == FwdWave ? 1 : 2;
+#else
+      c->diag[7] += 2;
+#endif
+    }
+  });
+  c->diag[6]++;
 }
 // iteration_after_scan: Jacobian sweep of the iterate against the previous point's rows, block factorisations, Woodbury
 // solve, J^T lambda update of the iterate (masked by work.nw == 1)
@@ -873,6 +930,7 @@ static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ct
       fwd_guess = it == 0 ? 2 : 1;
       c->round = it;
       iteration(it >= 1 ? 2 * h + (it & 1) : -1);
+      c->diag[8]++;
     }
     c->counters[6]++;
     if (it == 0) continue;
@@ -898,6 +956,106 @@ static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ct
     enter(h);
     if (sy.B > 0) launch(KNewtonEnd{c->w, count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf)}, sy.B);
   }
+  c->round = 0;
+  return 0;
+}
+
+// The arrays of the second problem's Work (chmc_ctx::pw), sized as chmc_layout.h sizes their counterparts.  Not in that list:
+// only the whole-batch view has them, as with the arrays of the trajectory trees.
+static void pair_alloc(chmc_ctx* c) {
+  if (c->have_pair) return;
+  const Sys& sy = c->sy;
+  const size_t B = sy.B, KM = sy.Kmax, RM = sy.RM, U = sy.U, X = sy.X, Z = sy.Z, ivls = KM * sy.NOBS;
+  Work& w = c->pw;
+  w = c->w;
+  auto zeroed = [&](size_t n) {
+    double* p = alloc<double>(c, n);
+    dev_zero(p, sizeof(double) * n);
+    return p;
+  };
+  w.qb = zeroed(B * sy.Q + CHMC_Q_PAD);
+  w.trajw = alloc<double>(c, B * sy.TRJ);
+  w.cpad = zeroed(B * KM * RM), w.tpad = alloc<double>(c, B * KM * RM), w.lampad = zeroed(B * KM * RM);
+  w.Ew = alloc<double>(c, B * KM * RM * U), w.Cb = alloc<double>(c, B * KM * U * U), w.sb = alloc<double>(c, B * KM * U);
+  w.Dw = alloc<double>(c, B * KM * RM * RM), w.JuL = alloc<double>(c, B * KM * RM * U), w.zbP = alloc<double>(c, B * KM * RM * Z);
+  if (c->plan.pb_allocated) {
+    w.muF = alloc<double>(c, B * ivls * X);
+    w.ivl = alloc<double>(c, B * ivls * (2 * X * X + X * Z));
+  }
+  w.err = alloc<double>(c, B), w.ndq = alloc<unsigned long long>(c, B);
+  w.iters = alloc<int>(c, B), w.nw = alloc<int>(c, B), w.nstat = alloc<int>(c, B), w.ok = alloc<int>(c, B), w.status = alloc<int>(c, B);
+  w.n_active = alloc<int>(c, 4);  // its own round slots
+  c->d_itf_next = alloc<int>(c, B);
+  c->have_pair = true;
+}
+
+// The reverse retraction of step i (problem 0: run_projection(.., 1, 1, .., 1) exactly, on c->w) and the forward retraction of
+// step i + 1 (problem 1, on c->pw: its iterate pw.qb holds the forward-flowed point, KPairFlow) in ONE lock-step loop.  Both are
+// Newton loops against the proposal slot's point (prev = 1) on an iterate in a work array (qsel = 1).  A round is one forward
+// scan for both problems (iteration_scan_pair; the single form once one of them has finished), then each problem's own
+// sweep, solve, update and check, on the one stream.  Each problem keeps the read-backs, the speculation and the predicted stop
+// of a loop of its own (run_projection), counted per problem: poll slots 2 p + parity, proj_rounds / proj_stable of its
+// direction -- so a problem is enqueued for exactly the rounds its own loop would have been, and counters[6] counts a round
+// once per problem that had work.
+static int run_projection_pair(chmc_ctx* c, int newton, double ctol, double ptol, double dtol, int max_iters) {
+  const Sys& sy = c->sy;
+  const int prev = 1, qsel = 1;
+  const Work wk[2] = {c->w, c->pw};
+  int* const iters_dst[2] = {c->d_itb, c->d_itf_next};
+  const int dir[2] = {1, 0};  // problem 0 is a reverse retraction, problem 1 a forward one
+  auto enter = [&](int p) { c->w = wk[p]; };
+  bool done[2], predict[2], stopped[2] = {false, false};
+  int rounds_done[2] = {0, 0};
+  for (int p = 0; p < 2; ++p) {
+    enter(p);
+    launch(KNewtonBegin{c->w}, sy.B);
+    done[p] = sy.B <= 0;
+    predict[p] = c->proj_stable[dir[p]] >= 3 && c->proj_rounds[dir[p]] >= 2;
+  }
+  for (int it = 0; it < max_iters && !(done[0] && done[1]); ++it) {
+    for (int p = 0; p < 2; ++p)  // (the count of round it - 1 was requested in that round)
+      if (!done[p] && predict[p] && it >= c->proj_rounds[dir[p]] && poll_end(2 * p + ((it - 1) & 1)) == 0)
+        done[p] = stopped[p] = true;
+    if (done[0] && done[1]) break;
+    c->round = it;
+    if (!done[0] && !done[1]) {
+      enter(0);
+      iteration_scan_pair(c, newton, prev, qsel, wk[1]);
+    } else {
+      enter(done[0] ? 1 : 0);
+      iteration_scan(c, newton, prev, qsel, it == 0 ? 2 : 1, 1);
+    }
+    for (int p = 0; p < 2; ++p) {
+      if (done[p]) continue;
+      enter(p);
+      iteration_after_scan(c, newton, prev, qsel);
+      const KCheck chk{c->w, ctol, ptol, dtol, max_iters, sy.B, iters_dst[p], it & 3};
+      if (it >= 1) launch_publish(chk, sy.B, c->w.n_active + (it & 3), 2 * p + (it & 1));
+      else launch(chk, sy.B);
+      c->counters[6]++, c->diag[8]++;
+    }
+    if (it == 0) continue;
+    for (int p = 0; p < 2; ++p) {
+      if (done[p]) continue;
+      if (it >= 2 && poll_end(2 * p + ((it - 1) & 1)) == 0) {  // round it - 1 left no chain active: round it was empty
+        done[p] = true;
+        c->counters[6]--;
+        continue;
+      }
+      rounds_done[p] = it + 1;
+      if (it + 1 >= max_iters) poll_end(2 * p + (it & 1));  // drain the last read-back before the slots are reused
+    }
+  }
+  for (int p = 0; p < 2; ++p) {
+    int& expect = c->proj_rounds[dir[p]];
+    int& stable = c->proj_stable[dir[p]];
+    if (stopped[p] && rounds_done[p] < expect) rounds_done[p] = expect;  // (stopped by the prediction: `expect` rounds had work)
+    stable = rounds_done[p] == expect ? stable + 1 : 0;
+    expect = rounds_done[p];
+    enter(p);  // a chain the host left in the loop is a failure, never a silent success
+    if (sy.B > 0) launch(KNewtonEnd{c->w, iters_dst[p]}, sy.B);
+  }
+  enter(0);
   c->round = 0;
   return 0;
 }
@@ -1458,7 +1616,7 @@ static int nld_core(chmc_ctx* ctx, int use_gaussian_splitting, double* grad_dev)
       sp.order = ctx->d_order_ident;
       CHMC_FWD_PAR(ctx->plan.nld_waves, (long)sy.B, sp, ctx->sl, ctx->w, 0, 1, 0, 2, 1, 0);
     } else if (ctx->plan.nld == FwdWave)
-      launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sf, ctx->sl, ctx->w, 0, 1, 0, 2);
+      launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sf, ctx->sl, ctx->w, 0, 1, 0, 2, ctx->w, 0, 0);
     else
       launch(KFullScan<M>{sy, ctx->w.qb, ctx->w.trajw, QH}, sy.B, 7);
     launch_wave(k_nld_grad_wave<M>, (long)sy.B, 0, sy, ctx->w.qb, ctx->w.trajw, QH, use_gaussian_splitting, ctx->d_ham,
@@ -1620,8 +1778,13 @@ struct KInnerRestore {  // failed chains that had completed inner steps: back to
 static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, const int* active_dev, int n_inner, int newton,
                         double ctol, double ptol, double dtol, int max_iters, double rev_tol,
                         const int* n_steps_host = nullptr, int n_steps_all = 1, bool want_n_done = false,
-                        bool skip_end_kick = false, bool pending_kick = false) {
+                        bool skip_end_kick = false, bool pending_kick = false, bool pair_next = false) {
   const Sys& sy = ctx->sy;
+  // pair_next: the forward retraction of the NEXT step of the trajectory runs beside this step's reverse one
+  // (run_projection_pair); that step then opens by adopting the result instead of flowing and retracting
+  const bool adopt = pending_kick && ctx->pair_ready;
+  ctx->pair_ready = false;
+  if (pair_next) pair_alloc(ctx);
   // dt / active change rarely between consecutive steps of a trajectory: upload only when they do
   const double* d_dt = nullptr;
   if (ctx->last_dt.size() != (size_t)sy.B || ctx->last_n_inner != n_inner ||
@@ -1710,15 +1873,22 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
         // A(dt/2): proposal.p = P(q)[ state.p - dt/2 dh1_dpos(state) ] = state.p - dt/2 pg for a tangent momentum;
         // B: h2 flow from the state with the kicked momentum
         // (pending_kick: the step before, of the same trajectory, left its closing A(dt/2) to this pass)
-        if (pending_kick) launch_rows(KKick2FlowPg{sy, ctx->sl, ctx->w, kick}, sy.Q, sy.B, 8);
-        else launch_rows(KKickFlowPg{sy, ctx->sl, ctx->w, kick}, sy.Q, sy.B, 8);
+        if (adopt) {
+          launch_rows(KPairAdopt{sy, ctx->sl, ctx->w, kick, ctx->pw.qb}, sy.Q, sy.B, 8);
+          launch(KPairAdoptStatus{ctx->w, ctx->pw, ctx->d_itf, ctx->d_itf_next}, sy.B);
+        } else if (pending_kick) {
+          launch_rows(KKick2FlowPg{sy, ctx->sl, ctx->w, kick}, sy.Q, sy.B, 8);
+        } else {
+          launch_rows(KKickFlowPg{sy, ctx->sl, ctx->w, kick}, sy.Q, sy.B, 8);
+        }
       } else {
         launch(KKick{sy, ctx->sl, ctx->w, 0, 1, kick}, (long)sy.B * sy.Q, 8);
         project_momentum(ctx, 0, 3, 2);
         launch_rows(KFlow{sy, ctx->sl, ctx->w, 0, 0, 1, 1.0}, sy.Q, sy.B, 8);
       }
     }
-    run_projection(ctx, newton, 0, 0, ctol, ptol, dtol, max_iters, two ? &full : nullptr, 0);  // retraction onto the manifold
+    if (!adopt)
+      run_projection(ctx, newton, 0, 0, ctol, ptol, dtol, max_iters, two ? &full : nullptr, 0);  // retraction onto the manifold
     for (int h = 0; h < nh; ++h) {
       enter(h);
       state_eval_core(ctx, 1, last, 3);  // J, factors, log det at the new point; on the last inner step dh1_dpos as well
@@ -1730,13 +1900,21 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
         launch_rows(KMomFixInitPg{sy, ctx->sl, ctx->w, 1}, sy.Q, sy.B, 8);
       const bool flow_in_update = last && ctx->plan.rev_flow_in_update;
       if (last)  // P p and pg = P dh1_dpos, one pass over the new Jacobian rows
-        project_momentum_and_kick_direction(ctx, 1, false, fix_in_jw, flow_in_update);
+        project_momentum_and_kick_direction(ctx, 1, false, fix_in_jw, flow_in_update, pair_next ? ctx->pw.qb : nullptr, kick);
       else
         project_momentum(ctx, 1, 0, 0);  // (pg of an intermediate point is never used)
       // reverse retraction from the new point and reversibility check (the reverse flow: in the J^T lambda pass where that is
       // possible, the u-part here)
       launch_rows(KFlow{sy, ctx->sl, ctx->w, 1, 1, 0, -1.0}, flow_in_update ? sy.U : sy.Q, sy.B, 8);
+      if (pair_next) {  // ... and the forward flow of the next step into the second problem's iterate, likewise
+        launch(KPairBegin{ctx->w, ctx->pw, ctx->d_itf_next}, sy.B);
+        launch_rows(KPairFlow{sy, ctx->sl, ctx->w, kick, ctx->pw.qb}, flow_in_update ? sy.U : sy.Q, sy.B, 8);
+      }
     }
+    if (pair_next) {
+      run_projection_pair(ctx, newton, ctol, ptol, dtol, max_iters);
+      ctx->pair_ready = true;
+    } else
     run_projection(ctx, newton, 1, 1, ctol, ptol, dtol, max_iters, two ? &full : nullptr, 1);
     for (int h = 0; h < nh; ++h) {
       enter(h);
@@ -1877,8 +2055,11 @@ extern "C" int chmc_leapfrog_steps(chmc_ctx* ctx, const double* dt, const int* a
     for (int c = 0; c < B; ++c) any = (run[c] = act[c] && left[c] > 0) || any;
     if (!any) break;
     const bool skip = fuse_kicks && ctx->mom_tangent && k + 1 < longest;
+    // ... and the forward retraction of step k + 1 runs beside the reverse retraction of step k (KernelPlan::pair_retractions):
+    // under the same conditions, where the merged scan launch fits the chip (pair_this_call, chmc_plan.h; the same bits)
+    const bool pair = skip && ctx->halves == 1 && pair_this_call(ctx->plan, ctx->plan_in.wave_kernels, B, sy.K, ctx->num_cus);
     if (step_enqueue(ctx, dt, run.data(), nullptr, n_inner, newton, ctol, ptol, dtol, max_iters, rev_tol, nullptr, 1, false, skip,
-                     pending))
+                     pending, pair))
       return -1;
     pending = skip;
     step_finish(ctx, true, n_inner, st.data(), f.data(), b.data(), r1.data());

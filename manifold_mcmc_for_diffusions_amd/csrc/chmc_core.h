@@ -1646,16 +1646,36 @@ struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: bo
   // for the columns of this pass, from the momentum it has just projected (the u-part: a KFlow launch over U columns;
   // standard splitting only)
   int flow_rev = 0;
-  CHMC_HD void rev_flow2(int c, int s, size_t i, double px, double py) const {  // KFlow's expressions, a 16-byte pair
+  // ... and, inside a trajectory whose next step's forward retraction runs beside this step's reverse one (KernelPlan::
+  // pair_retractions), that step's forward-flowed point as well, into the second problem's iterate fwd_qb: KKick2FlowPg's
+  // expressions on the p and pg this pass has just formed (fwd_hfrac: its hfrac)
+  double* fwd_qb = nullptr;
+  double fwd_hfrac = 0.0;
+  CHMC_HD void rev_flow2(int c, int s, size_t i, double px, double py, double gx, double gy) const {  // KFlow's expressions, a 16-byte pair
     const double2_ q0 = ld2_stream(pick(sl.q, s) + i);
     const double dt = -1.0 * w.dt[c];
     double2_ qn;
     qn.x = q0.x + dt * px, qn.y = q0.y + dt * py;
     stv2(w.qb + i, qn, true, true);
+    if (fwd_qb) {
+      const double h = fwd_hfrac * w.dt[c];
+      double2_ p1, p0, qf;
+      p1.x = px - h * gx, p1.y = py - h * gy;
+      p0.x = p1.x - h * gx, p0.y = p1.y - h * gy;
+      qf.x = q0.x + w.dt[c] * p0.x, qf.y = q0.y + w.dt[c] * p0.y;
+      stv2(fwd_qb + i, qf, true, true);
+    }
   }
-  CHMC_HD void rev_flow1(int c, int s, size_t i, double px) const {  // ... one component
+  CHMC_HD void rev_flow1(int c, int s, size_t i, double px, double gx) const {  // ... one component
     const double dt = -1.0 * w.dt[c];
-    w.qb[i] = pick(sl.q, s)[i] + dt * px;
+    const double q0 = pick(sl.q, s)[i];
+    w.qb[i] = q0 + dt * px;
+    if (fwd_qb) {
+      const double h = fwd_hfrac * w.dt[c];
+      const double p1 = px - h * gx;
+      const double p0 = p1 - h * gx;
+      fwd_qb[i] = q0 + w.dt[c] * p0;
+    }
   }
   CHMC_HD bool active(int c) const {
     int p_ = 0, q_ = 0;
@@ -1742,7 +1762,7 @@ struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: bo
           if (TGT == 3) {
             o.x = old2[e * V], o.y = old2[e * V + V - 1];
             *reinterpret_cast<double2_*>(tgt2 + to + e * V) = o;
-            if (flow_rev) rev_flow2(c, s, off + to + e * V, o.x, o.y);
+            if (flow_rev) rev_flow2(c, s, off + to + e * V, o.x, o.y, old[e * V], old[e * V + V - 1]);
           }
         } else {
           CHMC_UNROLL
@@ -1750,7 +1770,7 @@ struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: bo
             tgt[to + e * V + k] = old[e * V + k];
             if (TGT == 3) {
               tgt2[to + e * V + k] = old2[e * V + k];
-              if (flow_rev) rev_flow1(c, s, off + to + e * V + k, old2[e * V + k]);
+              if (flow_rev) rev_flow1(c, s, off + to + e * V + k, old2[e * V + k], old[e * V + k]);
             }
           }
         }
@@ -1784,11 +1804,12 @@ struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: bo
         }
       }
       if (TGT == 0) r = absbits(d);
-      tgt[col] -= d;
+      const double gn = tgt[col] - d;
+      tgt[col] = gn;
       if (TGT == 3) {
         const double pn = tgt2[col] - d2;
         tgt2[col] = pn;
-        if (flow_rev) rev_flow1(c, s, off + col, pn);
+        if (flow_rev) rev_flow1(c, s, off + col, pn, gn);
       }
     }
     return r;
@@ -2177,6 +2198,22 @@ struct KKickFlowPg {
 // lock-step path): p1 = p - h pg goes back to the state slot (the state a failing step leaves behind), the flow starts from
 // p1 - h pg.  Same operations in the same order as KKickPg followed by KKickFlowPg; two vector passes less per step.
 // (Not used with a block metric: its u-part reads all of p_u while other work items would be rewriting it.)
+// (the arithmetic, shared with the passes that do the same work in two parts when the retractions of a trajectory are
+// paired: KPairFlow forms qn before the step, KPairAdopt p1 and pn at its start)
+CHMC_FI CHMC_HD inline void kick2_flow(const Sys& sy, const Work& w, int c, double h, const double2_& q0, const double2_& pp,
+                                const double2_& g, double2_& p1, double2_& qn, double2_& pn) {
+  double2_ p0;
+  p1.x = pp.x - h * g.x, p1.y = pp.y - h * g.y;  // KKickPg of the step before
+  p0.x = p1.x - h * g.x, p0.y = p1.y - h * g.y;
+  if (sy.gaussian) {
+    const double sn = w.sdt[c], cs = w.cdt[c];
+    qn.x = q0.x * cs + sn * p0.x, qn.y = q0.y * cs + sn * p0.y;
+    pn.x = p0.x * cs - sn * q0.x, pn.y = p0.y * cs - sn * q0.y;
+  } else {
+    qn.x = q0.x + w.dt[c] * p0.x, qn.y = q0.y + w.dt[c] * p0.y;
+    pn = p0;
+  }
+}
 struct KKick2FlowPg {
   Sys sy;
   Slots sl;
@@ -2190,20 +2227,84 @@ struct KKick2FlowPg {
     const bool two = col + 1 < sy.Q, wide = two && !(sy.Q & 1);
     const double2_ q0 = ldv2(pick(sl.q, s) + i, wide, two), pp = ldv2(pick(sl.p, s) + i, wide, two);
     const double2_ g = ldv2(pick(sl.pg, s) + i, wide, two);
-    double2_ p1, p0, qn, pn;
-    p1.x = pp.x - h * g.x, p1.y = pp.y - h * g.y;  // KKickPg of the step before
-    p0.x = p1.x - h * g.x, p0.y = p1.y - h * g.y;
-    if (sy.gaussian) {
-      const double sn = w.sdt[c], cs = w.cdt[c];
-      qn.x = q0.x * cs + sn * p0.x, qn.y = q0.y * cs + sn * p0.y;
-      pn.x = p0.x * cs - sn * q0.x, pn.y = p0.y * cs - sn * q0.y;
-    } else {
-      qn.x = q0.x + w.dt[c] * p0.x, qn.y = q0.y + w.dt[c] * p0.y;
-      pn = p0;
-    }
+    double2_ p1, qn, pn;
+    kick2_flow(sy, w, c, h, q0, pp, g, p1, qn, pn);
     stv2(pick(sl.p, s) + i, p1, wide, two);
     stv2(pick(sl.q, s ^ 1) + i, qn, wide, two);
     stv2(pick(sl.p, s ^ 1) + i, pn, wide, two);
+  }
+};
+// Paired retractions (KernelPlan::pair_retractions): KKick2FlowPg of step i + 1 in two parts around the loop that runs its
+// forward retraction beside the reverse retraction of step i.
+//   KPairBegin  the second problem's chain flags: the chains that are good at this point of step i; its own status and
+//               forward iteration counts
+//   KPairFlow   before the loop: the forward-flowed point of step i + 1 from q', p', pg' of the PROPOSAL slot into the second
+//               problem's iterate; writes nothing into the slots
+//   KPairAdopt  the opening pass of step i + 1 (after KCommit of step i: q' is the state slot): p1 to the state slot, the
+//               flowed momentum and the CONVERGED iterate to the proposal slot
+//   KPairAdoptStatus  ... and the forward loop's verdict and iteration count become those of step i + 1: a chain whose
+//               forward retraction failed fails step i + 1 with that status, its state slot holding p1 as after KKick2FlowPg
+struct KPairBegin {
+  Work w, w2;
+  int* itf_next;
+  CHMC_HD void operator()(int c) const {
+    w2.ok[c] = w.ok[c];
+    w2.status[c] = w.ok[c] ? 0 : -1;
+    itf_next[c] = 0;
+  }
+};
+struct KPairFlow {
+  Sys sy;
+  Slots sl;
+  Work w;
+  double hfrac;
+  double* qf;  // [B][Q] the second problem's iterate
+  CHMC_HD bool active(int c) const { return w.ok[c] != 0; }
+  CHMC_FI CHMC_HD void operator()(int c, int col) const {  // row launch: components col, col + 1 of chain c
+    const int s = sl.cur[c] ^ 1;
+    const double h = hfrac * w.dt[c];
+    const size_t i = (size_t)c * sy.Q + col;
+    const bool two = col + 1 < sy.Q, wide = two && !(sy.Q & 1);
+    const double2_ q0 = ldv2(pick(sl.q, s) + i, wide, two), pp = ldv2(pick(sl.p, s) + i, wide, two);
+    const double2_ g = ldv2(pick(sl.pg, s) + i, wide, two);
+    double2_ p1, qn, pn;
+    kick2_flow(sy, w, c, h, q0, pp, g, p1, qn, pn);
+    stv2(qf + i, qn, wide, two);
+  }
+};
+struct KPairAdopt {
+  Sys sy;
+  Slots sl;
+  Work w;
+  double hfrac;
+  const double* qf;
+  CHMC_HD bool active(int c) const { return w.ok[c] != 0; }
+  CHMC_FI CHMC_HD void operator()(int c, int col) const {  // row launch: components col, col + 1 of chain c
+    const int s = sl.cur[c];
+    const double h = hfrac * w.dt[c];
+    const size_t i = (size_t)c * sy.Q + col;
+    const bool two = col + 1 < sy.Q, wide = two && !(sy.Q & 1);
+    double2_ q0;
+    q0.x = q0.y = 0.0;
+    if (sy.gaussian) q0 = ldv2(pick(sl.q, s) + i, wide, two);  // (the standard flow leaves the momentum as it is)
+    const double2_ pp = ldv2(pick(sl.p, s) + i, wide, two), g = ldv2(pick(sl.pg, s) + i, wide, two);
+    const double2_ qc = ldv2(qf + i, wide, two);
+    double2_ p1, qn, pn;
+    kick2_flow(sy, w, c, h, q0, pp, g, p1, qn, pn);
+    stv2(pick(sl.p, s) + i, p1, wide, two);
+    stv2(pick(sl.q, s ^ 1) + i, qc, wide, two);
+    stv2(pick(sl.p, s ^ 1) + i, pn, wide, two);
+  }
+};
+struct KPairAdoptStatus {
+  Work w, w2;
+  int* itf;
+  const int* itf_next;
+  CHMC_HD void operator()(int c) const {
+    itf[c] = w.ok[c] ? itf_next[c] : 0;
+    if (!w.ok[c]) return;
+    w.iters[c] = w2.iters[c], w.nstat[c] = w2.nstat[c];
+    if (!w2.ok[c]) w.ok[c] = 0, w.status[c] = w2.status[c];
   }
 };
 // reverse check distance max |q_back - q_start| (mici maximum_norm); column-max kernel, two components per work item

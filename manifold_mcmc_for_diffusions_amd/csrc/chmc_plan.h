@@ -35,6 +35,10 @@
 //   CHMC_RETRACT_KERNEL=0/1/2  one 16-row block per chain: batched launches / one workgroup of 8 wavefronts per chain / of 4
 //                           wavefronts (two chains per compute unit).  Default: 8 up to one chain per compute unit, 4 up to
 //                           four, batched beyond; all three give the same bits
+//   CHMC_PAIR_RETRACT=0/1   chmc_leapfrog_steps: 0 = every retraction in a Newton loop of its own; 1 = the reverse retraction of
+//                           step i and the forward retraction of step i + 1 advance round for round in one loop with one
+//                           forward-scan launch per round for both (KernelPlan::pair_retractions).  Default: paired while the
+//                           merged launch still has a compute unit per workgroup (pair_this_call); both give the same bits
 #pragma once
 #include <climits>
 #include <cstdlib>
@@ -56,7 +60,7 @@ struct Switches {
   bool compact_rows = true, gram_mfma = false;
   int par_scan = kSwitchUnset, par_waves = kSwitchUnset, row_split = 0, halves = 1;
   bool no_fwd_scan = false, step_fusions = true;
-  int retract_kernel = kSwitchUnset;
+  int retract_kernel = kSwitchUnset, pair_retract = kSwitchUnset;
 };
 inline Switches read_switches() {
   auto env = [](const char* name, int unset) {
@@ -70,6 +74,7 @@ inline Switches read_switches() {
   s.row_split = env("CHMC_ROW_SPLIT", 0), s.halves = env("CHMC_HALVES", 1);
   s.no_fwd_scan = getenv("CHMC_NO_FWD_SCAN") != nullptr, s.step_fusions = env("CHMC_STEP_FUSIONS", 1) != 0;
   s.retract_kernel = env("CHMC_RETRACT_KERNEL", kSwitchUnset);
+  s.pair_retract = env("CHMC_PAIR_RETRACT", kSwitchUnset);
   return s;
 }
 
@@ -88,7 +93,8 @@ struct PlanInput {
   bool gaussian;         // Gaussian splitting
   bool wave_kernels;     // CHMC_WAVE_KERNELS: without them every pass is a generic functor over the stored rows
   Switches sw;           // as read by chmc_create
-  Switches call;         // as read on entry to the current call: no_fwd_scan, step_fusions, retract_kernel; the comparator's scan
+  Switches call;         // as read on entry to the current call: no_fwd_scan, step_fusions, retract_kernel, pair_retract; the
+                         // comparator's scan
 };
 
 enum RowFamily { RowsCompact, RowsStored, RowsStoredMfma };
@@ -143,6 +149,17 @@ struct KernelPlan {
   bool mom_fix_in_jp;       // a step's momentum correction (KMomFixInitPg) rides in the J p pass (k_jw_pb<.., FIX>)
   bool rev_flow_in_update;  // the reverse flow of the reversibility check (KFlow) rides in the J^T lambda pass (KUpdatePB<.., 3>)
   int retract_kernel;       // CHMC_RETRACT_KERNEL of this call
+  // Inside a trajectory (chmc_leapfrog_steps, one n_steps for all chains) the reverse retraction of step i -- the
+  // reversibility check -- and the forward retraction of step i + 1 are independent Newton loops against the same point q':
+  // they advance round for round in ONE lock-step loop, and each round's forward scan is one launch for both (k_fwd_scan<..,
+  // PAIR>: twice the lanes at the latency of one scan).  Lock-step round path only: not the per-chain kernel layouts
+  // (k_retract_chain / k_traj_chain), not two half-batches, and not the time-parallel scan -- its first sweep takes the
+  // state slot's trajectory as its guess, which before the commit of step i is not the one the unpaired step i + 1 starts
+  // from, and a chain's bits must not depend on the pairing.  With the wave kernels only where the scan is k_fwd_scan (the
+  // generic functor has no merged launch: two launches would save nothing), unless CHMC_PAIR_RETRACT=1 asks for it.  Whether a
+  // call pairs is then pair_this_call's choice.
+  bool pair_retractions;
+  int pair_retract;         // CHMC_PAIR_RETRACT of this call
   PartitionPlan part[2];
 };
 
@@ -198,6 +215,9 @@ inline KernelPlan make_plan(const PlanInput& in) {
   pl.mom_fix_in_jp = step_fusions && in.V == 2 && in.even_dims;
   pl.rev_flow_in_update = step_fusions && !in.gaussian;
   pl.retract_kernel = in.call.retract_kernel;
+  pl.pair_retract = in.call.pair_retract;
+  pl.pair_retractions = in.call.pair_retract != 0 && sw.halves != 2 && pl.fwd != FwdPar &&
+                        (!in.wave_kernels || pl.fwd_cold == FwdWave || in.call.pair_retract == 1);
 
   for (int p = 0; p < in.num_partition; ++p) {
     PartitionPlan& pp = pl.part[p];
@@ -228,6 +248,7 @@ inline KernelPlan make_plan(const PlanInput& in) {
     // to require `chain16 && pl.par_scan && pl.fwd_waves == CHMC_CHAIN_SCAN_WAVES` here.
     pp.retract_chain = compact && rows16 && K == 1;
     pp.traj_chain = pp.retract_chain && ivl16;
+    if (pp.retract_chain) pl.pair_retractions = false;
   }
   return pl;
 }
@@ -247,6 +268,20 @@ inline int chain_kernel_waves(const KernelPlan& pl, bool eligible, int B, int nu
   const int want = pl.retract_kernel != kSwitchUnset ? pl.retract_kernel
                    : B <= num_cus ? 1 : B <= CHMC_CHAIN_WG4_MAX_PER_CU * num_cus ? 2 : 0;
   return want == 1 ? CHMC_RETRACT_WAVES : want == 2 ? 4 : 0;
+}
+
+// Paired retractions against a loop per retraction: the other choice made per call -- like the one above a pure scheduling
+// decision, the bits are the same either way (tests/test_pair_retractions.py), so it may look at the batch.  The merged scan
+// launch has 2 ceil(B K / 64) workgroups, and it keeps the latency of a single scan only while each of them has a compute
+// unit to itself: measured on one box (steps/s, paired | unpaired), FitzHugh-Nagumo S = 400, 256 chains
+// (160 workgroups on 256 compute units): 55.4-56.3 k | 53.2-53.7 k; S = 800, 512 chains (320 workgroups): 31.0 k | 32.4 k --
+// the scans of two workgroups that share a compute unit take as long as two scans, and the second problem's passes are no
+// longer free.  Without the wave kernels (the host emulation of the tests) there is no merged launch to fit: always paired.
+// CHMC_PAIR_RETRACT=1 pairs whatever the batch.
+inline bool pair_this_call(const KernelPlan& pl, bool wave_kernels, int B, int K, int num_cus) {
+  if (!pl.pair_retractions) return false;
+  if (pl.pair_retract == 1 || !wave_kernels) return true;
+  return 2 * (((long)B * K + 63) / 64) <= num_cus;
 }
 
 }  // namespace chmc

@@ -4779,9 +4779,17 @@ __device__ inline bool scan_select(const Work& w, int c, int use_nw, int& which,
 #ifndef CHMC_SCAN_HELPERS
 #define CHMC_SCAN_HELPERS 1
 #endif
-template <class M, int RM, bool STORE>
+// PAIR: one launch for two problems on the same batch (the reverse retraction of a step and the forward retraction of the
+// next one, run_projection_pair): the first ceil(B K / 64) workgroups scan the iterate of (w, which, qsel), the others that of
+// (w1, which1, qsel1).  A workgroup picks its argument set once (uniform: scalar selects); the body is the same.
+template <class M, int RM, bool STORE, bool PAIR = false>
 __global__ void __launch_bounds__(STORE ? 64 * (1 + CHMC_SCAN_HELPERS) : 64)
-    k_fwd_scan(Sys sy, Slots sl, Work w, int which, int qsel, int use_nw, int store_traj) {
+    k_fwd_scan(Sys sy, Slots sl, Work w0, int which0, int qsel0, int use_nw, int store_traj, Work w1, int which1, int qsel1) {
+  const int wg0 = (sy.B * sy.K + 63) / 64;  // workgroups per problem
+  const bool second = PAIR && (int)blockIdx.x >= wg0;
+  const Work w = second ? w1 : w0;
+  int which = second ? which1 : which0, qsel = second ? qsel1 : qsel0;
+  const int wg = second ? (int)blockIdx.x - wg0 : (int)blockIdx.x;
   constexpr int X = M::X, V = M::V, PF = 8;
   constexpr int NLD = PF * V / 2;        // 16-byte loads per lane and tile
   constexpr int NST = PF * X / 2;        // 16-byte chunks per trajectory row and tile
@@ -4807,7 +4815,7 @@ __global__ void __launch_bounds__(STORE ? 64 * (1 + CHMC_SCAN_HELPERS) : 64)
   const bool helper = STORE && wave_id != 0;
   const int hid = wave_id - 1;  // which helper
   const int n = sy.B * sy.K, S = sy.S;
-  const int tid0 = blockIdx.x * 64;
+  const int tid0 = wg * 64;
 
   // both waves work out the longest block of the 64 (same loop trip count and barrier count)
   int maxL = 0;
