@@ -165,6 +165,33 @@ def rel(a, b):
     return float(np.max(np.abs(a - b))) / max(1.0, float(np.max(np.abs(b))))
 
 
+UNJUDGED = "unjudged_chains"  # in a `worst` dict: chains whose REFERENCE holds a non-finite entry; a count, not a distance
+
+
+def distance(a, b):
+    """(relative distance of a library value `a` from its reference `b`, whether every entry of `b` is finite).  Entries
+    whose reference is not finite are not compared; a library entry that is not finite where the reference is gives inf
+    (np.max / the builtin max would drop a NaN: max(0.0, nan) is 0.0)."""
+    a, b = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64))
+    fin = np.isfinite(b)
+    if not fin.any():
+        return 0.0, False
+    af, bf = a[fin], b[fin]
+    if not np.isfinite(af).all():
+        return np.inf, bool(fin.all())
+    return float(np.max(np.abs(af - bf))) / max(1.0, float(np.max(np.abs(bf)))), bool(fin.all())
+
+
+def failures(worst, tol):
+    """The operators of `worst` that miss `tol` (the count of unjudged chains is not a distance and not subject to it)."""
+    return {k: v for k, v in worst.items() if k != UNJUDGED and not v < tol}
+
+
+def largest(worst):
+    """The largest operator distance of `worst`."""
+    return max(v for k, v in worst.items() if k != UNJUDGED)
+
+
 def library_ops(ctx, h, part):
     """What the library computes for every chain of the handle's states in one partition."""
     d = h["parts"][part]
@@ -183,7 +210,8 @@ def library_ops(ctx, h, part):
 
 
 def compare_ops(lib, ref, c, nrows, worst, show=False):
-    """One chain's library results against one ops_job result; updates `worst` {operator: largest relative distance}."""
+    """One chain's library results against one ops_job result; updates `worst` {operator: largest relative distance, inf
+    where the library is not finite and the reference is; UNJUDGED: chains whose reference is not finite somewhere}."""
     rm = ref["dc_dv"].shape[0]
     pairs = [(k, lib[k][c], ref[k]) for k in ("c", "dc_du", "chol_C", "Jw", "Ginv_lam", "grad", "JTlam", "nsc") if k in ref]
     pairs.append(("dc_dv", lib["dc_dv"][c][:rm], ref["dc_dv"]))
@@ -196,11 +224,15 @@ def compare_ops(lib, ref, c, nrows, worst, show=False):
     pairs.append(("log_det", np.array([lib["log_det"][c]]), np.array([ref["log_det"]])))
     if "h" in ref:
         pairs.append(("hamiltonian", np.array([lib["h"][c]]), np.array([ref["h"]])))
+    judged = True
     for k, a, b in pairs:
-        e = rel(a, b)
+        assert np.shape(a) == np.shape(b), (k, np.shape(a), np.shape(b))
+        e, fin = distance(a, b)
+        judged &= fin
         worst[k] = max(worst.get(k, 0.0), e)
         if show:
             print(f"    chain {c} {k}: {e:.2e}")
+    worst[UNJUDGED] = worst.get(UNJUDGED, 0) + (not judged)
 
 
 def check_ops(ctx, h, tol=OP_TOL, timeout=600, show=True):
@@ -213,7 +245,7 @@ def check_ops(ctx, h, tol=OP_TOL, timeout=600, show=True):
             compare_ops(lib, fut.result(timeout=timeout), c, nrows, worst)
     if show:
         print("  library vs autodiff, operators (rel):", {k: f"{v:.1e}" for k, v in worst.items()})
-    bad = {k: v for k, v in worst.items() if not v < tol}
+    bad = failures(worst, tol)
     assert not bad, f"library vs autodiff oracle (rel err): {bad}; all: {worst}"
     return worst
 

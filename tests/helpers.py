@@ -3,6 +3,7 @@
 Test infrastructure only (may import oracle/)."""
 import numpy as np
 from oracle import c_oracle
+from autodiff_checks import UNJUDGED, distance, failures
 from manifold_mcmc_for_diffusions_amd import example_models as em
 
 FHN_U = np.array([-1.2, -2.0, 0.4, 0.8])  # log sigma, log eps, log gamma, beta  (sigma 0.3, eps 0.135, gamma 1.5)
@@ -60,16 +61,26 @@ def make_ctx(case, **kw):
 
 
 def _upd(worst, k, a, b):
-    scale = max(1.0, float(np.max(np.abs(b))))
-    worst[k] = max(worst.get(k, 0.0), float(np.max(np.abs(a - b))) / scale)
+    """worst[k] = the larger of itself and the distance of the library's `a` from the reference `b` (inf where `a` is not
+    finite and `b` is); returns whether every entry of the reference was finite, i.e. whether all of `a` was judged."""
+    e, judged = distance(a, b)
+    worst[k] = max(worst.get(k, 0.0), e)
+    return judged
+
+
+def _count_unjudged(worst, judged):
+    """worst[UNJUDGED] += the chains of `judged` (one flag per chain) with a reference value that was not finite."""
+    worst[UNJUDGED] = worst.get(UNJUDGED, 0) + sum(not j for j in judged)
 
 
 def _ops_at_point(ctx, osys, q, xo, part, rng, worst):
     """Every per-op entry point of the C ABI at the context's current state, which the caller says is (q, xo, part)."""
     B = ctx.B
 
+    judged = [True] * B  # per chain: every reference value finite
+
     def upd(k, a, b):
-        _upd(worst, k, a, b)
+        judged[c] &= _upd(worst, k, a, b)
 
     c_h = ctx.constr()
     du_h, dv_h = ctx.jacob_constr_blocks()
@@ -100,18 +111,21 @@ def _ops_at_point(ctx, osys, q, xo, part, rng, worst):
         upd("rmult_jacob", JTl[c], JTlo)
         upd("inv_gram", Gil[c], Gilo)
         upd("normal_space", nsc[c], nsco)
+    return judged
 
 
-def check_ops_against_oracle(ctx, case, tol=1e-10):
-    """Every per-op entry point of the C ABI against the C oracle, for every partition; returns max rel errors."""
+def check_ops_against_oracle(ctx, case, tol=1e-10, parts=None):
+    """Every per-op entry point of the C ABI against the C oracle, for every partition; returns max rel errors and, under
+    "unjudged_chains", how many (partition, chain) points the oracle itself had a non-finite value at (not compared there).
+    parts: the partitions to visit (default: all, in order)."""
     osys, q, xo, B = case["osys"], case["q"], case["x_obs"], case["B"]
     rng = case["rng"]
     worst = {}
-    for part in range(ctx.num_partition):
+    for part in range(ctx.num_partition) if parts is None else parts:
         p = rng.standard_normal((B, ctx.Q))
         ctx.set_state(q, p, xo, part)
-        _ops_at_point(ctx, osys, q, xo, part, rng, worst)
-    bad = {k: v for k, v in worst.items() if not v < tol}
+        _count_unjudged(worst, _ops_at_point(ctx, osys, q, xo, part, rng, worst))
+    bad = failures(worst, tol)
     assert not bad, f"op parity failures (rel err): {bad}; all: {worst}"
     return worst
 
@@ -127,16 +141,17 @@ def check_ops_at_current_state(ctx, osys, tol=1e-10, x_obs_current=True, rng=Non
     q, p, xo, part = ctx.get_state()
     assert (ctx.M_0 is None) == (getattr(osys, "M0", None) is None), "oracle and context must have the same metric"
     worst = {}
-    _ops_at_point(ctx, osys, q, xo, part, np.random.default_rng(0) if rng is None else rng, worst)
+    judged = _ops_at_point(ctx, osys, q, xo, part, np.random.default_rng(0) if rng is None else rng, worst)
     h = ctx.hamiltonian()
     current = np.broadcast_to(np.asarray(x_obs_current, dtype=bool), (ctx.B,))
     for c in range(ctx.B):
         ch = c_oracle.OracleChain(osys)
         ch.set(q[c], p[c], xo[c], part)
-        _upd(worst, "hamiltonian", np.array([h[c, 0]]), np.array([ch.hamiltonian()]))
+        judged[c] &= _upd(worst, "hamiltonian", np.array([h[c, 0]]), np.array([ch.hamiltonian()]))
         if current[c]:
-            _upd(worst, "x_obs_seq", xo[c], osys.generate_x_obs_seq(q[c]))
-    bad = {k: v for k, v in worst.items() if not v < tol}
+            judged[c] &= _upd(worst, "x_obs_seq", xo[c], osys.generate_x_obs_seq(q[c]))
+    _count_unjudged(worst, judged)
+    bad = failures(worst, tol)
     assert not bad, f"op parity failures at the current state (rel err): {bad}; all: {worst}"
     return worst
 

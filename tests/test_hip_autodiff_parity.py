@@ -16,7 +16,9 @@ Seeds that were replaced: fhn_noisy_s16 106 -> 206 (chain 64, quasi-Newton: reve
 metric_fhn_nb_6_4_2 125 -> 425 (125: chain 2, quasi-Newton, forward |c| 9.93e-10; 225 and 325: a chain whose
 step does not succeed in either oracle); sir_two_16row_blocks 105 -> 205 (seed 105
 puts a perturbed state where a 16-row Gram block is numerically singular: the autodiff oracle's Cholesky refuses it);
-fhn_k65_rm7 111 -> 211 (chain 2, quasi-Newton: reverse |c| 9.96e-10 at the stop).  fhn_k65_rm7 is the 325-observation
+fhn_k65_rm7 111 -> 211 (chain 2, quasi-Newton: reverse |c| 9.96e-10 at the stop); sir16_k5_6_rows9 115 -> 215 (115: as 105, a
+perturbed state whose Gram block the autodiff oracle's Cholesky refuses).  sir_two_16row_blocks has had its Newton and
+quasi-Newton steps since the reference step was seen to succeed at its 0.1 between observations.  fhn_k65_rm7 is the 325-observation
 layout (K = [65, 66], 7 row slots), not the smaller stand-in: its test_references_agree case takes 60 to 100 s here on
 16 threads.
 
@@ -66,7 +68,11 @@ MID = {
     "sir16_s16": ("sir", 14, 16, 14, True, False, False, 37, C37, SIR16_STEPS, 102, 0.02),
     "sir16_s8_varsigma": ("sir", 14, 8, 14, True, False, True, 37, C37, SIR16_STEPS, 103, 0.02),
     "sir16_s16_varsigma": ("sir", 14, 16, 14, True, False, True, 37, C37, SIR16_STEPS, 204, 0.02),
-    "sir_two_16row_blocks": ("sir", 26, 24, 13, True, False, False, 5, [0, 2, 4], [], 205, 0.02),
+    "sir_two_16row_blocks": ("sir", 26, 24, 13, True, False, False, 5, [0, 2, 4], NQ, 205, 0.02),
+    # 16 row slots with several blocks per chain (tests/test_hip_multiblock16.py), every chain judged: K = [4, 5] (the interval-
+    # parallel and the stored-rows state evaluation in one context) and K = [5, 6] with 9 rows in 16 slots
+    "sir16_k4_5": ("sir", 40, 8, 10, True, False, False, 5, C5, NQ, 114, 0.02),
+    "sir16_k5_6_rows9": ("sir", 30, 8, 6, True, False, False, 5, C5, NQ, 215, 0.02),
     "fhn_noisy_s16": ("fhn", 12, 16, 5, True, False, False, 70, C70, NQ + [(True, 1, False)], 206, 0.05),
     "fhn_noiseless_gauss_s8": ("fhn", 7, 8, 3, False, True, False, 70, C70, NQ, 107, 0.05),
     "fhn_nb_noiseless_gauss_s8": ("fhn_nb", 7, 8, 3, False, True, False, 70, C70, NQ, 108, 0.05),
@@ -87,13 +93,17 @@ for _m, _T, _S, _R, _n, _seed in METRIC:
 FULL_SIR = ("sir", 14, 200, 14, True, False, False, 2, [0, 1], [(True, 1, True)], 141, 0.02)
 
 
+INTERVALS = {"sir_two_16row_blocks": 0.1, "sir16_k4_5": 0.05, "sir16_k5_6_rows9": 0.05}  # time between observations, by name
+
+
 def plan(name, cfg, ctx=None):
     """The inputs of one case: states for the operators (each chain its own OFF-manifold point), on-manifold states,
     raw momenta and step sizes for the steps.  Noiseless data need `ctx` (library) to spread the chains."""
     model, T, S, R, noisy, gaussian, var_sigma, B, chains, steps, seed, h = cfg
     # (SIR over 26 observations 0.25 apart: the prior draw's Gram matrix is so poorly conditioned that the two references
     # agree to 1e-9 only in inverse-Gram products; at 0.1 apart they agree to the bound asked of every other case)
-    oi = 0.1 if name == "sir_two_16row_blocks" else 0.25 if model == "sir" else None
+    # (the layouts of tests/test_hip_multiblock16.py: 0.05 apart, as there)
+    oi = INTERVALS.get(name, 0.25 if model == "sir" else None)
     rng = np.random.default_rng(seed)
     if noisy:
         case = distinct_on_manifold_chains(model, T, S, R, B, seed, obs_interval=oi, var_sigma=var_sigma)
@@ -224,7 +234,7 @@ def _gpu_case(name, cfg, want=("grad", "products")):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", [n for n in MID if n.startswith("sir16")])
+@pytest.mark.parametrize("name", [n for n in MID if n.startswith("sir16_s")])
 def test_sixteen_row_kernels(name):
     """SIR T = 14, R = 14 (one 16-row block per chain: k_traj_chain, k_retract_chain, k_fwd_par, k_newton_ivl /
     k_newton_comb_wg, state_factor16 / newton_factor16, k_gld_ivl_*), S = 8 and 16, fixed and variable sigma, 37 distinct
@@ -239,9 +249,23 @@ def test_sixteen_row_kernels(name):
 
 @pytest.mark.gpu
 def test_two_sixteen_row_blocks_both_partitions():
-    """SIR T = 26, R = 13, S = 24: two 16-row blocks per chain, both partitions, every operator, 3 chains."""
+    """SIR T = 26, R = 13, S = 24: two 16-row blocks per chain, both partitions, every operator, 3 chains; Newton and
+    quasi-Newton steps in partition 0."""
     ctx, _ = _gpu_case("sir_two_16row_blocks", MID["sir_two_16row_blocks"])
     assert ctx.RM == 16 and ctx.num_partition == 2
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["sir16_k4_5", "sir16_k5_6_rows9"])
+def test_sixteen_row_blocks_several_per_chain(name):
+    """SIR (40, 8, 10), K = [4, 5], and (30, 8, 6), K = [5, 6] (9 rows in 16 slots), 0.05 between observations: all 5 distinct
+    chains, every operator in both partitions (interval-parallel state evaluation up to 4 blocks per chain, stored rows beyond),
+    Newton and quasi-Newton steps in partition 0, judged by the oracle that shares no model code with the device."""
+    ctx, traj = _gpu_case(name, MID[name])
+    d = ctx.diagnostics()
+    assert ctx.RM == 16 and ctx.K == {"sir16_k4_5": [4, 5], "sir16_k5_6_rows9": [5, 6]}[name]
+    assert traj == 0 and d["retract_kernel_launches"] == 0 and d["gram_valu_launches"] > 0, d
     ctx.close()
 
 

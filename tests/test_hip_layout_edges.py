@@ -191,11 +191,23 @@ def test_one_context_takes_both_newton_paths_across_a_partition_switch():
     ctx.close()
 
 
-def switch_body(ctx, case, cfg, on_device=True):
+def fsm_or_factor8(ctx, part, d0, d1):
+    """The launch counters of the two Newton rounds of blocks of at most 8 rows, around a Newton step in `part`: K <= 64 raises
+    out80[68] only, K > 64 out80[69] only."""
+    fsm, factor8 = (d1[k] - d0[k] for k in ("newton_fsm_launches", "newton_factor8_launches"))
+    print(f"  partition {part} (K = {ctx.K[part]}): out80[68] +{fsm}, out80[69] +{factor8}")
+    assert (fsm > 0 and factor8 == 0) if ctx.K[part] <= 64 else (fsm == 0 and factor8 > 0), (fsm, factor8)
+
+
+def switch_body(ctx, case, cfg, on_device=True, witness=fsm_or_factor8, after_switch=None, dt_scale=0.25, seed=5):
+    """A step in partition 0, chmc_switch_partition, a step in partition 1, back, a step in partition 0: distinct chains from
+    their own points, each against an oracle chain that does the same (status 0, both iteration counts, 1e-9).  On the device
+    witness(ctx, part, diagnostics before, after) judges the launch counters around each step; after_switch(ctx), if given,
+    runs after every switch (both sides have projected their momenta by then)."""
     from oracle import c_oracle
-    B, dts = case["B"], 0.25 * dts_of(cfg)  # (from the chains' own, distinct points: chain 2 diverges in the oracle at 0.1)
-    assert ctx.K == [64, 65]
-    p_raw = np.random.default_rng(5).standard_normal(case["q"].shape)
+    B, dts = case["B"], dt_scale * dts_of(cfg)  # (FHN, from the chains' own, distinct points: chain 2 diverges in the oracle at 0.1)
+    assert ctx.K == cfg[9] and ctx.num_partition == 2
+    p_raw = np.random.default_rng(seed).standard_normal(case["q"].shape)
     ctx.set_state(case["q"], p_raw, case["x_obs"], 0)
     ctx.project_onto_cotangent_space()
     chains = []
@@ -217,10 +229,8 @@ def switch_body(ctx, case, cfg, on_device=True):
             assert (res["status"][c], res["iters_fwd"][c], res["iters_bwd"][c]) == (st, itf, itb) and st == 0, (c, res, st, itf, itb)
             assert np.abs(q1[c] - qo).max() <= 1e-9 * max(1.0, np.abs(qo).max()), c
             assert np.abs(p1[c] - po).max() <= 1e-9 * max(1.0, np.abs(po).max()), c
-        delta = (d1["newton_fsm_launches"] - d0["newton_fsm_launches"],
-                 d1["newton_factor8_launches"] - d0["newton_factor8_launches"])
-        print(f"  partition {part} (K = {ctx.K[part]}): out80[68] +{delta[0]}, out80[69] +{delta[1]}")
-        return delta
+        if on_device:
+            witness(ctx, part, d0, d1)
 
     def switch():
         ctx.switch_partition()
@@ -228,15 +238,14 @@ def switch_body(ctx, case, cfg, on_device=True):
         for ch in chains:
             ch.switch_partition()
             ch.project_mom()
+        if after_switch is not None:
+            after_switch(ctx)
 
-    fsm, factor8 = step_and_compare(0)
-    assert not on_device or (fsm > 0 and factor8 == 0)
+    step_and_compare(0)
     switch()
-    fsm, factor8 = step_and_compare(1)
-    assert not on_device or (fsm == 0 and factor8 > 0)
-    switch()  # ... and back to the fused round with the 65-strided arrays
-    fsm, factor8 = step_and_compare(0)
-    assert not on_device or (fsm > 0 and factor8 == 0)
+    step_and_compare(1)
+    switch()  # ... and back, with the arrays strided by Kmax
+    step_and_compare(0)
 
 
 @pytest.mark.gpu
@@ -254,15 +263,16 @@ def test_masked_and_failing_chains_past_64_blocks(name, newton):
     ctx.close()
 
 
-def masked_body(ctx, case, cfg, newton):
+def masked_body(ctx, case, cfg, newton, dt_scale=0.25, max_iters=None, seed=16):
     from oracle import c_oracle
     B = case["B"]
-    dts = 0.25 * dts_of(cfg)  # (as in switch_body)
+    dts = dt_scale * dts_of(cfg)  # (as in switch_body)
     dts[1] = 5.0
-    max_iters = 3 if newton else 8  # (quasi-Newton needs 4 to 7 iterations at these step sizes)
+    if max_iters is None:
+        max_iters = 3 if newton else 8  # (FHN: quasi-Newton needs 4 to 7 iterations at these step sizes)
     active = np.ones(B, dtype=np.int32)
     active[3] = 0
-    p_raw = np.random.default_rng(16).standard_normal(case["q"].shape)
+    p_raw = np.random.default_rng(seed).standard_normal(case["q"].shape)
     for part in range(ctx.num_partition):
         ctx.set_state(case["q"], p_raw, case["x_obs"], part)
         ctx.project_onto_cotangent_space()

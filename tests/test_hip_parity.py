@@ -748,13 +748,15 @@ def test_half_batches_sixteen_row_blocks(monkeypatch, row_split):
     """Half-batch views of the arrays that only 16-row layouts with several blocks per chain have (one 16-row block per chain
     always runs as one batch): SIR (26, 24, 13) at 0.1, K = [2, 3], 7 chains (3 / 4), both partitions, bitwise against the
     one-batch step.  Default switches: the interval-parallel sweeps (work.gcq, gbw, ivl, Slots::PB, LF with 16 row slots);
-    CHMC_ROW_SPLIT=1: the stored-rows 16-row sweeps (work.JvW and Slots::Jv with 16 row slots)."""
+    CHMC_ROW_SPLIT=1: the stored-rows 16-row sweeps (work.JvW and Slots::Jv with 16 row slots).  Then SIR (40, 8, 10) at 0.05,
+    K = [4, 5]: by default partition 0 takes the first family and partition 1 the second, with views strided by Kmax = 5."""
     from helpers import halves_vs_single_batch
     if row_split:
         monkeypatch.setenv("CHMC_ROW_SPLIT", row_split)
-    case = make_case("sir", 26, 24, 13, True, B=7, seed=81, obs_interval=0.1)
-    for part in range(2):
-        halves_vs_single_batch(case, monkeypatch, part=part, masked=(1, 6), failing=(2, 4))
+    for case in (make_case("sir", 26, 24, 13, True, B=7, seed=81, obs_interval=0.1),
+                 make_case("sir", 40, 8, 10, True, B=7, seed=81, obs_interval=0.05)):
+        for part in range(2):
+            halves_vs_single_batch(case, monkeypatch, part=part, masked=(1, 6), failing=(2, 4))
 
 
 _HALVES_FAMILY_SCRIPT = r"""
@@ -788,18 +790,29 @@ def test_half_batches_stored_row_families():
 
 # variable observation noise: sigma = generate_σ_y(u) = exp(u[dim_z]), dim_u = dim_z + 1
 # (sde/mici_extensions.py:353-358, 559-569, 601-608; scripts/sir_model_chmc_experiment.py:44,58,77)
-VS_CASES =[("sir", 5, 6, None, False), ("sir", 6, 8, 2, False), ("sir", 6, 16, 2, False), ("fhn", 6, 8, 2, False),
-            ("fhn", 7, 5, 3, True), ("sir", 14, 8, 14, False)]
+# model, T, S, R, gaussian, time between observations (None: the model's default)
+VS_CASES = [("sir", 5, 6, None, False, None), ("sir", 6, 8, 2, False, None), ("sir", 6, 16, 2, False, None),
+            ("fhn", 6, 8, 2, False, None), ("fhn", 7, 5, 3, True, None), ("sir", 14, 8, 14, False, None),
+            ("sir", 40, 8, 10, False, 0.05)]  # SirVsModel with 16 row slots and K = [4, 5]
 
 
-@pytest.mark.parametrize("model,T,S,R,gaussian", VS_CASES)
-def test_variable_observation_noise(model, T, S, R, gaussian):
-    case = make_case(model, T, S, R, True, B=23, seed=11, gaussian=gaussian, var_sigma=True)
+# Seeds of the operator case and of the step case, where not 11 and 12.  SIR (40, 8, 10), screened on the CPU emulation build:
+# with 11, 31 or 131 one of the 23 prior draws runs into the model's +-500 clip and the oracle's own Cholesky factors are NaN
+# there (unjudged_chains = 1); 231 is clean, and no retraction residual of the step case lies within 1e-2 of a tolerance.
+VS_SEEDS = {("sir", 40, 8, 10): (231, 12)}
+
+
+@pytest.mark.parametrize("model,T,S,R,gaussian,obs_interval", VS_CASES, ids=["-".join(map(str, c[:5])) for c in VS_CASES])
+def test_variable_observation_noise(model, T, S, R, gaussian, obs_interval):
+    ops_seed, steps_seed = VS_SEEDS.get((model, T, S, R), (11, 12))
+    case = make_case(model, T, S, R, True, B=23, seed=ops_seed, gaussian=gaussian, var_sigma=True, obs_interval=obs_interval)
     ctx = make_ctx(case)
     assert ctx.U == 5 and ctx.Q == case["q"].shape[1]
-    check_ops_against_oracle(ctx, case)
+    worst = check_ops_against_oracle(ctx, case)
+    print("  operators (rel):", {k: f"{v:.1e}" for k, v in worst.items()})
+    assert obs_interval is None or worst["unjudged_chains"] == 0
     ctx.close()
-    case = make_case(model, T, S, R, True, B=5, seed=12, gaussian=gaussian, var_sigma=True)
+    case = make_case(model, T, S, R, True, B=5, seed=steps_seed, gaussian=gaussian, var_sigma=True, obs_interval=obs_interval)
     ctx = make_ctx(case)
     dts = np.array([0.05, -0.05, 0.1, 0.02, -0.08])
     for newton in ((True,) if R == 14 else (True, False)):  # (14-row quasi-Newton counts sit on the tolerance's edge)
@@ -1086,8 +1099,13 @@ def test_time_parallel_scan_absorbed_and_nan_trajectories(monkeypatch):
     assert np.isfinite(xs).sum() >= B // 4
 
 
+# Seeds where not 23 + T, screened on the CPU emulation build: (39, 8, 13) with 62 has a chain whose oracle values are not
+# finite (the model's +-500 clip), (40, 8, 10) with 63 a forward |dq| of 9.985e-09 against position_tol 1e-8.
+SPLIT_SEEDS = {(39, 8, 13): 31, (40, 8, 10): 31}
+
+
 @pytest.mark.parametrize("split", ["1", "4"])
-@pytest.mark.parametrize("T,S,R,B", [(14, 200, 14, 3), (26, 24, 13, 5), (16, 72, 16, 2)])
+@pytest.mark.parametrize("T,S,R,B", [(14, 200, 14, 3), (26, 24, 13, 5), (16, 72, 16, 2), (39, 8, 13, 5), (40, 8, 10, 5)])
 def test_sixteen_row_blocks_row_split_settings(monkeypatch, split, T, S, R, B):
     """16-row blocks (SIR): the two state evaluations (CHMC_ROW_SPLIT=1: the stored-rows sweeps k_rev_wave_ldsrows +
     k_gram_rows + k_gld_fwd_wave + k_gld_bwd_wave_ldsrows that large batches keep; otherwise, the default for up to 1 024
@@ -1096,14 +1114,20 @@ def test_sixteen_row_blocks_row_split_settings(monkeypatch, split, T, S, R, B):
     k_gld_ivl_finish) against the C oracle: every per-operator entry point (chol_gram_blocks :794-810,
     grad_log_det_sqrt_gram :1143-1146, jacob_constr_blocks :704-763 -- the rows are rebuilt from the compact form on demand)
     and two leapfrog steps; single-block layout at full size, two blocks per chain (13 observation rows + 3 state rows, then
-    13 rows) and a full 16-row block."""
+    13 rows) and a full 16-row block.  S = 8: 0.05 between observations (Gram blocks of condition number of the order of 1e3 instead
+    of 3.8e7), K = [3, 4] with full 16-row blocks and K = [4, 5], at the project's 1e-10: CHMC_ROW_SPLIT=1 puts 3 and 4 blocks per
+    chain on the stored-rows sweeps, CHMC_ROW_SPLIT=4 puts 5 blocks per chain on the interval-parallel ones -- the two settings
+    the default plan never chooses for them.  The steps run in every partition."""
     monkeypatch.setenv("CHMC_ROW_SPLIT", split)
-    case = make_case("sir", T, S, R, True, B=B, seed=23 + T, obs_interval=0.25)
+    case = make_case("sir", T, S, R, True, B=B, seed=SPLIT_SEEDS.get((T, S, R), 23 + T), obs_interval=0.05 if S == 8 else 0.25)
     ctx = make_ctx(case)
     assert ctx.RM == 16
     # (the two-block prior draw has a poorly conditioned Gram matrix: inverse-Gram products agree to 1e-8 in every setting)
-    check_ops_against_oracle(ctx, case, tol=1e-7 if T == 26 else 1e-9)
-    check_steps_against_oracle(ctx, case, np.where(np.arange(B) % 2 == 0, 0.02, -0.02), n_steps=2)
+    worst = check_ops_against_oracle(ctx, case, **({} if S == 8 else {"tol": 1e-7 if T == 26 else 1e-9}))
+    print("  operators (rel):", {k: f"{v:.1e}" for k, v in worst.items()})
+    assert S != 8 or worst["unjudged_chains"] == 0
+    for part in range(ctx.num_partition):
+        check_steps_against_oracle(ctx, case, np.where(np.arange(B) % 2 == 0, 0.02, -0.02), n_steps=2, part=part)
     ctx.close()
 
 

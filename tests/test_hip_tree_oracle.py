@@ -49,6 +49,7 @@ import sys
 import numpy as np
 import pytest
 from helpers import make_case, make_ctx, check_ops_at_current_state, oracle_tree_transition
+from autodiff_checks import largest
 from test_hip_autodiff_parity import distinct_on_manifold_chains
 from test_emu_logic import emu_lib  # noqa: F401
 from test_rng import reference_normals
@@ -270,7 +271,7 @@ def transitions_body(ctx, case, cfg, max_delta_h=1000.0):
             w = check_ops_at_current_state(ctx, osys, x_obs_current=~moved)
             ctx.switch_partition()
             w2 = check_ops_at_current_state(ctx, osys)
-            worst["ops"] = max(worst["ops"], max(w.values()) / 1e-10, max(w2.values()) / 1e-10)
+            worst["ops"] = max(worst["ops"], largest(w) / 1e-10, largest(w2) / 1e-10)
         ctx.set_metric(None)
     finally:
         osys.set_metric(None)
@@ -327,10 +328,10 @@ def restore_body(ctx, case, cfg):
     assert np.array_equal(q2, np.where(keep, q1, q0)) and np.array_equal(p2, np.where(keep, p1, p0))
     assert np.array_equal(q2[[1, 3]], q0[[1, 3]]) and np.array_equal(p2[[1, 3]], p0[[1, 3]])
     # 5-7: caches at the reported point, the next step (tangent momenta: p - h pg), the switch, the step after it
-    worst["ops_after_restore"] = max(check_ops_at_current_state(ctx, osys, x_obs_current=np.arange(B) != 2).values()) / 1e-10
+    worst["ops_after_restore"] = largest(check_ops_at_current_state(ctx, osys, x_obs_current=np.arange(B) != 2)) / 1e-10
     worst["step_after_restore"] = _step_and_compare(ctx, osys, dts, "after restore")
     ctx.switch_partition()
-    worst["ops_after_switch"] = max(check_ops_at_current_state(ctx, osys).values()) / 1e-10
+    worst["ops_after_switch"] = largest(check_ops_at_current_state(ctx, osys)) / 1e-10
     worst["step_after_switch"] = _step_and_compare(ctx, osys, dts, "after switch")
     # 8: restore_device from buffers that hold the oracle's own stepped states (chain 3 is left as it is)
     rng = np.random.default_rng(seed + 2)
@@ -355,7 +356,7 @@ def restore_body(ctx, case, cfg):
         keep = (mask == 0)[:, None]
         assert np.array_equal(q3, np.where(keep, qc, qn)) and np.array_equal(p3, np.where(keep, pc, pn)), tangent
         k = "tangent" if tangent else "raw"
-        worst[f"ops_after_restore_device_{k}"] = max(check_ops_at_current_state(ctx, osys, x_obs_current=False).values()) / 1e-10
+        worst[f"ops_after_restore_device_{k}"] = largest(check_ops_at_current_state(ctx, osys, x_obs_current=False)) / 1e-10
         worst[f"step_after_restore_device_{k}"] = _step_and_compare(ctx, osys, dts, f"after restore_device {k}")
     # 9
     for n in (1, 6, ctx.Q):

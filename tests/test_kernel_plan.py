@@ -76,6 +76,11 @@ LAYOUTS = {
     "fhn_k64_65": layout("fhn", 128, 4, 2, True, chains=5),
     "fhn_k65_66_rm7": layout("fhn", 325, 8, 5, True, chains=5),
     "sir_k66_67": layout("sir", 132, 4, 2, True, chains=5),
+    # 16 row slots with 4 | 5 blocks per chain, and few long blocks with K > 1 (tests/test_hip_multiblock16.py runs them on the GPU)
+    "sir16_k4_5": layout("sir", 40, 8, 10, True, chains=5),
+    "sir16_long_k3_4": layout("sir", 39, 80, 13, True, chains=5),
+    "fhn_long_k2_3": layout("fhn", 4, 512, 2, True, chains=5),
+    "fhn_long_w2_k2_3": layout("fhn", 4, 1024, 2, True, chains=5),
 }
 
 SWITCHES = [{}, {"CHMC_COMPACT_ROWS": "0"}, {"CHMC_GRAM_MFMA": "1"}, {"CHMC_PAR_SCAN": "0"}, {"CHMC_PAR_SCAN": "1"},
@@ -197,6 +202,18 @@ DEFAULT_PLANS = {  # no switch set: every layout is on the compact rows
     "fhn_k64_65": _plan("KFwd", 1, "KFwd", 1, True, True, _FHN, _COMB),
     "fhn_k65_66_rm7": _plan("k_fwd_scan", 1, "k_fwd_par", 2, False, True, _COMB, _COMB),
     "sir_k66_67": _plan("KFwd", 1, "KFwd", 1, False, True, _COMB, _COMB),
+    # K = [4, 5], 16 row slots: at most 4 blocks per chain take the interval-parallel state evaluation and rebuild the rows on
+    # demand, 5 blocks keep the rows of k_rev_wave_ldsrows -- in the same context; the Newton round is the same in both
+    "sir16_k4_5": _plan("k_fwd_scan", 1, "k_fwd_scan", 1, False, False,
+                        _part("ivl+comb", "ivl+comb,factor_wave,solve", "ivl", "k_jw_pb", True),
+                        _part("ldsrows+gram", "ivl+comb,factor_wave,solve", "compact_fwd+ldsrows_bwd", "k_jw_pb", False)),
+    # few_long_blocks (K <= 4, longest block >= 1024 steps) with several blocks per chain: the time-parallel scan, one wavefront
+    # per block below 2048 steps, two from there; the comparator's one block of T S steps: 3120 and 2048 steps 2 wavefronts, 4096 4
+    "sir16_long_k3_4": _plan("k_fwd_par", 1, "k_fwd_par", 2, False, False,
+                             *[_part("ivl+comb", "ivl+comb,factor_wave,solve", "ivl", "k_jw_pb", True)] * 2, par_scan=True,
+                             fwd_cold="k_fwd_scan"),
+    "fhn_long_k2_3": _plan("k_fwd_par", 1, "k_fwd_par", 2, True, True, _FHN, _FHN, par_scan=True, fwd_cold="k_fwd_scan"),
+    "fhn_long_w2_k2_3": _plan("k_fwd_par", 2, "k_fwd_par", 4, True, True, _FHN, _FHN, par_scan=True, fwd_cold="k_fwd_scan"),
 }
 
 _CHILD = r"""
@@ -250,6 +267,12 @@ def test_layout_integers():
     assert LAYOUTS["fhn_k64_65"]["K"] == [64, 65] and LAYOUTS["fhn_k64_65"]["rmt"] == 8
     assert LAYOUTS["fhn_k65_66_rm7"]["K"] == [65, 66] and LAYOUTS["fhn_k65_66_rm7"]["rmt"] == 7
     assert LAYOUTS["sir_k66_67"]["K"] == [66, 67] and LAYOUTS["sir_k66_67"]["rmt"] == 8
+    assert LAYOUTS["sir16_k4_5"] == dict(rmt=16, npart=2, K=[4, 5], longest=80, chain_steps=320, tiles8=True, V=3, even=False,
+                                         gaussian=False, chains=5, cus=256)
+    assert LAYOUTS["sir16_long_k3_4"]["K"] == [3, 4] and LAYOUTS["sir16_long_k3_4"]["longest"] == 1040
+    assert LAYOUTS["sir16_long_k3_4"]["rmt"] == 16 and LAYOUTS["sir16_long_k3_4"]["chain_steps"] == 3120
+    assert LAYOUTS["fhn_long_k2_3"]["K"] == [2, 3] and (LAYOUTS["fhn_long_k2_3"]["longest"], LAYOUTS["fhn_long_k2_3"]["rmt"]) == (1024, 8)
+    assert LAYOUTS["fhn_long_w2_k2_3"]["K"] == [2, 3] and LAYOUTS["fhn_long_w2_k2_3"]["longest"] == 2048
 
 
 def test_default_plans_by_hand(probe):
@@ -260,6 +283,11 @@ def test_default_plans_by_hand(probe):
     # K = [64, 65]: the wavefront-per-chain round (NewtonIvlFsm) holds one block per lane, so 64 blocks are its last layout
     # and the 65 blocks of the other partition take the unfused round (NewtonIvlComb) -- in the same context
     assert [pp["newton"] for pp in got["fhn_k64_65"]["part"]] == ["ivl+comb,fsm", "ivl+comb,factor,solve"]
+    # K = [4, 5] with 16 row slots: both state evaluations in one context
+    assert [(pp["state"], pp["rebuild_rows"]) for pp in got["sir16_k4_5"]["part"]] == [("ivl+comb", True), ("ldsrows+gram", False)]
+    # the time-parallel scan never pairs retractions and is the only scan with more than one wavefront per block
+    for name in ("sir16_long_k3_4", "fhn_long_k2_3", "fhn_long_w2_k2_3"):
+        assert got[name]["par_scan"] and got[name]["fwd"] == "k_fwd_par" and got[name]["fwd_cold"] == "k_fwd_scan", name
 
 
 @pytest.mark.parametrize("env", SWITCHES + [{"CHMC_COMPACT_ROWS": "0", "CHMC_GRAM_MFMA": "1"}, {"CHMC_RETRACT_KERNEL": "0"},

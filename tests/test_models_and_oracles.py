@@ -330,3 +330,68 @@ def test_autodiff_oracle_block_metric_against_c_oracle_and_dense_algebra(model, 
     osy.set_metric(None)
     with pytest.raises(ValueError):  # sde/mici_extensions.py:293-300
         osys.make_system(omodels.fhn, 0.2, 4, 2, np.zeros((6, 1)), sigma=0.1, use_gaussian_splitting=True, M_0=M0)
+
+
+def test_operator_comparators_do_not_drop_non_finite_values():
+    """helpers._upd and autodiff_checks.compare_ops (no library involved): a NaN or an inf on the library side where the
+    reference is finite fails the enclosing check -- max(0.0, nan) is 0.0, so a plain running maximum would lose it --, and a
+    NaN on the reference side is not compared but counts the chain under "unjudged_chains", which no tolerance applies to."""
+    import autodiff_checks as ac
+    import helpers
+    ref = np.array([1.0, -2.0, 3.0])
+    for poison in (np.nan, np.inf, -np.inf):
+        for first in (True, False):  # the poisoned chain before / after a clean one: the running maximum must keep it
+            worst = {}
+            lib = ref.copy()
+            lib[1] = poison
+            judged = [helpers._upd(worst, "op", a, ref) for a in ((lib, ref + 1e-13) if first else (ref + 1e-13, lib))]
+            helpers._count_unjudged(worst, judged)
+            assert worst["op"] == np.inf and worst[ac.UNJUDGED] == 0 and ac.failures(worst, 1e-10) == {"op": np.inf}
+    # NaN in the reference: that entry is skipped, the others are judged, the chain is counted once
+    worst = {}
+    bad_ref = ref.copy()
+    bad_ref[0] = np.nan
+    judged = [helpers._upd(worst, "op", ref + 1e-13, bad_ref) & helpers._upd(worst, "op2", ref, np.full(3, np.nan)),
+              helpers._upd(worst, "op", ref, ref)]
+    helpers._count_unjudged(worst, judged)
+    assert judged == [False, True] and worst[ac.UNJUDGED] == 1 and 0 < worst["op"] < 1e-12 and worst["op2"] == 0.0
+    assert ac.failures(worst, 1e-10) == {}
+    worst = {}
+    helpers._upd(worst, "op", ref + 1.0, bad_ref)  # ... and a finite entry beside it that is wrong still fails
+    assert ac.failures(worst, 1e-10) == {"op": 1.0 / 3.0}
+
+    # compare_ops: one chain, two blocks of 2 and 1 rows
+    rng = np.random.default_rng(0)
+    good = dict(c=rng.standard_normal(3), dc_du=rng.standard_normal((3, 4)), dc_dv=rng.standard_normal((2, 7)),
+                chol_C=rng.standard_normal((4, 4)), chol_D=[rng.standard_normal((2, 2)), rng.standard_normal((1, 1))],
+                Jw=rng.standard_normal(3), Ginv_lam=rng.standard_normal(3), grad=rng.standard_normal(11), log_det=0.7)
+
+    def as_library(r, pad_rows=1):
+        out = {k: {0: np.array(v, copy=True)} for k, v in r.items() if k not in ("dc_dv", "chol_D")}
+        out["dc_dv"] = {0: np.vstack([r["dc_dv"], np.zeros((pad_rows, 7))])}
+        out["chol_D"] = {0: [np.pad(b, ((0, 3), (0, 3))) for b in r["chol_D"]]}
+        return out
+
+    worst = {}
+    ac.compare_ops(as_library(good), good, 0, [2, 1], worst)
+    assert ac.failures(worst, 1e-10) == {} and worst[ac.UNJUDGED] == 0 and ac.largest(worst) == 0.0
+    for key, poison in (("grad", np.nan), ("chol_D", np.nan), ("log_det", np.inf), ("dc_dv", np.nan)):
+        lib = as_library(good)
+        if key == "chol_D":
+            lib[key][0][1][0, 0] = poison
+        elif key == "log_det":
+            lib[key][0] = np.array(poison)
+        elif key == "dc_dv":
+            lib[key][0][2, 3] = poison  # (a padded row slot)
+        else:
+            lib[key][0][1] = poison
+        worst = {}
+        ac.compare_ops(as_library(good), good, 0, [2, 1], worst)  # a clean chain first and last
+        ac.compare_ops(lib, good, 0, [2, 1], worst)
+        ac.compare_ops(as_library(good), good, 0, [2, 1], worst)
+        assert ac.failures(worst, 1e-9) == {"dc_dv_pad" if key == "dc_dv" else key: np.inf} and worst[ac.UNJUDGED] == 0, key
+    bad = dict(good, grad=np.full(11, np.nan), chol_D=[np.full((2, 2), np.nan), good["chol_D"][1]])
+    worst = {}
+    ac.compare_ops(as_library(good), bad, 0, [2, 1], worst)
+    ac.compare_ops(as_library(good), good, 0, [2, 1], worst)
+    assert worst[ac.UNJUDGED] == 1 and ac.failures(worst, 1e-9) == {}

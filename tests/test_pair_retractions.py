@@ -97,6 +97,11 @@ def compare(case, n_steps, part=0, newton=True, late_failure=False, merged_scan=
 SHAPES = [("fhn", 10, 8, 5, True, False), ("fhn", 12, 16, 5, True, False)]
 # one case each: FitzHugh-Nagumo noiseless, partitioned SIR with R = 2, Gaussian splitting
 OTHERS = [("fhn", 12, 16, 5, False, False), ("sir", 6, 16, 2, True, False), ("fhn", 7, 8, 3, False, True)]
+# 16 row slots with several blocks per chain, SIR at 0.05 between observations (k_fwd_scan<SirModel, 16, .., PAIR>; pair_alloc sizes a
+# second set of 16-row work arrays): K = [4, 5] -- interval-parallel and stored-rows state evaluation -- and K = [5, 6] with 9 rows
+# in 16 slots.  On the emulation build 68 of the 70 chains complete (the masked chain has status -1, the failing one status 2).
+SIR16 = [("sir", 40, 8, 10, True, False), ("sir", 30, 8, 6, True, False)]
+SIR16_INTERVAL = 0.05
 # Reversibility tolerance of the discarded-speculation case, chosen with the emulation build at SHAPES[0], 5 steps: the
 # reverse-check distances of a step lie between 1.3e-15 and 8.3e-15 there (the retractions converge to rounding), and at 5e-15
 # 36 chains fail the check (status 3) after at least one good step -- their forward retraction of the next step has run beside
@@ -112,8 +117,8 @@ def _cases(n_steps_list, shapes):
                                    f"{'noisy' if noisy else 'noiseless'}{'-gauss' if gaussian else ''}-p{part}-n{n}")
 
 
-def _check_all(model, T, S, R, noisy, gaussian, part, n_steps, merged_scan, **kw):
-    case = make_case(model, T, S, R, noisy, B=B, seed=21, gaussian=gaussian)
+def _check_all(model, T, S, R, noisy, gaussian, part, n_steps, merged_scan, obs_interval=None, **kw):
+    case = make_case(model, T, S, R, noisy, B=B, seed=21, gaussian=gaussian, obs_interval=obs_interval)
     return compare(case, n_steps, part=part, merged_scan=merged_scan, **kw)
 
 
@@ -141,6 +146,12 @@ def test_paired_equals_unpaired(emu_lib, model, T, S, R, noisy, gaussian, part, 
 @pytest.mark.parametrize("model,T,S,R,noisy,gaussian,part,n_steps", _cases((3,), OTHERS))
 def test_paired_equals_unpaired_other_models(emu_lib, model, T, S, R, noisy, gaussian, part, n_steps):  # noqa: F811
     _check_all(model, T, S, R, noisy, gaussian, part, n_steps, False)
+
+
+@pytest.mark.parametrize("model,T,S,R,noisy,gaussian,part,n_steps", _cases((2, 5), SIR16))
+def test_paired_equals_unpaired_sixteen_row_blocks(emu_lib, model, T, S, R, noisy, gaussian, part, n_steps):  # noqa: F811
+    b = _check_all(model, T, S, R, noisy, gaussian, part, n_steps, False, obs_interval=SIR16_INTERVAL)
+    assert (b["r"]["n_done"] == n_steps).sum() == B - 2
 
 
 def test_paired_equals_unpaired_quasi_newton(emu_lib):  # noqa: F811
@@ -174,6 +185,14 @@ def test_paired_equals_unpaired_hip(model, T, S, R, noisy, gaussian, part, n_ste
 def test_paired_equals_unpaired_other_models_hip(model, T, S, R, noisy, gaussian, part, n_steps):
     _hip()
     _check_all(model, T, S, R, noisy, gaussian, part, n_steps, True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("model,T,S,R,noisy,gaussian,part,n_steps", _cases((2, 5), SIR16))
+def test_paired_equals_unpaired_sixteen_row_blocks_hip(model, T, S, R, noisy, gaussian, part, n_steps):
+    _hip()
+    b = _check_all(model, T, S, R, noisy, gaussian, part, n_steps, True, obs_interval=SIR16_INTERVAL)
+    print(f"  chains that completed all {n_steps} steps: {(b['r']['n_done'] == n_steps).sum()} of {B}")
 
 
 @pytest.mark.gpu

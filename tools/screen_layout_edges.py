@@ -1,10 +1,13 @@
-"""CPU screening of the cases of tests/test_hip_layout_edges.py: runs the module's run_case on the TEST-ONLY emulation
-build with every C-oracle step traced, and reports per case whether
+"""CPU screening of the cases of tests/test_hip_layout_edges.py and tests/test_hip_multiblock16.py (a case id is looked up in
+both tables): runs the module's run_case on the TEST-ONLY emulation build with every C-oracle step traced, and reports per case
+whether
   * every oracle step ended with status 0, and in how many iterations,
   * any retraction residual (|c| against constraint_tol 1e-9, |dq| against position_tol 1e-8) of any iteration of any chain
     lies within 1e-2 relative of its tolerance -- the condition of test_hip_autodiff_parity.reference_side under which
     "equal iteration counts" is a fair demand on the library.
-A seed that fails is replaced in the test module and noted there.
+A seed that fails is replaced in the test module and noted there.  The other bodies of the two modules that use a case
+(partition switches, masked and failing chains, trajectories) run after it, traced the same way; their chain at dt = 5.0 fails
+by design, so only the steps of run_case must all end with status 0.
 
     python tools/screen_layout_edges.py [case id | case id:seed to try ...]"""
 import os
@@ -19,6 +22,7 @@ import numpy as np  # noqa: E402
 from oracle import c_oracle  # noqa: E402
 from manifold_mcmc_for_diffusions_amd import _lib  # noqa: E402
 import test_hip_layout_edges as le  # noqa: E402
+import test_hip_multiblock16 as mb  # noqa: E402
 from helpers import make_ctx  # noqa: E402
 
 EDGE = 1e-2
@@ -51,13 +55,14 @@ def main(names):
     bad = []
     for name in names:
         name, _, seed = name.partition(":")
-        cfg = le.CASES[name][:12] + (int(seed) if seed else le.CASES[name][12],)
+        mod = mb if name in mb.CASES else le
+        cfg = mod.CASES[name][:12] + (int(seed) if seed else mod.CASES[name][12],)
         del log[:]
         t0 = time.time()
         case = le.build_case(cfg)
         ctx = make_ctx(case)
         try:
-            le.run_case(ctx, case, cfg, on_device=False)
+            mod.run_case(ctx, case, cfg, on_device=False)
             err = None
         except AssertionError as e:  # (the emulation build's own mismatch, if any, is reported and the screening goes on)
             err = str(e)[:300]
@@ -68,12 +73,26 @@ def main(names):
                 assert all(st == 0 for st, _, _, _ in log[n_case:])
             for newton in (True, False):
                 le.masked_body(ctx, case, cfg, newton)  # (one chain fails by design)
+        if err is None and mod is mb:
+            try:
+                if name == "sir16_k4_5":
+                    mb.switch_16(ctx, case, cfg, on_device=False)
+                    assert all(st == 0 for st, _, _, _ in log[n_case:])
+                n_switch = len(log)
+                if name in ("sir16_k4_5", "sir16_long_k3_4"):
+                    mb.trajectories(case, cfg)
+                    assert all(st == 0 for st, _, _, _ in log[n_switch:])
+                if name in mb.MASKED:
+                    for newton in (True, False):
+                        mb.masked_16(ctx, case, cfg, name, newton, on_device=False)  # (one chain fails by design)
+            except AssertionError as e:
+                err = "other bodies: " + str(e)[:300]
         ctx.close()
         iters = [i for _, f, b, _ in log for i in (f, b)]
         statuses = sorted({st for st, _, _, _ in log[:n_case]})
         near = [n for _, _, _, ns in log for n in ns]
         ok = statuses == [0] and not near and err is None
-        print(f"SCREEN {name}: seed {cfg[12]} steps {len(log)} statuses {statuses} iterations {min(iters)}..{max(iters)} "
+        print(f"SCREEN {name}: seed {cfg[12]} steps {len(log)} statuses {statuses} iterations {min(iters, default=None)}..{max(iters, default=None)} "
               f"near-edge {near} {'' if err is None else 'ASSERT ' + err} {time.time() - t0:.1f} s {'ok' if ok else 'REPLACE'}",
               flush=True)
         if not ok:
@@ -83,4 +102,4 @@ def main(names):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1:] or list(le.CASES)))
+    sys.exit(main(sys.argv[1:] or list(le.CASES) + list(mb.CASES)))
