@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """End-to-end example on an MI355X: posterior sampling for the FitzHugh-Nagumo model with noisy observations
 (the configuration of scripts/fhn_model_noisy_obs_chmc_experiment.py in the reference: T = 100 observations,
-R = 5, sigma_y = 0.1) with batched constrained HMC.   usage: fhn_noisy_chmc.py [chains] [S] [iters] [warm-up] [output dir] [static|dynamic|dynamic-shared|metric]
+R = 5, sigma_y = 0.1) with batched constrained HMC.   usage: fhn_noisy_chmc.py [chains] [S] [iters] [warm-up] [output dir] [static|dynamic|dynamic-shared|metric] [R]
+`R`: observations per sub-sequence (num_obs_per_subseq, the reference's --num-obs-per-subseq; default 5, at most 14: blocks of R + 2
+constraint rows, at most 16).
 `metric`: static trajectories with the block-diagonal metric adapter of the reference (sde/mici_extensions.py:1804-1931) on the
 four global parameters during the warm-up.
 With an output directory the traced variables of the reference's trace function (sigma, epsilon, gamma, beta, x_0,
@@ -24,6 +26,7 @@ out_dir = sys.argv[5] if len(sys.argv) > 5 and sys.argv[5] != "-" else None
 dynamic = len(sys.argv) > 6 and sys.argv[6] in ("dynamic", "dynamic-shared")  # the reference's transition (no-U-turn trees) instead of 16 fixed steps
 shared_step = len(sys.argv) > 6 and sys.argv[6] == "dynamic-shared"        # one shared step size in the warm-up instead of one per chain
 adapt_metric = len(sys.argv) > 6 and sys.argv[6] == "metric"
+R = int(sys.argv[7]) if len(sys.argv) > 7 else 5
 
 
 def trace_func(head, ham):  # scripts/fhn_model_noisy_obs_chmc_experiment.py:82-99
@@ -33,8 +36,9 @@ def trace_func(head, ham):  # scripts/fhn_model_noisy_obs_chmc_experiment.py:82-
 
 
 t0 = time.time()
-wl = FhnWorkload(B, num_steps_per_obs=S, device_init=True)  # initial states solved on the device
-print(f"set-up {time.time() - t0:.1f} s: {B} chains, dim_q = {wl.ctx.Q}", flush=True)
+wl = FhnWorkload(B, num_steps_per_obs=S, num_obs_per_subseq=R, device_init=True)  # initial states solved on the device
+print(f"set-up {time.time() - t0:.1f} s: {B} chains, dim_q = {wl.ctx.Q}" + (f", R = {R}: K = {wl.ctx.K}, {wl.ctx.RM} row slots" if R != 5 else ""),
+      flush=True)
 t0 = time.time()
 if dynamic:
     from manifold_mcmc_for_diffusions_amd.dynamic import sample_dynamic_chmc  # noqa: E402

@@ -43,7 +43,11 @@ typedef struct chmc_config {
   int model;                  /* CHMC_MODEL_* */
   int num_obs;                /* T = y_seq.shape[0] (dim_y = 1) */
   int num_steps_per_obs;      /* S */
-  int num_obs_per_subseq;     /* R; 0 or >= T: no partitioning (:321-324) */
+  int num_obs_per_subseq;     /* R; 0 or >= T: no partitioning (:321-324).  A block has its observation rows plus dim_x state
+                               * rows (none in the last block) and at most 16 rows, for every model: R <= 14 with noisy, 15 with
+                               * noiseless FitzHugh-Nagumo observations; R <= 13 / 14 for SIR.  chmc_create refuses more
+                               * ("... not supported").  Row slots per block (dims[8] = RM): 6, 7 or 8 for blocks of at most 8
+                               * rows, 16 for blocks of 9 to 16 rows */
   int noisy;                  /* generate_sigma (:353-358): 0 None (noiseless observations), 1 a number (`sigma`),
                                * 2 the model's generate_sigma_y(u) = exp(u[dim_z]) (fhn.py:46-47, sir.py:92-93):
                                * variable observation noise, dim_u = dim_z + 1, q = [u(dim_u) | v_0 | v_seq | n] */
@@ -187,13 +191,14 @@ int chmc_switch_partition(chmc_ctx* ctx);
 /* ---- per-op entry points, evaluated at the current state ------------------------------------------------
  * Internally the library keeps the dc/dv rows of a state in a compact factored form (per step a row-independent X x V
  * matrix, per observation interval the RM x X adjoint frame; DESIGN.md section 4 "Compact rows") and the stepping path
- * never writes the full rows of blocks with at most 8 rows.  The entry points below that return rows or multiply by them
+ * never writes the full rows of blocks with at most 8 rows (nor of few 16-row blocks per chain).  The entry points below that return rows or multiply by them
  * rebuild the row-slot array first (one extra pass, only when called); results are the same to rounding.
  *
  * Environment switches: the table of every variable the library reads, and when, is in csrc/chmc_plan.h (read_switches is
  * the one place that reads them).  Defaults are chosen from the layout (blocks per chain, block length, rows) alone, never
  * from the number of chains -- the one exception, the execution model of single-block layouts (CHMC_RETRACT_KERNEL), chooses
- * between bit-identical paths --, so a chain's results do not depend on the shard it runs in (bitwise:
+ * between bit-identical paths; the per-chain kernels it selects exist for the SIR models only, a FitzHugh-Nagumo layout with
+ * one 16-row block per chain always runs the batched launches and the switch is a no-op there --, so a chain's results do not depend on the shard it runs in (bitwise:
  * tests/test_hip_parity.py::test_results_do_not_depend_on_the_shard_size).  Pinning a switch to a non-default value changes
  * bits at the rounding level (summation order; the time-parallel scan equals the sequential recursion to about 1e-15
  * relative after its final sweep, not bitwise), never statuses. */
@@ -305,7 +310,7 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *   out80[64]      launches of the fp64-MFMA Gram kernel (v_mfma_f64_16x16x4_f64; CHMC_GRAM_MFMA=1: 16-row blocks, and blocks
  *                  of at most 8 rows on the stored-rows family)
  *   out80[65]      launches of the vector-FMA Gram kernel over stored rows (16-row blocks)
- *   out80[66]      launches of the per-chain retraction kernel (k_retract_chain: one 16-row block per chain)
+ *   out80[66]      launches of the per-chain retraction kernel (k_retract_chain: one 16-row block per chain, SIR models only)
  *   out80[67]      launches of the per-chain trajectory kernel (k_traj_chain: whole leapfrog steps of such a chain)
  *   out80[68]      launches of k_newton_fsm_wave (blocks of at most 8 rows, at most 64 blocks per chain: block LU, Woodbury
  *                  solve and mu_F of a Newton round in one launch, a wavefront per chain)

@@ -189,8 +189,13 @@ static void select_partition(chmc_ctx* c, int p) {
     if ((ctx)->sy.varsig) { /* variable observation noise: dim_u = dim_z + 1 */ \
       if ((ctx)->model == CHMC_MODEL_FHN) {       \
         using M = FhnVsModel;                     \
-        constexpr int RM = 8;                     \
-        __VA_ARGS__                               \
+        if ((ctx)->RMt == 8) {                    \
+          constexpr int RM = 8;                   \
+          __VA_ARGS__                             \
+        } else {                                  \
+          constexpr int RM = 16;                  \
+          __VA_ARGS__                             \
+        }                                         \
       } else if ((ctx)->RMt == 8) {               \
         using M = SirVsModel;                     \
         constexpr int RM = 8;                     \
@@ -208,8 +213,11 @@ static void select_partition(chmc_ctx* c, int p) {
       } else if ((ctx)->RMt == 6) {               \
         constexpr int RM = 6;                     \
         __VA_ARGS__                               \
-      } else {                                    \
+      } else if ((ctx)->RMt == 8) {               \
         constexpr int RM = 8;                     \
+        __VA_ARGS__                               \
+      } else {                                    \
+        constexpr int RM = 16;                    \
         __VA_ARGS__                               \
       }                                           \
     } else if ((ctx)->model == CHMC_MODEL_FHN_NOTEBOOK) { \
@@ -217,8 +225,11 @@ static void select_partition(chmc_ctx* c, int p) {
       if ((ctx)->RMt == 6) {                      \
         constexpr int RM = 6;                     \
         __VA_ARGS__                               \
-      } else {                                    \
+      } else if ((ctx)->RMt == 8) {               \
         constexpr int RM = 8;                     \
+        __VA_ARGS__                               \
+      } else {                                    \
+        constexpr int RM = 16;                    \
         __VA_ARGS__                               \
       }                                           \
     } else if ((ctx)->RMt == 8) {                 \
@@ -390,9 +401,9 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
     kmax = c->K[p] > kmax ? c->K[p] : kmax;
   }
   sy.NOBS = nobsmax;
-  if (rmax > 16 || (fhn && rmax > 8)) {
+  if (rmax > 16) {
     delete c;
-    return fail("chmc_create: blocks with more than 8 (FHN) / 16 (SIR) constraint rows are not supported");
+    return fail("chmc_create: blocks with more than 16 constraint rows are not supported");
   }
   c->RMt = rmax <= 8 ? 8 : 16;
   if (fhn && !sy.varsig && (rmax == 6 || (rmax == 7 && cfg->model == CHMC_MODEL_FHN))) c->RMt = rmax;  // R = 5 with noisy (7) / noiseless (6) observations (BASELINE configs 1-3, 5): exact row count, no padded slot
@@ -839,13 +850,27 @@ static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel) {
 // same segmentation, k_newton_comb_wg, k_jw_pb_wg: tests/test_hip_parity.py::test_per_chain_kernels_equal_the_batched_path_
 // bitwise), so which of the two runs is a pure scheduling decision:
 // chain_kernel_waves (chmc_plan.h).
+// The per-chain kernels are instantiated for the SIR models only: they are sized to SIR's 75 KB of LDS.  A FitzHugh-Nagumo
+// layout with one 16-row block per chain (T <= 14) always runs the batched path of the same plan, so CHMC_RETRACT_KERNEL=1/2
+// changes nothing there.
+// The gate is written twice and the two must agree: chain_kernel_model (run time, on chmc_config::model) decides whether a
+// call takes the per-chain path, kChainKernels (compile time, on the model type CHMC_DISPATCH selects for that id) decides
+// which instantiations exist.  CHMC_DISPATCH maps CHMC_MODEL_SIR to SirModel / SirVsModel and nothing else to them, and both
+// carry SirModel::ID -- held below, so a model id that drifts from its type's ID does not compile rather than launching nothing.
+static_assert(SirModel::ID == CHMC_MODEL_SIR && SirVsModel::ID == CHMC_MODEL_SIR && FhnModel::ID == CHMC_MODEL_FHN &&
+                  FhnVsModel::ID == CHMC_MODEL_FHN && FhnNbModel::ID == CHMC_MODEL_FHN_NOTEBOOK,
+              "chain_kernel_model and kChainKernels gate the per-chain kernels on the same models");
+static bool chain_kernel_model(const chmc_ctx* c) { return c->model == CHMC_MODEL_SIR; }
+template <class M, int RM>
+constexpr bool kChainKernels = RM == 16 && M::ID == CHMC_MODEL_SIR;
 static int retract_waves(const chmc_ctx* c, int newton, const void* views) {
-  return chain_kernel_waves(c->plan, part_plan(c).retract_chain, c->sy.B, c->num_cus, newton != 0, views != nullptr);
+  return chain_kernel_waves(c->plan, part_plan(c).retract_chain && chain_kernel_model(c), c->sy.B, c->num_cus, newton != 0,
+                            views != nullptr);
 }
 // ... and whole leapfrog steps -- whole trajectories -- of a chain in one launch (k_traj_chain): the same layouts with the
 // interval-parallel 16-row state evaluation, one inner h2-flow step, momenta known to be tangent, one batch.
 static int traj_waves(const chmc_ctx* c, int n_inner, int newton) {
-  const bool eligible = part_plan(c).traj_chain && n_inner == 1 && c->mom_tangent && c->halves == 1;
+  const bool eligible = part_plan(c).traj_chain && chain_kernel_model(c) && n_inner == 1 && c->mom_tangent && c->halves == 1;
   return chain_kernel_waves(c->plan, eligible, c->sy.B, c->num_cus, newton != 0, false);
 }
 static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ctol, double ptol, double dtol,
@@ -855,7 +880,7 @@ static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ct
   if (const int waves = retract_waves(c, newton, views)) {
     int* iters_dst = count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf);
     CHMC_DISPATCH(c, {
-      if constexpr (RM == 16) {
+      if constexpr (kChainKernels<M, RM>) {
         if (waves == 4)
           launch_blocks(k_retract_chain<M, RM, 4>, (long)sy.B, 256, 1, sy, c->sl, c->w, prev, qsel, ctol, ptol, dtol, max_iters,
                         iters_dst);
@@ -1818,7 +1843,7 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
     begin_all(ctx, d_dt ? ctx->w.err : nullptr, d_active ? ctx->d_act : nullptr, 1.0);
     dev_zero(ctx->d_itf, sizeof(int) * sy.B), dev_zero(ctx->d_itb, sizeof(int) * sy.B);
     CHMC_DISPATCH(ctx, {
-      if constexpr (RM == 16) {
+      if constexpr (kChainKernels<M, RM>) {
         if (waves == 4)
           launch_blocks(k_traj_chain<M, RM, 4>, (long)sy.B, 256, 1, sy, ctx->sl, ctx->w,
                         n_steps_host ? ctx->d_nsteps : nullptr, n_steps_all, ctol, ptol, dtol, max_iters, rev_tol, ctx->d_itf,

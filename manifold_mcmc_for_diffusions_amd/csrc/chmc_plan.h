@@ -34,7 +34,9 @@
 //                           the J p / J^T lambda passes (same bits)
 //   CHMC_RETRACT_KERNEL=0/1/2  one 16-row block per chain: batched launches / one workgroup of 8 wavefronts per chain / of 4
 //                           wavefronts (two chains per compute unit).  Default: 8 up to one chain per compute unit, 4 up to
-//                           four, batched beyond; all three give the same bits
+//                           four, batched beyond; all three give the same bits.  The per-chain kernels are instantiated for the
+//                           SIR models only: a FitzHugh-Nagumo layout with one 16-row block per chain always runs the batched
+//                           launches of the same plan and the switch is a no-op there (retract_waves / traj_waves, chmc_api.inc)
 //   CHMC_PAIR_RETRACT=0/1   chmc_leapfrog_steps: 0 = every retraction in a Newton loop of its own; 1 = the reverse retraction of
 //                           step i and the forward retraction of step i + 1 advance round for round in one loop with one
 //                           forward-scan launch per round for both (KernelPlan::pair_retractions).  Default: paired while the

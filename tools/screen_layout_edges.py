@@ -1,12 +1,12 @@
-"""CPU screening of the cases of tests/test_hip_layout_edges.py and tests/test_hip_multiblock16.py (a case id is looked up in
-both tables): runs the module's run_case on the TEST-ONLY emulation build with every C-oracle step traced, and reports per case
+"""CPU screening of the cases of tests/test_hip_layout_edges.py, tests/test_hip_multiblock16.py and tests/test_hip_fhn16.py (a
+case id is looked up in all three tables): runs the module's run_case on the TEST-ONLY emulation build with every C-oracle step traced, and reports per case
 whether
   * every oracle step ended with status 0, and in how many iterations,
   * any retraction residual (|c| against constraint_tol 1e-9, |dq| against position_tol 1e-8) of any iteration of any chain
     lies within 1e-2 relative of its tolerance -- the condition of test_hip_autodiff_parity.reference_side under which
     "equal iteration counts" is a fair demand on the library.
-A seed that fails is replaced in the test module and noted there.  The other bodies of the two modules that use a case
-(partition switches, masked and failing chains, trajectories) run after it, traced the same way; their chain at dt = 5.0 fails
+A seed that fails is replaced in the test module and noted there.  The other bodies of the modules that use a case
+(partition switches, masked and failing chains, trajectories, the block metric of tests/test_hip_fhn16.py) run after it, traced the same way; their chain at dt = 5.0 fails
 by design, so only the steps of run_case must all end with status 0.
 
     python tools/screen_layout_edges.py [case id | case id:seed to try ...]"""
@@ -23,7 +23,8 @@ from oracle import c_oracle  # noqa: E402
 from manifold_mcmc_for_diffusions_amd import _lib  # noqa: E402
 import test_hip_layout_edges as le  # noqa: E402
 import test_hip_multiblock16 as mb  # noqa: E402
-from helpers import make_ctx  # noqa: E402
+import test_hip_fhn16 as f16  # noqa: E402
+from helpers import make_ctx, check_block_metric_against_oracle  # noqa: E402
 
 EDGE = 1e-2
 
@@ -55,7 +56,7 @@ def main(names):
     bad = []
     for name in names:
         name, _, seed = name.partition(":")
-        mod = mb if name in mb.CASES else le
+        mod = f16 if name in f16.CASES else mb if name in mb.CASES else le
         cfg = mod.CASES[name][:12] + (int(seed) if seed else mod.CASES[name][12],)
         del log[:]
         t0 = time.time()
@@ -87,6 +88,22 @@ def main(names):
                         mb.masked_16(ctx, case, cfg, name, newton, on_device=False)  # (one chain fails by design)
             except AssertionError as e:
                 err = "other bodies: " + str(e)[:300]
+        if err is None and mod is f16:
+            try:
+                if name == "fhn16_k4_5":
+                    f16.switch_16(ctx, case, cfg, on_device=False)
+                    f16.trajectories(case, cfg)
+                    for newton in (True, False):  # (the block metric's own case: same layout, 4 chains from one point)
+                        mcase = f16.metric_case()
+                        mctx = make_ctx(mcase)
+                        check_block_metric_against_oracle(mctx, mcase, newton, le.FHN_DTS[:4])
+                        mctx.close()
+                    assert all(st == 0 for st, _, _, _ in log[n_case:])
+                if name in f16.MASKED:
+                    for newton in (True, False):
+                        f16.masked_16(ctx, case, cfg, name, newton, on_device=False)  # (one chain fails by design)
+            except AssertionError as e:
+                err = "other bodies: " + str(e)[:300]
         ctx.close()
         iters = [i for _, f, b, _ in log for i in (f, b)]
         statuses = sorted({st for st, _, _, _ in log[:n_case]})
@@ -102,4 +119,4 @@ def main(names):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1:] or list(le.CASES) + list(mb.CASES)))
+    sys.exit(main(sys.argv[1:] or list(le.CASES) + list(mb.CASES) + list(f16.CASES)))
