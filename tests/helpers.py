@@ -393,6 +393,64 @@ _SOLVER_TO_ORACLE = {"max_iters": "max_iters", "reverse_check_tol": "rev_tol", "
                      "divergence_tol": "dtol", "newton": "newton", "n_inner_step": "n_inner"}
 
 
+def oracle_static_transition(osys, q, x_obs, part, c, seed, draw, M0, dt, length, u_accept, solver=None):
+    """One transition of sampling.sample_static_chmc for ONE chain with the oracle alone: the keyed momentum of global chain
+    `c` and draw `draw` (test_hip_tree_oracle.oracle_momentum), h0, up to `length` OracleChain.step calls of step size `dt`
+    that stop at the first non-zero status, and the acceptance probability and decision as the sampler writes them: prob =
+    exp(min(0, -dh)) for a complete trajectory with a finite dh = h1 - h0, else 0; accept = u_accept < prob.  `osys` carries
+    the metric M0 (None: identity); `solver` is the sampler's dict.
+
+    Returns a dict: `q` (the end point if accepted, else the start), `q_end` (where the trajectory ended), `accepted`, `prob`,
+    `status` (0, or the failing step's code), `n_done`, `iters_fwd` / `iters_bwd` (summed over the steps, the failing one
+    included), `dh` (None unless the trajectory is complete) and `margins`, the smallest margin of every kind of decision:
+      accept                        |u_accept - prob| of a complete trajectory (a failed one is rejected whatever the draw)
+      finite_dh                     0 for a complete trajectory whose dh is not finite (never admitted), else absent
+      constraint_tol, position_tol  relative distance of every retraction residual (OracleChain.trace: every iteration of
+                                    both retractions of the last inner step of every step) from its tolerance
+      reverse_check                 relative distance of every step's reversibility error from reverse_check_tol."""
+    from oracle import c_oracle as co
+    from test_hip_tree_oracle import oracle_momentum
+    had = getattr(osys, "M0", None)
+    assert (M0 is None) == (had is None) and (M0 is None or np.array_equal(had, M0)), "osys must carry the metric M0"
+    solver = dict(solver or {})
+    okw = {_SOLVER_TO_ORACLE[k]: v for k, v in solver.items()}
+    ctol, ptol, rtol = okw.get("ctol", 1e-9), okw.get("ptol", 1e-8), okw.get("rev_tol", 2e-8)
+    margins = {}
+
+    def note(kind, v):
+        if v == v:  # (a residual that is NaN is on no side of a tolerance)
+            margins[kind] = min(margins.get(kind, np.inf), float(v))
+
+    ch = co.OracleChain(osys)
+    ch.set(q, oracle_momentum(osys, q, x_obs, part, c, seed, draw, M0), x_obs, part)
+    h0 = ch.hamiltonian()
+    status, n_done, itf, itb = 0, 0, 0, 0
+    for _ in range(int(length)):
+        status, f, b, rev = ch.step(float(dt), **okw)
+        itf, itb = itf + f, itb + b
+        for direction in (0, 1):
+            err, ndq = ch.trace(direction)
+            for e, n in zip(err, ndq):
+                note("constraint_tol", abs(e - ctol) / ctol), note("position_tol", abs(n - ptol) / ptol)
+        if status in (0, 3):
+            note("reverse_check", abs(rev - rtol) / rtol)
+        if status != 0:
+            break
+        n_done += 1
+    dh, prob = None, 0.0
+    if status == 0:
+        dh = ch.hamiltonian() - h0
+        if np.isfinite(dh):
+            prob = float(np.exp(min(0.0, -dh)))
+        else:
+            margins["finite_dh"] = 0.0
+        note("accept", abs(u_accept - prob))
+    accepted = bool(u_accept < prob)
+    q_end = ch.get()[0]
+    return dict(q=q_end if accepted else np.array(q, copy=True), q_end=q_end, accepted=accepted, prob=prob, status=status,
+                n_done=n_done, iters_fwd=itf, iters_bwd=itb, dh=dh, h0=h0, margins=margins)
+
+
 def oracle_tree_transition(osys, q, p, x_obs, part, draw, eps, depth, max_delta_h, solver=None, W=None, extra=True):
     """One dynamic (no-U-turn, multinomial) transition of ONE chain, every leaf an OracleChain.step and every Hamiltonian an
     OracleChain.hamiltonian(): tests/test_dynamic.py::_reference_transition without the library.  `draw(kind, depth, leaf)`

@@ -193,9 +193,9 @@ def surface_body():
 
 def samplers_body():
     """The static and the dynamic sampler on fhn16_k4_5's layout: a few transitions each; every chain stays on the manifold
-    and some of them move.  A SURFACE SMOKE TEST, not a parity check: it shows that nothing on the samplers' path refuses or
-    breaks on 16 row slots, and would pass with subtly wrong arithmetic -- that is judged by the oracle-compared bodies
-    (run_case, the trajectories, transitions_body / restore_body, which drive the same leapfrog_steps / tree calls)."""
+    and some of them move: nothing on the samplers' path refuses or breaks on 16 row slots.  The arithmetic of whole
+    transitions on this layout is judged against the C oracle elsewhere: the static sampler's loop (with the metric adapter)
+    by tests/test_hip_static_oracle.py's case fhn16_k4_5, the dynamic transition by transitions_body / restore_body here."""
     from manifold_mcmc_for_diffusions_amd.sampling import sample_static_chmc
     from manifold_mcmc_for_diffusions_amd.dynamic import sample_dynamic_chmc
     cfg = CASES["fhn16_k4_5"]
