@@ -235,6 +235,30 @@ int chmc_neg_log_dens_and_grad_device(chmc_ctx* ctx, const void* q_dev, int use_
 int chmc_adam_objective_device(chmc_ctx* ctx, const void* u_v_dev, void* grad_dev, double* out3);
 int chmc_adam_update_device(chmc_ctx* ctx, void* u_v_dev, void* m_dev, void* v_dev, const void* grad_dev,
                             const double* coef, double b1, double b2, double eps);
+/* Keyed normal draws on the device: the start points and restart points of the same finder (sde/mici_extensions.py:1743-1765
+ * draws them from one NumPy generator in the order the tries happen to start) as a function of (seed, stream, draw) alone.
+ * Writes n_cols standard normals into each of the n_rows listed rows of a caller-owned [B][ld] fp64 buffer: row rows[r]
+ * gets the Philox4x32-10 + Box-Muller stream of chmc_sample_momentum with counter (component pair, low word of draw[r],
+ * stream[r], high word of draw[r]) and key `seed` -- i.e. the unprojected normals the momentum refresh draws for global
+ * chain stream[r] at draw index draw[r].  rows, stream, draw [n_rows] are host arrays; rows in [0, B), none twice
+ * (n_rows = 0 is allowed); columns n_cols .. ld - 1 and unlisted rows are not touched.  A value does not depend on the row
+ * it lands in, on the other rows listed, on B or on the launch geometry.  The finder uses stream = chain_offset + chain and
+ * draw = 2^63 | try: the high bit keeps its draws disjoint from the momentum refresh, whose draw index is the transition
+ * number.  chmc_fill_normal is the host-pointer twin (dst [B][ld] on the host): the same kernel and a copy back, so a
+ * draw has one set of bits per backend. */
+int chmc_fill_normal_device(chmc_ctx* ctx, unsigned long long seed, int n_rows, const int* rows, const int* stream,
+                            const unsigned long long* draw, int n_cols, void* dst_dev, long ld);
+int chmc_fill_normal(chmc_ctx* ctx, unsigned long long seed, int n_rows, const int* rows, const int* stream,
+                     const unsigned long long* draw, int n_cols, double* dst, long ld);
+/* "Deal a try into a row" of the device-resident loop: for every listed row of u_v_dev, m_dev, v_dev, grad_dev
+ * [B][U + V0 + T S V], u_v = the keyed normals of (seed, stream[r], draw[r]) as above (replacing rng.standard_normal of
+ * :1743-1765 plus an upload), m = v = grad = 0, and the row's carried scan guess -- the work trajectory that the
+ * time-parallel scan of chmc_adam_objective_device / chmc_neg_log_dens_and_grad[_device] (layouts with T S >= 1024) would
+ * otherwise inherit from whatever was evaluated in that row before -- is reset to the cold guess (zeros) a new context
+ * starts from.  Afterwards every evaluation of the try depends on the try's own (point, previous iterate) only: its bits
+ * do not depend on the row, on the batch, or on the tries that used the row earlier. */
+int chmc_adam_begin_tries_device(chmc_ctx* ctx, unsigned long long seed, int n_rows, const int* rows, const int* stream,
+                                 const unsigned long long* draw, void* u_v_dev, void* m_dev, void* v_dev, void* grad_dev);
 
 /* Projection solvers (newton != 0: newton_projection :1065-1135 with its host wrapper :1405-1476;
  * newton == 0: quasi_newton_projection :999-1063 / :1323-1402).  Projects the points q [B][Q] onto the manifold

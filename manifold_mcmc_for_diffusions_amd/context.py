@@ -336,6 +336,39 @@ class ChmcContext:
                                              C.c_void_p(grad_dev_ptr), ptr(coef), float(b1), float(b2), float(eps)),
               "chmc_adam_update_device")
 
+    @staticmethod
+    def _row_keys(rows, stream, draw):
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        stream = np.ascontiguousarray(np.broadcast_to(np.asarray(stream, dtype=np.int32), rows.shape))
+        draw = np.ascontiguousarray(np.broadcast_to(np.asarray(draw, dtype=np.uint64), rows.shape))
+        return rows, stream, draw, draw.ctypes.data_as(C.POINTER(C.c_ulonglong))
+
+    def fill_normal_device(self, seed, rows, stream, draw, n_cols, dst_dev_ptr, ld=None):
+        """Keyed N(0, 1) draws into the listed rows of a device buffer [B, ld] (chmc_fill_normal_device, include/chmc.h):
+        row rows[r] gets n_cols values of the stream (seed, stream[r], draw[r])."""
+        rows, stream, draw, dptr = self._row_keys(rows, stream, draw)
+        check(self.L.chmc_fill_normal_device(self.h, int(seed), len(rows), iptr(rows), iptr(stream), dptr, int(n_cols),
+                                             C.c_void_p(dst_dev_ptr), int(n_cols if ld is None else ld)),
+              "chmc_fill_normal_device")
+
+    def fill_normal(self, seed, rows, stream, draw, out):
+        """The same into the listed rows of a host array `out` [B, n_cols] (or a [B, ld] array's view [:, :n_cols]), in place;
+        the same kernel, hence the same bits as fill_normal_device on this backend."""
+        if out.dtype != np.float64 or out.ndim != 2 or out.shape[0] != self.B or out.strides[1] != 8 or out.strides[0] % 8:
+            raise ValueError(f"out must be a float64 array [{self.B}, n_cols] with contiguous rows")
+        rows, stream, draw, dptr = self._row_keys(rows, stream, draw)
+        check(self.L.chmc_fill_normal(self.h, int(seed), len(rows), iptr(rows), iptr(stream), dptr, int(out.shape[1]),
+                                      out.ctypes.data_as(_lib.dp), out.strides[0] // 8), "chmc_fill_normal")
+        return out
+
+    def adam_begin_tries_device(self, seed, rows, stream, draw, u_v_dev_ptr, m_dev_ptr, v_dev_ptr, grad_dev_ptr):
+        """Deal a try into each listed row of the finder's device buffers (chmc_adam_begin_tries_device): keyed start
+        point, zero moments and gradient, the row's carried scan guess back to the cold guess."""
+        rows, stream, draw, dptr = self._row_keys(rows, stream, draw)
+        check(self.L.chmc_adam_begin_tries_device(self.h, int(seed), len(rows), iptr(rows), iptr(stream), dptr,
+                                                  C.c_void_p(u_v_dev_ptr), C.c_void_p(m_dev_ptr), C.c_void_p(v_dev_ptr),
+                                                  C.c_void_p(grad_dev_ptr)), "chmc_adam_begin_tries_device")
+
     def project(self, q, dt, newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50):
         q = self._bq(q, "q")
         dt = as_c(np.broadcast_to(np.asarray(dt, dtype=np.float64), (self.B,)))

@@ -41,6 +41,7 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   unsigned long long* d_out = nullptr;  // [rev | status | iters_fwd | iters_bwd] x B (alias_step_outputs)
   BlockDesc* d_blk_full = nullptr;       // one block spanning all observations (chmc_neg_log_dens_and_grad)
   int* d_order_ident = nullptr;          // identity work order [B] for that one-block-per-chain layout
+  unsigned long long* d_fill_keys = nullptr;  // chmc_fill_normal*: [B][2] (stream, draw) of the listed rows, then [B] ints: the rows
   bool mom_tangent = false;  // every chain's momentum is known to lie in the cotangent space of its current point
   bool snap_tangent = false; // ... at the time of chmc_snapshot
   bool have_state = false;   // a chain state has been set (chmc_set_metric then refreshes its cached factors)
@@ -455,6 +456,9 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
   h2d(c->d_y, cfg->y_seq, sizeof(double) * sy.T);
   c->npart_sum = rowsum_groups(sy.Q);
   alloc_chain_arrays(c);  // every per-chain array: chmc_layout.h
+  // the comparator target's time-parallel scan (nld_core) takes a row's work trajectory as its guess: the first call of a
+  // context sees the cold guess chmc_adam_begin_tries_device deals out (zeros), not whatever the allocation held
+  dev_zero(c->w.trajw, sizeof(double) * B * sy.TRJ);
   sy.y = c->d_y, sy.xobs = c->d_xobs;
   c->d_out = alloc<unsigned long long>(c, step_outputs_words(B));
   alias_step_outputs(*c, c->d_out, B, 0);
@@ -1704,6 +1708,91 @@ extern "C" int chmc_adam_update_device(chmc_ctx* ctx, void* u_v_dev, void* m_dev
   launch(KAdamUpdate{(double*)u_v_dev, (double*)m_dev, (double*)v_dev, (const double*)grad_dev, ctx->d_ham, n, b1, b2, eps},
          (long)sy.B * n, 8);
   CHMC_LEAVE("chmc_adam_update_device")
+}
+// Keyed normal draws (KNormalFillRows): the listed rows' (stream, draw) keys and indices go up in one copy.  Checks shared by
+// chmc_fill_normal_device, chmc_fill_normal and chmc_adam_begin_tries_device: every row in [0, B), none listed twice.
+static int upload_row_keys(chmc_ctx* ctx, const char* fn, int n_rows, const int* rows, const int* stream,
+                           const unsigned long long* draw, const int** rows_dev) {
+  const int B = ctx->sy.B;
+  if (n_rows < 0 || n_rows > B) return fail(std::string(fn) + ": n_rows out of range");
+  if (n_rows && (!rows || !stream || !draw)) return fail(std::string(fn) + ": null argument");
+  std::vector<unsigned long long> h((size_t)B * 3, 0ULL);
+  int* hr = reinterpret_cast<int*>(h.data() + (size_t)B * 2);
+  std::vector<char> seen(B, 0);
+  for (int r = 0; r < n_rows; ++r) {
+    if (rows[r] < 0 || rows[r] >= B) return fail(std::string(fn) + ": row index out of range");
+    if (seen[rows[r]]) return fail(std::string(fn) + ": a row is listed twice");
+    seen[rows[r]] = 1;
+    h[2 * r] = (unsigned long long)(unsigned)stream[r], h[2 * r + 1] = draw[r], hr[r] = rows[r];
+  }
+  if (!ctx->d_fill_keys) ctx->d_fill_keys = alloc<unsigned long long>(ctx, (size_t)B * 3);
+  if (n_rows) h2d(ctx->d_fill_keys, h.data(), sizeof(unsigned long long) * h.size());
+  *rows_dev = reinterpret_cast<const int*>(ctx->d_fill_keys + (size_t)B * 2);
+  return 0;
+}
+static int fill_rows(chmc_ctx* ctx, const char* fn, unsigned long long seed, int n_rows, const int* rows_dev, int n_cols,
+                     double* dst_dev, long long ld) {
+  const long npair = ((long)n_cols + 1) / 2;
+  if ((long)n_rows * npair > 0x7fffffffL) return fail(std::string(fn) + ": too many values for one call");
+  const int wide = ld % 2 == 0 && n_cols % 2 == 0 && (reinterpret_cast<uintptr_t>(dst_dev) & 15) == 0;
+  launch(KNormalFillRows{seed, rows_dev, ctx->d_fill_keys, n_cols, dst_dev, ld, wide}, (long)n_rows * npair, 8);
+  return 0;
+}
+extern "C" int chmc_fill_normal_device(chmc_ctx* ctx, unsigned long long seed, int n_rows, const int* rows, const int* stream,
+                                       const unsigned long long* draw, int n_cols, void* dst_dev, long ld) {
+  CHMC_ENTER("chmc_fill_normal_device")
+  if (!dst_dev) return fail("chmc_fill_normal_device: null argument");
+  if (n_cols < 0 || ld < n_cols) return fail("chmc_fill_normal_device: need 0 <= n_cols <= ld");
+  const int* rows_dev = nullptr;
+  if (upload_row_keys(ctx, "chmc_fill_normal_device", n_rows, rows, stream, draw, &rows_dev)) return -1;
+  if (fill_rows(ctx, "chmc_fill_normal_device", seed, n_rows, rows_dev, n_cols, (double*)dst_dev, ld)) return -1;
+  CHMC_LEAVE("chmc_fill_normal_device")
+}
+// host-pointer twin: the same kernel into a compact scratch [n_rows][n_cols], copied back row by row (padding and unlisted
+// rows of dst are not touched)
+extern "C" int chmc_fill_normal(chmc_ctx* ctx, unsigned long long seed, int n_rows, const int* rows, const int* stream,
+                                const unsigned long long* draw, int n_cols, double* dst, long ld) {
+  CHMC_ENTER("chmc_fill_normal")
+  if (!dst) return fail("chmc_fill_normal: null argument");
+  if (n_cols < 0 || ld < n_cols) return fail("chmc_fill_normal: need 0 <= n_cols <= ld");
+  const int* rows_dev = nullptr;
+  if (upload_row_keys(ctx, "chmc_fill_normal", n_rows, rows, stream, draw, &rows_dev)) return -1;
+  if (n_rows == 0 || n_cols == 0) return 0;
+  // (the scratch rows are 0 .. n_rows - 1: an identity row list behind the uploaded one)
+  std::vector<int> ident(n_rows);
+  for (int r = 0; r < n_rows; ++r) ident[r] = r;
+  const size_t n = (size_t)n_rows * n_cols;
+  double* scratch = (double*)dev_alloc(sizeof(double) * n + sizeof(int) * (size_t)n_rows);
+  int* ident_dev = reinterpret_cast<int*>(scratch + n);
+  h2d(ident_dev, ident.data(), sizeof(int) * (size_t)n_rows);
+  int rc = fill_rows(ctx, "chmc_fill_normal", seed, n_rows, ident_dev, n_cols, scratch, n_cols);
+  std::vector<double> h(n);
+  if (!rc) d2h(h.data(), scratch, sizeof(double) * n);
+  if (dev_sync()) rc = fail(std::string("chmc_fill_normal: ") + g_err);
+  dev_free(scratch);
+  if (rc) return -1;
+  for (int r = 0; r < n_rows; ++r) memcpy(dst + (size_t)rows[r] * (size_t)ld, h.data() + (size_t)r * n_cols, sizeof(double) * (size_t)n_cols);
+  return 0;
+}
+// "Deal a try into a row" for the device-resident finder (init.py): keyed start points, zero moments and gradient, and the
+// row's carried scan guess back to the cold guess of a new context, so that every evaluation of a try depends on that try's
+// own (point, previous iterate) only, whichever row it runs in and whatever ran there before
+extern "C" int chmc_adam_begin_tries_device(chmc_ctx* ctx, unsigned long long seed, int n_rows, const int* rows,
+                                            const int* stream, const unsigned long long* draw, void* u_v_dev, void* m_dev,
+                                            void* v_dev, void* grad_dev) {
+  CHMC_ENTER("chmc_adam_begin_tries_device")
+  const Sys& sy = ctx->sy;
+  if (!u_v_dev || !m_dev || !v_dev || !grad_dev) return fail("chmc_adam_begin_tries_device: null argument");
+  if (!sy.noisy) return fail("chmc_adam_begin_tries_device: needs observation noise");
+  const int n = sy.U + sy.NV;
+  const int* rows_dev = nullptr;
+  if (upload_row_keys(ctx, "chmc_adam_begin_tries_device", n_rows, rows, stream, draw, &rows_dev)) return -1;
+  if (fill_rows(ctx, "chmc_adam_begin_tries_device", seed, n_rows, rows_dev, n, (double*)u_v_dev, n)) return -1;
+  const long long span = (long long)sy.TRJ > n ? (long long)sy.TRJ : n;
+  if ((long long)n_rows * span > 0x7fffffffLL) return fail("chmc_adam_begin_tries_device: too many rows for one call");
+  launch(KBeginTries{rows_dev, (double*)m_dev, (double*)v_dev, (double*)grad_dev, n, ctx->w.trajw, (long long)sy.TRJ, span},
+         (long)n_rows * span, 8);
+  CHMC_LEAVE("chmc_adam_begin_tries_device")
 }
 extern "C" int chmc_hamiltonian(chmc_ctx* ctx, double* h) {
   CHMC_ENTER("chmc_hamiltonian")

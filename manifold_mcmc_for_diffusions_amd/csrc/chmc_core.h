@@ -1883,6 +1883,19 @@ CHMC_HD inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_
   }
   out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
 }
+// Normals 2 j and 2 j + 1 of the stream (seed, draw, stream word): the one place that turns a counter into a pair of N(0, 1)
+// values, shared by the momentum refresh (stream word = global chain) and by the keyed row fill below.
+CHMC_HD inline void philox_normal_pair(unsigned long long seed, unsigned long long draw, uint32_t stream, uint32_t j,
+                                       double& n0, double& n1) {
+  uint32_t r[4];
+  philox4x32_10(j, (uint32_t)draw, stream, (uint32_t)(draw >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+  const double u1 = (((uint64_t)r[0] << 21) ^ ((uint64_t)r[1] >> 11)) * (1.0 / 9007199254740992.0) +
+                    (0.5 / 9007199254740992.0);  // (0, 1)
+  const double u2 = (((uint64_t)r[2] << 21) ^ ((uint64_t)r[3] >> 11)) * (1.0 / 9007199254740992.0);
+  const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925286766559 * u2;
+  n0 = rad * cos(ang);
+  n1 = rad * sin(ang);
+}
 struct KNormalFill {  // one work item per (chain, component pair); writes N(0, 1) into the state slot's momentum
   Sys sy;
   Slots sl;
@@ -1891,16 +1904,61 @@ struct KNormalFill {  // one work item per (chain, component pair); writes N(0, 
   CHMC_HD void operator()(int tid) const {
     const int npair = (sy.Q + 1) / 2;
     const int c = tid / npair, j = tid - c * npair;
-    uint32_t r[4];
-    philox4x32_10((uint32_t)j, (uint32_t)draw, (uint32_t)(c + chain_offset), (uint32_t)(draw >> 32), (uint32_t)seed,
-                  (uint32_t)(seed >> 32), r);
-    const double u1 = (((uint64_t)r[0] << 21) ^ ((uint64_t)r[1] >> 11)) * (1.0 / 9007199254740992.0) +
-                      (0.5 / 9007199254740992.0);  // (0, 1)
-    const double u2 = (((uint64_t)r[2] << 21) ^ ((uint64_t)r[3] >> 11)) * (1.0 / 9007199254740992.0);
-    const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925286766559 * u2;
+    double n0, n1;
+    philox_normal_pair(seed, draw, (uint32_t)(c + chain_offset), (uint32_t)j, n0, n1);
     double* p = pick(sl.p, sl.cur[c]) + (size_t)c * sy.Q;
-    p[2 * j] = rad * cos(ang);
-    if (2 * j + 1 < sy.Q) p[2 * j + 1] = rad * sin(ang);
+    p[2 * j] = n0;
+    if (2 * j + 1 < sy.Q) p[2 * j + 1] = n1;
+  }
+};
+// Keyed normal draws into listed rows of a [.. ][ld] buffer (chmc_fill_normal_device; the start points of the Adam-based
+// initial-state finder, sde/mici_extensions.py:1743-1765): row rows[r] gets n_cols values of the stream (seed, draw[r],
+// stream[r]) -- the momentum generator's counter layout with `stream` in the chain word.  One work item per (listed row,
+// component pair); `wide`: ld and n_cols even and the buffer 16-byte aligned, the pair goes out as one 16-byte store.  A
+// value depends on (seed, stream, draw, component) alone: not on the row, the other rows listed, or the launch geometry.
+struct alignas(16) double2a_ {
+  double x, y;
+};
+struct KNormalFillRows {
+  unsigned long long seed;
+  const int* rows;                  // [n_rows]
+  const unsigned long long* key;    // [n_rows][2] = stream, draw
+  int n_cols;
+  double* dst;
+  long long ld;
+  int wide;
+  CHMC_HD void operator()(int tid) const {
+    const int npair = (n_cols + 1) / 2;
+    const int r = tid / npair, j = tid - r * npair;
+    double n0, n1;
+    philox_normal_pair(seed, key[2 * r + 1], (uint32_t)key[2 * r], (uint32_t)j, n0, n1);
+    double* p = dst + (size_t)rows[r] * (size_t)ld + 2 * j;
+    if (wide) {
+      double2a_ v;
+      v.x = n0, v.y = n1;
+      *reinterpret_cast<double2a_*>(p) = v;
+    } else {
+      p[0] = n0;
+      if (2 * j + 1 < n_cols) p[1] = n1;
+    }
+  }
+};
+// "Deal a try into a row" (chmc_adam_begin_tries_device): zero moments and gradient of the listed rows, and the row's work
+// trajectory -- the guess the time-parallel scan of the comparator target would otherwise inherit from whatever was
+// evaluated in that row before.  One work item per (listed row, element), the longer of the two spans.
+struct KBeginTries {
+  const int* rows;
+  double *m, *v, *g;
+  int n;         // U + NV
+  double* trajw;
+  long long TRJ;
+  long long span;  // max(n, TRJ)
+  CHMC_HD void operator()(int tid) const {
+    const int r = (int)(tid / span);
+    const long long i = tid - (long long)r * span;
+    const size_t row = (size_t)rows[r];
+    if (i < n) m[row * n + i] = 0.0, v[row * n + i] = 0.0, g[row * n + i] = 0.0;
+    if (i < TRJ) trajw[row * (size_t)TRJ + i] = 0.0;
   }
 };
 

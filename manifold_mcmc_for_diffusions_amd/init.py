@@ -100,8 +100,11 @@ def init_objective_and_grad_device(ctx, u_v_dev_ptr, grad_dev_ptr):
     return ctx.neg_log_dens_and_grad_device(u_v_dev_ptr, grad_dev_ptr, use_gaussian_splitting=False)
 
 
+KEYED_DRAW_BIT = 1 << 63  # draw index of the finder's keyed start points: 2^63 | try (the momentum refresh counts transitions)
+
+
 def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, threshold, slow_progress_ratio, check_iter,
-                    max_num_tries, log, max_parallel_tries=16, _calls=None):
+                    max_num_tries, log, max_parallel_tries=16, _calls=None, seed=None, chain_offset=0, return_status=False):
     """The finder with (u_v, m, v) and the gradient resident in HBM: per Adam iteration TWO library calls -- objective +
     gradient + row statistics (scan, adjoint sweep, one [B, 3] read-back), then the Adam step (one kernel, one [B, 2]
     upload); the [B, Q] arrays never cross PCIe.  Same restart rules as the host loop below.
@@ -112,7 +115,13 @@ def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, thresho
     with nearly every row idle.  Rows of finished chains are therefore handed to the chains still searching, which run their
     next tries k+1, k+2, ... side by side; the chain's result is still its FIRST successful try in try order (a later try
     that succeeds earlier waits, frozen, until every earlier one has failed), so each chain's answer is distributed as
-    with sequential tries, and `tries` counts as the reference does."""
+    with sequential tries, and `tries` counts as the reference does.
+
+    seed (keyed mode, `rng` None): try k of the chain in row c starts from the keyed draw (seed, stream = chain_offset + c,
+    draw = 2^63 | k) and is dealt into its row by ONE library call (chmc_adam_begin_tries_device: start point, zero moments
+    and gradient, the row's carried scan guess back to the cold guess) instead of rng.standard_normal + an upload + index
+    assignments.  A try then depends on its own (chain, try number) only -- not on the row it runs in, on what ran there
+    before, or on when it was started -- so the winners do not depend on the slot schedule (see the public function)."""
     import torch
     if _calls is None:                                     # the two library calls of an iteration, on device pointers
         dev = _torch_device(ctx)
@@ -120,13 +129,20 @@ def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, thresho
         objective = lambda u_v, g: ctx.adam_objective_device(u_v.data_ptr(), g.data_ptr())
         adam_update = lambda u_v, m, v, g, coef, b1, b2, eps: ctx.adam_update_device(
             u_v.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), coef, b1, b2, eps)
+        begin_tries = lambda rows, stream, draw, u_v, m, v, g: ctx.adam_begin_tries_device(
+            seed, rows, stream, draw, u_v.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr())
     else:                                                  # (CPU test of the slot bookkeeping: stand-ins on CPU tensors)
-        dev, sync, objective, adam_update = _calls
+        dev, sync, objective, adam_update = _calls[:4]
+        begin_tries = _calls[4] if len(_calls) > 4 else None
+    keyed = seed is not None
     B, Q, T = ctx.B, ctx.Q, ctx.T
     nuv = Q - T
     var_sigma = getattr(ctx, "variable_sigma", False)
     isig = ctx.U - 1                                       # index of log sigma in u (variable observation noise)
-    u_v = torch.from_numpy(rng.standard_normal((B, nuv))).to(dev)
+    if keyed:
+        u_v = torch.zeros((B, nuv), dtype=torch.float64, device=dev)
+    else:
+        u_v = torch.from_numpy(rng.standard_normal((B, nuv))).to(dev)
     m, v, g = torch.zeros_like(u_v), torch.zeros_like(u_v), torch.empty_like(u_v)
     t_adam = np.zeros(B)
     prev = np.full(B, np.inf)
@@ -147,6 +163,8 @@ def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, thresho
     if dev.type == "cuda":
         ls_host = ls_host.pin_memory()
     sync()                                                 # (the draws are on the device before the library reads them)
+    if keyed:                                              # try 0 of every chain, dealt into the chain's own row
+        begin_tries(np.arange(B), chain_offset + np.arange(B), np.full(B, KEYED_DRAW_BIT, dtype=np.uint64), u_v, m, v, g)
 
     def release(c, s):
         if slot_state[s] == 0:
@@ -228,14 +246,19 @@ def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, thresho
         if len(idle):                                      # a slot left idle holds a harmless point (a failed try may be NaN)
             idx = torch.from_numpy(np.asarray(idle)).to(dev)
             u_v[idx], m[idx], v[idx], g[idx] = 0.0, 0.0, 0.0, 0.0
-        if fresh:
+        if fresh and keyed:
+            fr = np.asarray(fresh)
+            sync()                                         # (a winner's point has left the row before the row is dealt out again)
+            begin_tries(fr, chain_offset + owner[fr], np.uint64(KEYED_DRAW_BIT) | tryno[fr].astype(np.uint64), u_v, m, v, g)
+            t_adam[fr], it_in_try[fr], prev[fr] = 0.0, 0, np.inf
+        elif fresh:
             fr = np.asarray(fresh)
             idx = torch.from_numpy(fr).to(dev)
             u_v[idx] = torch.from_numpy(rng.standard_normal((len(fresh), nuv))).to(dev)
             m[idx], v[idx] = 0.0, 0.0
             g[idx] = 0.0                                   # (a fresh try's moments start from zero at its next gradient)
             t_adam[fr], it_in_try[fr], prev[fr] = 0.0, 0, np.inf
-        if fresh or len(idle):
+        if (fresh and not keyed) or len(idle):
             sync()
         step = slot_state == 0
         if fresh:
@@ -268,12 +291,14 @@ def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, thresho
     ctx.update_x_obs_seq()
     xo = ctx.get_state(want_p=False)[2]
     ctx.set_state(q, None, xo, 0)
-    return q, xo, tries
+    return (q, xo, tries, status) if return_status else (q, xo, tries)
 
 
-def find_initial_states_by_gradient_descent_noisy_system(ctx, rng, adam_step_size=2e-2, max_iters=1000, max_init_tries=100,
+def find_initial_states_by_gradient_descent_noisy_system(ctx, rng=None, adam_step_size=2e-2, max_iters=1000, max_init_tries=100,
                                                          threshold=1.0, slow_progress_ratio=0.8, check_iter=100,
-                                                         max_num_tries=10, log=None, device_resident=None):
+                                                         max_num_tries=10, log=None, device_resident=None, seed=None,
+                                                         chain_offset=0, total_chains=None, max_parallel_tries=16,
+                                                         return_status=False):
     """find_initial_state_by_gradient_descent_noisy_system (sde/mici_extensions.py:1679-1801), for every chain of `ctx`
     at once (the SIR script's initialisation, scripts/sir_model_chmc_experiment.py:103-109).
 
@@ -290,7 +315,28 @@ def find_initial_states_by_gradient_descent_noisy_system(ctx, rng, adam_step_siz
     device_resident (None: when possible): the iteration runs with (u_v, m, v) resident in HBM and the objective / gradient
     from the library's scan + single adjoint sweep (`_adam_on_device`), for a fixed observation noise and for
     sigma = generate_σ_y(u) alike (round 4; the gradient's u[dim_z] component is T - sum r^2 + u[dim_z]); the host loop below
-    (full state evaluation per iteration through the per-operator entry points) is the independent second implementation."""
+    (full state evaluation per iteration through the per-operator entry points) is the independent second implementation.
+
+    Exactly one of `rng` and `seed` is given.  With `rng` (a NumPy generator) the start points and restart points are drawn
+    from it in the order the tries happen to start (:1743-1765), so they depend on the batch.  With `seed` (keyed mode) the
+    start point of try k of chain c is the keyed draw (seed, stream = chain_offset + c, draw = 2^63 | k) of the library's
+    counter-based generator (chmc_fill_normal / chmc_adam_begin_tries_device; the high bit keeps the draws disjoint from the
+    momentum refresh, whose draw index is the transition number): chain c of ANY sharding of `total_chains` chains over
+    contexts (chain_offset = the shard's first global chain) gets the same states, bit for bit, within one backend.  The
+    slot scheduler of the device-resident loop is the same in both modes -- rows of finished chains run later tries side by
+    side, the first successful try in try order wins; the keyed mode is what makes its outcome independent of the schedule,
+    because a try then depends on its own (chain, try number) and nothing else (not the row, not the tries that used the
+    row before, not `max_parallel_tries`).  Two places remain where the schedule can show, both failure paths that raise:
+    the global iteration budget (max_iters * max_num_tries iterations for the whole batch: how many tries fit depends on
+    how many rows become free) and the `limit` on tries (max_num_tries * max_init_tries per chain, with tries beyond the
+    winner started speculatively).  return_status: the device-resident loop also returns its per-chain {try: row or -1}
+    maps."""
+    if (rng is None) == (seed is None):
+        raise ValueError("give exactly one of rng (legacy draws) and seed (keyed draws)")
+    if seed is not None:
+        total = ctx.B + chain_offset if total_chains is None else total_chains
+        if chain_offset < 0 or chain_offset + ctx.B > total:
+            raise ValueError("chain_offset + the context's chains exceed total_chains")
     if not ctx.noisy or ctx.num_blocks != 1 or ctx.num_partition != 1:
         raise ValueError("needs a noisy-observation context with a single sub-sequence (num_obs_per_subseq >= num_obs)")
     B, Q, T = ctx.B, ctx.Q, ctx.T
@@ -298,7 +344,8 @@ def find_initial_states_by_gradient_descent_noisy_system(ctx, rng, adam_step_siz
     var_sigma = getattr(ctx, "variable_sigma", False)
     if device_resident is not False and _torch_device(ctx) is not None:
         return _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, threshold, slow_progress_ratio, check_iter,
-                               max_num_tries, log)
+                               max_num_tries, log, max_parallel_tries=max_parallel_tries, seed=seed, chain_offset=chain_offset,
+                               return_status=return_status)
     if device_resident is True:
         raise ValueError("the device-resident finder needs a CUDA-capable torch")
     iσ = ctx.U - 1                                         # index of log sigma in u (variable observation noise)
@@ -314,7 +361,11 @@ def find_initial_states_by_gradient_descent_noisy_system(ctx, rng, adam_step_siz
             g[:, iσ] += T - np.sum((c / sigma) ** 2, 1)
         return -c / sigma, g
 
-    u_v = rng.standard_normal((B, nuv))
+    streams = chain_offset + np.arange(B)
+    if seed is None:
+        u_v = rng.standard_normal((B, nuv))
+    else:                                                  # try 0 of every chain
+        u_v = ctx.fill_normal(seed, np.arange(B), streams, KEYED_DRAW_BIT, np.zeros((B, nuv)))
     m, v = np.zeros_like(u_v), np.zeros_like(u_v)
     t_adam = np.zeros(B)
     done = np.zeros(B, dtype=bool)
@@ -340,7 +391,11 @@ def find_initial_states_by_gradient_descent_noisy_system(ctx, rng, adam_step_siz
             if (tries[restart] >= max_num_tries * max_init_tries).any():
                 raise RuntimeError(f"Did not find valid state in {max_num_tries} tries.")
             n = int(restart.sum())
-            u_v[restart] = rng.standard_normal((n, nuv))
+            if seed is None:
+                u_v[restart] = rng.standard_normal((n, nuv))
+            else:                                          # (tries counts from 1: the new try's number is the old count)
+                rr = np.flatnonzero(restart)
+                ctx.fill_normal(seed, rr, streams[rr], np.uint64(KEYED_DRAW_BIT) | tries[rr].astype(np.uint64), u_v)
             m[restart], v[restart], t_adam[restart], it_in_try[restart], prev[restart] = 0.0, 0.0, 0.0, 0, np.inf
             tries[restart] += 1
         step = ~done & ~restart
@@ -360,4 +415,4 @@ def find_initial_states_by_gradient_descent_noisy_system(ctx, rng, adam_step_siz
     ctx.update_x_obs_seq()
     xo = ctx.get_state(want_p=False)[2]
     ctx.set_state(q, None, xo, 0)
-    return q, xo, tries
+    return (q, xo, tries, None) if return_status else (q, xo, tries)

@@ -80,10 +80,12 @@ class SirWorkload(FhnWorkload):
     """SIR chains on the boarding-school data as scripts/sir_model_chmc_experiment.py sets them up (BASELINE.json
     configs[3]): 14 daily counts, S steps per observation, ONE sub-sequence of R = 14 observations (dense 14 x 14 Gram
     block), sigma_y = 1, initial states by the Adam-based finder of the noisy system (sde/mici_extensions.py:1679-1801)
-    with one generator for the whole batch (the finder restarts chains, so draws are not chain-indexed)."""
+    with one generator for the whole batch (the finder restarts chains, so draws are not chain-indexed) -- or, with
+    keyed_init, from draws keyed by (seed, global chain, try): chain c of `total_chains` then starts from the same state
+    whichever shard [chain_offset, chain_offset + num_chains) it runs in."""
 
     def __init__(self, num_chains, num_steps_per_obs=200, sigma=1.0, device=0, chain_offset=0, total_chains=None,
-                 use_gaussian_splitting=False, seed=SEED, adam_step_size=1e-1, log=None):
+                 use_gaussian_splitting=False, seed=SEED, adam_step_size=1e-1, log=None, keyed_init=False):
         from . import init
         self.B, self.S, self.T, self.R = num_chains, num_steps_per_obs, len(BOARDING_SCHOOL_COUNTS), len(BOARDING_SCHOOL_COUNTS)
         self.sigma, self.obs_interval = sigma, 1.0
@@ -92,8 +94,13 @@ class SirWorkload(FhnWorkload):
         self.ctx = ChmcContext("sir", self.obs_interval, num_steps_per_obs, self.R, self.y[:, 0], sigma=sigma,
                                use_gaussian_splitting=use_gaussian_splitting, num_chains=num_chains, device=device)
         rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(chain_offset + 1)[chain_offset])
-        _, _, self.init_tries = init.find_initial_states_by_gradient_descent_noisy_system(
-            self.ctx, rng, adam_step_size=adam_step_size, max_iters=5000, log=log)
+        if keyed_init:
+            _, _, self.init_tries = init.find_initial_states_by_gradient_descent_noisy_system(
+                self.ctx, seed=seed, chain_offset=chain_offset, total_chains=total_chains, adam_step_size=adam_step_size,
+                max_iters=5000, log=log)
+        else:
+            _, _, self.init_tries = init.find_initial_states_by_gradient_descent_noisy_system(
+                self.ctx, rng, adam_step_size=adam_step_size, max_iters=5000, log=log)
         self.rngs = [rng]
         self.solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
                            reverse_check_tol=2e-8)

@@ -1,10 +1,42 @@
-"""Host (NumPy) against device initial-state generation for the bench workload.  usage: python tools/init_timing.py [chains]"""
+"""Wall time of initial-state generation.
+usage: python tools/init_timing.py [chains]                            FitzHugh-Nagumo bench workload: host (NumPy) against device
+       python tools/init_timing.py sir [chains] [legacy|keyed] [sigma]  boarding-school SIR (S = 200): the Adam-based finder, device
+                                                                       loop, draws from one generator (legacy) or keyed by
+                                                                       (seed, chain, try); sigma: a number or "variable"
+The SIR mode prints one line per run: two runs on fresh contexts in one process, the second is the figure to quote (the first
+pays for the process's HIP and torch start-up)."""
 import sys, os, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 from manifold_mcmc_for_diffusions_amd import example_models as em
 from manifold_mcmc_for_diffusions_amd.context import ChmcContext
 from manifold_mcmc_for_diffusions_amd import init
+
+
+def sir(B, mode, sigma):
+    from manifold_mcmc_for_diffusions_amd.workload import BOARDING_SCHOOL_COUNTS, SEED
+    y = np.asarray(BOARDING_SCHOOL_COUNTS, dtype=np.float64)
+    for run in range(2):
+        ctx = ChmcContext("sir", 1.0, 200, len(y), y, sigma=sigma, num_chains=B)
+        t0 = time.perf_counter()
+        if mode == "keyed":
+            _, _, tries = init.find_initial_states_by_gradient_descent_noisy_system(
+                ctx, seed=SEED, adam_step_size=0.1, max_iters=5000, device_resident=True)
+        else:
+            _, _, tries = init.find_initial_states_by_gradient_descent_noisy_system(
+                ctx, np.random.default_rng(SEED), adam_step_size=0.1, max_iters=5000, device_resident=True)
+        dt = time.perf_counter() - t0
+        print(f"sir {B} chains sigma={sigma} {mode} run {run}: {dt:.3f} s; tries max {int(tries.max())} mean {tries.mean():.3f}",
+              flush=True)
+        ctx.close()
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "sir":
+    B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
+    mode = sys.argv[3] if len(sys.argv) > 3 else "legacy"
+    sigma = sys.argv[4] if len(sys.argv) > 4 else "1.0"
+    sir(B, mode, sigma if sigma == "variable" else float(sigma))
+    sys.exit(0)
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 y = em.simulate_fhn_observations(100, 0.2, 10000, seed=20200710, sigma=0.1)
