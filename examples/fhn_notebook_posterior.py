@@ -10,7 +10,12 @@ static-trajectory sampler is used (a different Markov kernel for the same poster
 With `dynamic` as sixth argument the batched dynamic (no-U-turn, multinomial) transition of dynamic.py is used, the
 counterpart of the notebook's own transition.
 
-usage: fhn_notebook_posterior.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir] [static|dynamic]"""
+With `--init gradient-descent` the initial states come from the reference's generic finder
+(find_initial_state_by_gradient_descent; init.find_initial_states_by_gradient_descent, batched on the device) instead of
+the notebook's linear interpolation; candidates are screened in the same way.
+
+usage: fhn_notebook_posterior.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir] [static|dynamic]
+                                 [--init linear-interpolation|gradient-descent]"""
 import json
 import os
 import sys
@@ -39,7 +44,9 @@ def notebook_data():
 
 
 def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=20200710, verbose=True,
-        transition="static"):
+        transition="static", init="linear-interpolation"):
+    if init not in ("linear-interpolation", "gradient-descent"):
+        raise ValueError("init must be linear-interpolation or gradient-descent")
     d = notebook_data()
     m = em.fhn_nb
     rng = np.random.default_rng(seed)
@@ -58,8 +65,17 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
     # state is useless as a start, for the reference as much as here (it has no check; its two chains happened to be
     # fine).  Candidates are screened on the device and the first `num_chains` usable ones are kept.
     cand = context(3 * num_chains)
-    u, v_0, x_obs_init = draws(3 * num_chains)
-    cand.init_by_linear_interpolation(u, v_0, x_obs_init)
+    if init == "gradient-descent":
+        from manifold_mcmc_for_diffusions_amd.init import find_initial_states_by_gradient_descent, fhn_x_obs_seq_init
+        t_init = time.time()
+        q_init, x_obs_init, tries = find_initial_states_by_gradient_descent(
+            cand, fhn_x_obs_seq_init(d["y"], seed), seed, log=print if verbose else None)
+        if verbose:
+            print(f"gradient-descent initial states: {3 * num_chains} chains in {time.time() - t_init:.1f} s, "
+                  f"tries per chain max {tries.max()}, mean {tries.mean():.2f}")
+    else:
+        u, v_0, x_obs_init = draws(3 * num_chains)
+        cand.init_by_linear_interpolation(u, v_0, x_obs_init)
     usable = np.isfinite(cand.hamiltonian()[:, 0]) & (np.abs(cand.constr()).max(1) < 1e-8)
     # ... and a short pilot run weeds out the starts from which no trajectory is ever accepted (Gram matrix so
     # ill-conditioned that the energy is noise): a chain that has not moved in 20 short transitions never will
@@ -71,7 +87,10 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
         print(f"initial states: {usable.sum()} of {usable.size} prior draws usable, keeping {keep.size}")
     assert keep.size == num_chains, "not enough usable initial states"
     ctx = context(num_chains)
-    ctx.init_by_linear_interpolation(u[keep], v_0[keep], x_obs_init[keep])
+    if init == "gradient-descent":
+        ctx.set_state(q_init[keep], None, x_obs_init[keep], 0)
+    else:
+        ctx.init_by_linear_interpolation(u[keep], v_0[keep], x_obs_init[keep])
 
     def trace_func(head, ham):  # cell 41
         z = m.generate_z(head[:, :4])
@@ -161,5 +180,10 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    run(*(int(x) for x in a[:4]), out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
+    init = "linear-interpolation"
+    if "--init" in a:
+        i = a.index("--init")
+        init = a[i + 1]
+        del a[i:i + 2]
+    run(*(int(x) for x in a[:4]), init=init, out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
         transition=a[5] if len(a) > 5 else "static")

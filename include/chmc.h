@@ -259,6 +259,35 @@ int chmc_fill_normal(chmc_ctx* ctx, unsigned long long seed, int n_rows, const i
  * do not depend on the row, on the batch, or on the tries that used the row earlier. */
 int chmc_adam_begin_tries_device(chmc_ctx* ctx, unsigned long long seed, int n_rows, const int* rows, const int* stream,
                                  const unsigned long long* draw, void* u_v_dev, void* m_dev, void* v_dev, void* grad_dev);
+/* The device-resident loop of find_initial_state_by_gradient_descent (sde/mici_extensions.py:1550-1676), the generic finder:
+ * any partition, noisy or noiseless observations, every model.  One Adam iteration is chmc_gd_objective_device +
+ * chmc_adam_update_cols_device; a try that gets within coarse_tol calls chmc_gd_project_device.
+ * chmc_gd_objective_device: init_objective (:1582-1618) and its gradient with respect to ALL of q at q_dev [B][Q], given
+ *   x_obs_seq_init in xo_dev [B][T][X]:
+ *     c[t] = x_S(z(u), v_subseq[t]; start x_init[t]) - xo[t],  x_init[0] = generate_x_0(z, v_0), x_init[t] = xo[t - 1] (a constant),
+ *     objective = 1/2 mean(c^2) + 1/2 reg_coeff mean(q^2)      (means over the T X entries of c and the Q entries of q);
+ *   the observation-noise part n and a variable-sigma u[Z] only receive the regulariser's reg_coeff q / Q.  Gradient into
+ *   grad_dev [B][Q]; in one read-back out3 [B][3] = objective, max |c|, 1 if the objective and every gradient entry are
+ *   finite (else 0).  The T intervals of a chain are independent scans: a work item per (chain, interval), the intervals'
+ *   sums added in interval order (no atomics), so a row's results depend on the row's own (q, xo) only -- not on B, the row
+ *   index or the other rows.  Works in a noiseless context (unlike chmc_adam_objective_device); does not touch the chain
+ *   states.
+ * chmc_adam_update_cols_device: chmc_adam_update_device (:1625, jax.example_libraries.optimizers.adam) on buffers of
+ *   [B][n_cols] (this finder: n_cols = Q); same kernel, same coef [B][2].
+ * chmc_gd_project_device: the projection of :1654-1669 for the chains with mask[c] != 0.  The chain's state becomes
+ *   (pos = row c of q_dev, mom = 0, x_obs_seq = row c of xo_dev, partition 0) with the state caches evaluated, and that
+ *   position is projected from that state (state_prev = state) with dt = 1 by the solver chmc_project runs (newton,
+ *   tolerances and max_iters as there).  On convergence the projected point is written back into row c of q_dev and becomes
+ *   the chain's state (caches re-evaluated); otherwise row c of q_dev is left alone (the chain's state stays the one
+ *   projected from).  Chains with mask[c] == 0 keep their state and their row.  status [B]: chmc_project's codes (-1 for
+ *   unmasked chains); iters, err [B] (0 for unmasked chains); any of the three may be NULL.  The context must hold a state
+ *   in partition 0 in every row before the first call (chmc_set_state; a state at u = 0 is finite for every model). */
+int chmc_gd_objective_device(chmc_ctx* ctx, const void* q_dev, const void* xo_dev, double reg_coeff, void* grad_dev,
+                             double* out3);
+int chmc_adam_update_cols_device(chmc_ctx* ctx, int n_cols, void* x_dev, void* m_dev, void* v_dev, const void* grad_dev,
+                                 const double* coef, double b1, double b2, double eps);
+int chmc_gd_project_device(chmc_ctx* ctx, const int* mask, void* q_dev, const void* xo_dev, int newton, double constraint_tol,
+                           double position_tol, double divergence_tol, int max_iters, int* status, int* iters, double* err);
 
 /* Projection solvers (newton != 0: newton_projection :1065-1135 with its host wrapper :1405-1476;
  * newton == 0: quasi_newton_projection :999-1063 / :1323-1402).  Projects the points q [B][Q] onto the manifold

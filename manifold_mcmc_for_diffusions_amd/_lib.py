@@ -82,6 +82,11 @@ SYMBOLS = [
                                    C.c_long]),
     ("chmc_adam_begin_tries_device", C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, ip, ip, C.POINTER(C.c_ulonglong),
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chmc_gd_objective_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, dp]),
+    ("chmc_adam_update_cols_device", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, dp,
+                                               C.c_double, C.c_double, C.c_double]),
+    ("chmc_gd_project_device", C.c_int, [C.c_void_p, ip, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                         C.c_double, C.c_int, ip, ip, dp]),
     ("chmc_hamiltonian", C.c_int, [C.c_void_p, dp]),
     ("chmc_project", C.c_int, [C.c_void_p, C.c_int, dp, dp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, ip,
                                dp, dp, ip]),

@@ -369,6 +369,33 @@ class ChmcContext:
                                                   C.c_void_p(u_v_dev_ptr), C.c_void_p(m_dev_ptr), C.c_void_p(v_dev_ptr),
                                                   C.c_void_p(grad_dev_ptr)), "chmc_adam_begin_tries_device")
 
+    def gd_objective_device(self, q_dev_ptr, xo_dev_ptr, reg_coeff, grad_dev_ptr):
+        """Objective and gradient of the generic gradient-descent finder on device buffers q [B, Q], x_obs_seq_init
+        [B, T, X] (chmc_gd_objective_device): returns [B, 3] = objective, max |c|, objective and gradient finite."""
+        out = np.empty((self.B, 3))
+        check(self.L.chmc_gd_objective_device(self.h, C.c_void_p(q_dev_ptr), C.c_void_p(xo_dev_ptr), float(reg_coeff),
+                                              C.c_void_p(grad_dev_ptr), ptr(out)), "chmc_gd_objective_device")
+        return out
+
+    def adam_update_cols_device(self, n_cols, x_dev_ptr, m_dev_ptr, v_dev_ptr, grad_dev_ptr, coef, b1=0.9, b2=0.999, eps=1e-8):
+        """adam_update_device on buffers of [B, n_cols]."""
+        coef = as_c(np.asarray(coef, dtype=np.float64).reshape(self.B, 2))
+        check(self.L.chmc_adam_update_cols_device(self.h, int(n_cols), C.c_void_p(x_dev_ptr), C.c_void_p(m_dev_ptr),
+                                                  C.c_void_p(v_dev_ptr), C.c_void_p(grad_dev_ptr), ptr(coef), float(b1),
+                                                  float(b2), float(eps)), "chmc_adam_update_cols_device")
+
+    def gd_project_device(self, mask, q_dev_ptr, xo_dev_ptr, newton=True, constraint_tol=1e-9, position_tol=1e-8,
+                          divergence_tol=1e10, max_iters=50):
+        """Masked rows of q [B, Q] / x_obs_seq_init [B, T, X] (device) become the chains' states in partition 0 and are
+        projected from there with dt = 1; converged points replace row and state (chmc_gd_project_device)."""
+        m = np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        status, iters, err = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32), np.zeros(self.B)
+        check(self.L.chmc_gd_project_device(self.h, iptr(m), C.c_void_p(q_dev_ptr), C.c_void_p(xo_dev_ptr), int(newton),
+                                            constraint_tol, position_tol, divergence_tol, int(max_iters), iptr(status),
+                                            iptr(iters), ptr(err)), "chmc_gd_project_device")
+        self.partition = 0
+        return dict(status=status, iters=iters, err=err)
+
     def project(self, q, dt, newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50):
         q = self._bq(q, "q")
         dt = as_c(np.broadcast_to(np.asarray(dt, dtype=np.float64), (self.B,)))

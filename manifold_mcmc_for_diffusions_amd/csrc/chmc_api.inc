@@ -42,6 +42,7 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   BlockDesc* d_blk_full = nullptr;       // one block spanning all observations (chmc_neg_log_dens_and_grad)
   int* d_order_ident = nullptr;          // identity work order [B] for that one-block-per-chain layout
   unsigned long long* d_fill_keys = nullptr;  // chmc_fill_normal*: [B][2] (stream, draw) of the listed rows, then [B] ints: the rows
+  double* d_gd = nullptr;  // chmc_gd_objective_device: [B][T][X] c, [B][T][Z + 2] interval partials, [B][2] chain sums (whole-batch launches only)
   bool mom_tangent = false;  // every chain's momentum is known to lie in the cotangent space of its current point
   bool snap_tangent = false; // ... at the time of chmc_snapshot
   bool have_state = false;   // a chain state has been set (chmc_set_metric then refreshes its cached factors)
@@ -1794,6 +1795,48 @@ extern "C" int chmc_adam_begin_tries_device(chmc_ctx* ctx, unsigned long long se
          (long)n_rows * span, 8);
   CHMC_LEAVE("chmc_adam_begin_tries_device")
 }
+// find_initial_state_by_gradient_descent (sde/mici_extensions.py:1550-1676), device-resident loop (init.py): objective,
+// gradient with respect to ALL of q and the row statistics of its try rules in one call and one read-back of [B][3].
+// Forward half KGdFwd, backward half k_gd_grad_wave (HIP) / KGdGrad (host emulation), chain level KGdReduce.
+extern "C" int chmc_gd_objective_device(chmc_ctx* ctx, const void* q_dev, const void* xo_dev, double reg_coeff, void* grad_dev,
+                                        double* out3) {
+  CHMC_ENTER("chmc_gd_objective_device")
+  const Sys& sy = ctx->sy;
+  if (!q_dev || !xo_dev || !grad_dev || !out3) return fail("chmc_gd_objective_device: null argument");
+  const long long tasks = (long long)sy.B * sy.T;
+  if (tasks > 0x7fffffffLL) return fail("chmc_gd_objective_device: too many (chain, interval) tasks for one call");
+  const size_t ncres = (size_t)tasks * sy.X;
+  if (!ctx->d_gd) ctx->d_gd = alloc<double>(ctx, ncres + (size_t)tasks * CHMC_GD_NPART(sy.Z) + (size_t)sy.B * 2);
+  const double *q = (const double*)q_dev, *xo = (const double*)xo_dev;
+  double *g = (double*)grad_dev, *cres = ctx->d_gd, *part = ctx->d_gd + ncres;
+  double* stat = part + (size_t)tasks * CHMC_GD_NPART(sy.Z);  // [B][2] = 1/2 mean(c^2), max |c|
+  CHMC_DISPATCH(ctx, {
+    (void)RM;
+    launch(KGdFwd<M>{sy, q, xo, ctx->w.trajw, cres}, (long)tasks, 7);
+#ifdef CHMC_WAVE_KERNELS
+    launch_wave(k_gd_grad_wave<M>, (long)tasks, 0, sy, q, (const double*)ctx->w.trajw, (const double*)cres, reg_coeff, g, part);
+#else
+    launch(KGdGrad<M>{sy, q, ctx->w.trajw, cres, reg_coeff, g, part}, (long)tasks);
+#endif
+    launch(KGdReduce<M>{sy, q, part, reg_coeff, g, stat}, sy.B);
+  });
+  launch_rowsum(KAdamRow{q, g, sy.Q}, sy.Q, sy.B, 2, ctx->w.part, 8);
+  launch(KGdStats{ctx->w.part, stat, rowsum_groups(sy.Q), sy.Q, reg_coeff, ctx->d_ham}, sy.B);
+  d2h(out3, ctx->d_ham, sizeof(double) * (size_t)sy.B * 3);
+  CHMC_LEAVE("chmc_gd_objective_device")
+}
+// chmc_adam_update_device over an explicit number of columns (the same kernel): that finder's parameters are all of q
+extern "C" int chmc_adam_update_cols_device(chmc_ctx* ctx, int n_cols, void* x_dev, void* m_dev, void* v_dev,
+                                            const void* grad_dev, const double* coef, double b1, double b2, double eps) {
+  CHMC_ENTER("chmc_adam_update_cols_device")
+  const Sys& sy = ctx->sy;
+  if (!x_dev || !m_dev || !v_dev || !grad_dev || !coef) return fail("chmc_adam_update_cols_device: null argument");
+  if (n_cols < 0 || (long long)sy.B * n_cols > 0x7fffffffLL) return fail("chmc_adam_update_cols_device: n_cols out of range");
+  h2d(ctx->d_ham, coef, sizeof(double) * (size_t)sy.B * 2);
+  launch(KAdamUpdate{(double*)x_dev, (double*)m_dev, (double*)v_dev, (const double*)grad_dev, ctx->d_ham, n_cols, b1, b2, eps},
+         (long)sy.B * n_cols, 8);
+  CHMC_LEAVE("chmc_adam_update_cols_device")
+}
 extern "C" int chmc_hamiltonian(chmc_ctx* ctx, double* h) {
   CHMC_ENTER("chmc_hamiltonian")
   if (!h) return fail("chmc_hamiltonian: null output");
@@ -1868,6 +1911,48 @@ extern "C" int chmc_project(chmc_ctx* ctx, int newton, const double* q, const do
   if (norm_dq) d2h(norm_dq, ctx->w.ndq, sizeof(double) * sy.B);
   if (status) d2h(status, ctx->w.nstat, sizeof(int) * sy.B);
   CHMC_LEAVE("chmc_project")
+}
+
+// The projection step of find_initial_state_by_gradient_descent (:1654-1669) on the caller's device rows: the masked chains'
+// states become (q_dev row, zero momentum, xo_dev row, partition 0), the position is projected from that state with dt = 1
+// by the solver of chmc_project, and a converged point replaces both the row and the state.
+extern "C" int chmc_gd_project_device(chmc_ctx* ctx, const int* mask, void* q_dev, const void* xo_dev, int newton, double ctol,
+                                      double ptol, double dtol, int max_iters, int* status, int* iters, double* err) {
+  CHMC_ENTER("chmc_gd_project_device")
+  if (!mask || !q_dev || !xo_dev) return fail("chmc_gd_project_device: mask, q_dev and xo_dev are required");
+  if (max_iters < 0) return fail("chmc_gd_project_device: max_iters < 0");
+  if (!ctx->have_state || ctx->part != 0)
+    return fail("chmc_gd_project_device: the context must hold a state in partition 0 in every row");
+  const Sys& sy = ctx->sy;
+  h2d(ctx->d_act, mask, sizeof(int) * sy.B);
+  ctx->last_active_null = true;
+  ctx->last_active.clear();
+  launch(KGdSetRows{sy, ctx->sl, (const double*)q_dev, (const double*)xo_dev, ctx->d_xobs, ctx->d_act}, (long)sy.B * sy.Q, 8);
+  begin_all(ctx, nullptr, ctx->d_act);  // the state caches of the masked chains only
+  state_eval(ctx, 0);
+  const std::vector<double> ones(sy.B, 1.0);
+  h2d(ctx->w.err, ones.data(), sizeof(double) * sy.B);  // staging for dt
+  ctx->last_dt.clear();                                 // the step-size cache of chmc_leapfrog_step is now stale
+  begin_all(ctx, ctx->w.err, ctx->d_act);
+  launch(KCopyToOther{sy, ctx->sl, (const double*)q_dev}, (long)sy.B * sy.Q);
+  run_projection(ctx, newton, 0, 0, ctol, ptol, dtol, max_iters);
+  std::vector<int> st(sy.B);
+  d2h(st.data(), ctx->w.nstat, sizeof(int) * sy.B);
+  if (iters) d2h(iters, ctx->w.iters, sizeof(int) * sy.B);
+  if (err) d2h(err, ctx->w.err, sizeof(double) * sy.B);
+  launch(KGdConverged{ctx->w, ctx->d_act}, sy.B);
+  launch(KGdAdopt{sy, ctx->sl, ctx->d_act, (double*)q_dev}, (long)sy.B * sy.Q, 8);
+  begin_all(ctx, nullptr, ctx->d_act);  // ... and of the chains that moved onto the manifold
+  state_eval(ctx, 0);
+  if (dev_sync()) return fail(std::string("chmc_gd_project_device: ") + g_err);
+  for (int c = 0; c < sy.B; ++c) {
+    if (status) status[c] = mask[c] ? st[c] : CHMC_INACTIVE;
+    if (!mask[c]) {
+      if (iters) iters[c] = 0;
+      if (err) err[c] = 0.0;
+    }
+  }
+  return 0;
 }
 
 struct KInnerRestore {  // failed chains that had completed inner steps: back to the step's start state

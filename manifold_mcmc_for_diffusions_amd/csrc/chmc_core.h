@@ -2858,4 +2858,205 @@ struct KAdamUpdate {
   }
 };
 
+// Gradient-descent initial states for any system (find_initial_state_by_gradient_descent, sde/mici_extensions.py:1550-1676).
+// init_objective (:1582-1618) conditions on a full state at EVERY observation time,
+//     c[t] = x_S(z(u), v_subseq[t]; start x_init[t]) - x_obs_seq[t],   x_init[0] = generate_x_0(z, v_0), x_init[t] = x_obs_seq[t - 1],
+//     objective = 1/2 mean(c^2) + 1/2 reg_coeff mean(q^2),
+// so the T observation intervals of a chain are independent S-step scans: one work item per (chain, interval) everywhere.
+// Scratch per (chain, interval): cres [B][T][X] = c, part [B][T][Z + 2] = {lambda^T Z_f sums, sum c^2, max |c|}.
+#define CHMC_GD_NPART(Z_) ((Z_) + 2)
+// max over |x| that keeps a NaN once it has seen one (jnp.max(jnp.abs(.)), maximum_norm)
+CHMC_HD inline double gd_absmax(double m, double x) {
+  const double a = fabs(x);
+  return (a > m || a != a) ? a : m;
+}
+// Forward half: interval t of chain c from x_init[t], its S states-before-a-step into slots t S .. t S + S - 1 of the work
+// trajectory (slot t S holds x_init[t]: the adjoint of the interval's first step is taken there) and c[t] into cres.
+template <class M>
+struct KGdFwd {
+  Sys sy;
+  const double* qin;  // [B][Q]
+  const double* xo;   // [B][T][X]
+  double* traj;       // [B][TRJ]
+  double* cres;       // [B][T][X]
+  CHMC_HD void operator()(int tid) const {
+    constexpr int X = M::X, V = M::V;
+    const int c = tid / sy.T, t = tid - c * sy.T;
+    const double* q = qin + (size_t)c * sy.Q;
+    const double* xoc = xo + (size_t)c * sy.T * X;
+    ChainConsts<M> cc;
+    cc.init(q, sy.dl);
+    double x[X], xn[X];
+    if (t == 0) {
+      M::gx0(cc.z, q + sy.U, x);
+    } else {
+      for (int a = 0; a < X; ++a) x[a] = xoc[(t - 1) * X + a];
+    }
+    const double* v = q + sy.U + sy.V0 + (size_t)t * sy.S * V;
+    double* tr = traj + (size_t)c * sy.TRJ + (size_t)t * sy.S * X;
+    for (int i = 0; i < sy.S; ++i) {
+      for (int a = 0; a < X; ++a) tr[(size_t)i * X + a] = x[a];
+      M::step(cc.k, x, v + (size_t)i * V, xn);
+      for (int a = 0; a < X; ++a) x[a] = xn[a];
+    }
+    for (int a = 0; a < X; ++a) cres[((size_t)c * sy.T + t) * X + a] = x[a] - xoc[t * X + a];
+  }
+};
+// Backward half, functor twin of k_gd_grad_wave (chmc_wave.h; the host emulation build runs this one): the adjoint of ONE
+// source c[t] / (T X) at the interval's end, a plain loop over the interval's steps.  Writes the v_seq part of the gradient
+// (lambda^T B + reg v / Q), for interval 0 the v_0 part through generate_x_0, and the interval's partials.
+template <class M>
+struct KGdGrad {
+  Sys sy;
+  const double* qin;
+  const double* traj;
+  const double* cres;
+  double reg;
+  double* grad;  // [B][Q]
+  double* part;  // [B][T][Z + 2]
+  CHMC_HD void operator()(int tid) const {
+    constexpr int X = M::X, V = M::V, Z = M::Z, V0 = M::V0, NP = CHMC_GD_NPART(Z);
+    const int c = tid / sy.T, t = tid - c * sy.T;
+    const double* q = qin + (size_t)c * sy.Q;
+    double* g = grad + (size_t)c * sy.Q;
+    ChainConsts<M> cc;
+    cc.init(q, sy.dl);
+    const double regq = reg / sy.Q, wsrc = 1.0 / ((double)sy.T * X);
+    double Lam[X], zacc[Z], csq = 0.0, cmax = 0.0;
+    for (int a = 0; a < X; ++a) {
+      const double ca = cres[((size_t)c * sy.T + t) * X + a];
+      Lam[a] = ca * wsrc;
+      csq += ca * ca;
+      cmax = gd_absmax(cmax, ca);
+    }
+    for (int a = 0; a < Z; ++a) zacc[a] = 0.0;
+    const double* vbase = q + sy.U + sy.V0;
+    for (int i = sy.S - 1; i >= 0; --i) {
+      const size_t s = (size_t)t * sy.S + i;
+      double A[X * X], Bm[X * V], Zf[X * Z];
+      const double* vv = vbase + s * V;
+      M::jac(cc.k, traj + (size_t)c * sy.TRJ + s * X, vv, A, Bm, Zf);
+      for (int d = 0; d < V; ++d) {
+        double tt = regq * vv[d];
+        for (int a = 0; a < X; ++a) tt += Lam[a] * Bm[a * V + d];
+        g[sy.U + sy.V0 + s * V + d] = tt;
+      }
+      for (int mz = 0; mz < Z; ++mz)
+        for (int a = 0; a < X; ++a) zacc[mz] += Lam[a] * Zf[a * Z + mz];
+      double nl[X];
+      for (int d = 0; d < X; ++d) {
+        double tt = 0.0;
+        for (int a = 0; a < X; ++a) tt += Lam[a] * A[a * X + d];
+        nl[d] = tt;
+      }
+      for (int d = 0; d < X; ++d) Lam[d] = nl[d];
+    }
+    if (t == 0) {  // x_init[0] = generate_x_0(z, v_0): the v_0 columns and the z-dependence
+      double dz[X * Z], dv0[X * V0];
+      M::gx0_jac(dz, dv0);
+      for (int mz = 0; mz < Z; ++mz)
+        for (int a = 0; a < X; ++a) zacc[mz] += Lam[a] * dz[a * Z + mz];
+      for (int d = 0; d < V0; ++d) {
+        double tt = regq * q[sy.U + d];
+        for (int a = 0; a < X; ++a) tt += Lam[a] * dv0[a * V0 + d];
+        g[sy.U + d] = tt;
+      }
+    }
+    double* po = part + ((size_t)c * sy.T + t) * NP;
+    for (int mz = 0; mz < Z; ++mz) po[mz] = zacc[mz];
+    po[Z] = csq, po[Z + 1] = cmax;
+  }
+};
+// Chain level: the intervals' partials added IN INTERVAL ORDER (no atomics: the sums do not depend on scheduling), the
+// generate_z chain rule and the regulariser on u, and the components the data term does not reach (u[Z] with variable
+// observation noise, the observation-noise part n): reg q / Q.  stat [B][2] = {1/2 mean(c^2), max |c|}.
+template <class M>
+struct KGdReduce {
+  Sys sy;
+  const double* qin;
+  const double* part;
+  double reg;
+  double* grad;
+  double* stat;
+  CHMC_HD void operator()(int c) const {
+    constexpr int X = M::X, Z = M::Z, NP = CHMC_GD_NPART(Z);
+    const double* q = qin + (size_t)c * sy.Q;
+    double* g = grad + (size_t)c * sy.Q;
+    const double regq = reg / sy.Q;
+    double zs[Z], csq = 0.0, cmax = 0.0;
+    for (int mz = 0; mz < Z; ++mz) zs[mz] = 0.0;
+    for (int t = 0; t < sy.T; ++t) {
+      const double* pi = part + ((size_t)c * sy.T + t) * NP;
+      for (int mz = 0; mz < Z; ++mz) zs[mz] += pi[mz];
+      csq += pi[Z];
+      cmax = gd_absmax(cmax, pi[Z + 1]);
+    }
+    double G[Z * Z];
+    M::gz_jac(q, G);
+    for (int d = 0; d < Z; ++d) {
+      double tt = regq * q[d];
+      for (int mz = 0; mz < Z; ++mz) tt += zs[mz] * G[mz * Z + d];
+      g[d] = tt;
+    }
+    for (int d = Z; d < sy.U; ++d) g[d] = regq * q[d];
+    for (int d = sy.U + sy.NV; d < sy.Q; ++d) g[d] = regq * q[d];
+    stat[c * 2] = 0.5 * csq / ((double)sy.T * X);
+    stat[c * 2 + 1] = cmax;
+  }
+};
+struct KGdStats {
+  const double* part;  // row sums of KAdamRow over all Q columns: |q|^2, gradient entries that are not finite
+  const double* stat;
+  int npart, Q;
+  double reg;
+  double* out;  // [B][3]: objective, max |c|, 1 when the objective and every gradient entry are finite
+  CHMC_HD void operator()(int c) const {
+    double sq = 0.0, bad = 0.0;
+    for (int j = 0; j < npart; ++j) sq += part[((size_t)c * npart + j) * 2], bad += part[((size_t)c * npart + j) * 2 + 1];
+    const double obj = stat[c * 2] + 0.5 * reg * (sq / Q);
+    out[c * 3] = obj;
+    out[c * 3 + 1] = stat[c * 2 + 1];
+    out[c * 3 + 2] = (bad == 0.0 && obj - obj == 0.0) ? 1.0 : 0.0;
+  }
+};
+// chmc_gd_project_device: the listed rows of the caller's buffers become the chains' states (zero momentum) ...
+struct KGdSetRows {
+  Sys sy;
+  Slots sl;
+  const double* qin;
+  const double* xo;
+  double* xobs;  // [B][T][X] of the context
+  const int* mask;
+  CHMC_HD void operator()(int tid) const {
+    const int c = tid / sy.Q, col = tid - c * sy.Q;
+    if (!mask[c]) return;
+    const int s = sl.cur[c];
+    pick(sl.q, s)[tid] = qin[tid];
+    pick(sl.p, s)[tid] = 0.0;
+    const int nx = sy.T * sy.X;
+    for (int i = col; i < nx; i += sy.Q) xobs[(size_t)c * nx + i] = xo[(size_t)c * nx + i];
+  }
+};
+// ... and, for the chains whose projection converged, the projected point (the other slot) replaces both the state's
+// position and the caller's row
+struct KGdConverged {
+  Work w;
+  int* act;  // in: the caller's mask; out: masked and converged
+  CHMC_HD void operator()(int c) const { act[c] = act[c] != 0 && w.nstat[c] == 0; }
+};
+struct KGdAdopt {
+  Sys sy;
+  Slots sl;
+  const int* act;
+  double* qout;
+  CHMC_HD void operator()(int tid) const {
+    const int c = tid / sy.Q;
+    if (!act[c]) return;
+    const int s = sl.cur[c];
+    const double v = pick(sl.q, s ^ 1)[tid];
+    pick(sl.q, s)[tid] = v;
+    qout[tid] = v;
+  }
+};
+
 }  // namespace chmc

@@ -13,7 +13,7 @@
 //   d_y [T], d_m0 [3][U][U], the block tables d_blk / d_obs2blk / d_blk_full and the work orders d_order / d_order_half /
 //   d_order_ident (a view takes its half's order);
 //   d_ham [B][4] ([B][3] Hamiltonian terms, or [B] values + [B][3] statistics: not chain-major) and the arrays of the
-//   trajectory trees (TreeState, d_tree_*), which only whole-batch launches use.
+//   trajectory trees (TreeState, d_tree_*) and the scratch of chmc_gd_objective_device (d_gd), which only whole-batch launches use.
 #pragma once
 #include <cstddef>
 #include "chmc_plan.h"

@@ -2137,6 +2137,127 @@ __global__ void __launch_bounds__(256) k_nld_grad_wave(Sys sy, const double* qin
   }
 }
 
+// Backward half of init_objective of find_initial_state_by_gradient_descent (sde/mici_extensions.py:1582-1618; functor twin
+// and scratch layout: KGdGrad, chmc_core.h): one wavefront per (chain, observation interval).  The interval is an
+// independent S-step scan from x_init[t] (KGdFwd left its states in slots t S .. of the work trajectory), so there is ONE
+// source, c[t] / (T X) at the interval's end, and nothing propagates across intervals: 64-step tiles are swept backwards
+// with M::jac and dpp_prefix_products as in k_nld_grad_wave.  Per step lambda^T B + reg v / Q goes straight into the
+// gradient; lambda^T Z_f is summed per lane and butterfly-reduced once; interval 0 carries lambda through generate_x_0 into
+// the v_0 columns and the z sums.  The z partials, sum c^2 and max |c| of the interval go to part [B][T][Z + 2], which
+// KGdReduce adds in interval order (no atomics).
+template <class M>
+__global__ void __launch_bounds__(256) k_gd_grad_wave(Sys sy, const double* qin, const double* trajb, const double* cres,
+                                                      double reg, double* grad, double* part) {
+  constexpr int X = M::X, V = M::V, Z = M::Z, V0 = M::V0, NP = CHMC_GD_NPART(Z);
+  const int lane = threadIdx.x & 63;
+  const long wid = (long)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wid >= (long)sy.B * sy.T) return;
+  const int c = (int)(wid / sy.T), j = (int)(wid - (long)c * sy.T);
+  const double* q = qin + (size_t)c * sy.Q;
+  const double* traj = trajb + (size_t)c * sy.TRJ;
+  double* g = grad + (size_t)c * sy.Q;
+  const double* vbase = q + sy.U + sy.V0;
+  ChainConsts<M> cc;
+  cc.init(q, sy.dl);
+  const int S = sy.S, ntile = (S + 63) >> 6;
+  const double regq = reg / sy.Q, wsrc = 1.0 / ((double)sy.T * X);
+  double Lam[X], zacc[Z], csq = 0.0, cmax = 0.0;
+#pragma unroll
+  for (int a = 0; a < X; ++a) {
+    const double ca = cres[((size_t)c * sy.T + j) * X + a];  // wave-uniform
+    Lam[a] = ca * wsrc;
+    csq += ca * ca;
+    cmax = gd_absmax(cmax, ca);
+  }
+#pragma unroll
+  for (int a = 0; a < Z; ++a) zacc[a] = 0.0;
+  for (int t = ntile - 1; t >= 0; --t) {
+    const int off = (t << 6) + (63 - lane);  // later steps in lower lanes (DPP prefix scans)
+    const bool valid = off < S;
+    const size_t s = (size_t)j * S + off;
+    double A[X * X], Bm[X * V], Zf[X * Z], vv[V];
+    if (valid) {
+      double x[X];
+#pragma unroll
+      for (int a = 0; a < X; ++a) x[a] = traj[s * X + a];
+#pragma unroll
+      for (int a = 0; a < V; ++a) vv[a] = vbase[s * V + a];
+      M::jac(cc.k, x, vv, A, Bm, Zf);
+    } else {
+#pragma unroll
+      for (int i = 0; i < X * X; ++i) A[i] = (i / X == i % X) ? 1.0 : 0.0;
+#pragma unroll
+      for (int i = 0; i < X * V; ++i) Bm[i] = 0.0;
+#pragma unroll
+      for (int i = 0; i < X * Z; ++i) Zf[i] = 0.0;
+#pragma unroll
+      for (int a = 0; a < V; ++a) vv[a] = 0.0;
+    }
+    double Inc[X * X], Eex[X * X];  // inclusive / exclusive products of the later steps (lower lanes)
+    dpp_prefix_products<X>(A, Inc, Eex);
+    double I0[X * X];
+#pragma unroll
+    for (int i = 0; i < X * X; ++i) I0[i] = bcast_lane63(Inc[i]);
+    double Ls[X];
+#pragma unroll
+    for (int d = 0; d < X; ++d) {
+      double tt = 0.0;
+#pragma unroll
+      for (int a = 0; a < X; ++a) tt += Lam[a] * Eex[a * X + d];
+      Ls[d] = tt;
+    }
+    if (valid) {
+#pragma unroll
+      for (int d = 0; d < V; ++d) {
+        double tt = regq * vv[d];
+#pragma unroll
+        for (int a = 0; a < X; ++a) tt += Ls[a] * Bm[a * V + d];
+        g[sy.U + sy.V0 + s * V + d] = tt;
+      }
+    }
+#pragma unroll
+    for (int mz = 0; mz < Z; ++mz) {
+      double tt = zacc[mz];
+#pragma unroll
+      for (int a = 0; a < X; ++a) tt += Ls[a] * Zf[a * Z + mz];
+      zacc[mz] = tt;
+    }
+    double nl[X];
+#pragma unroll
+    for (int d = 0; d < X; ++d) {
+      double tt = 0.0;
+#pragma unroll
+      for (int a = 0; a < X; ++a) tt += Lam[a] * I0[a * X + d];
+      nl[d] = tt;
+    }
+#pragma unroll
+    for (int d = 0; d < X; ++d) Lam[d] = nl[d];
+  }
+#pragma unroll
+  for (int mz = 0; mz < Z; ++mz) {
+    double v = zacc[mz];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    zacc[mz] = v;
+  }
+  if (lane == 0) {
+    if (j == 0) {  // x_init[0] = generate_x_0(z, v_0): the v_0 columns and the z-dependence
+      double dz[X * Z], dv0[X * V0];
+      M::gx0_jac(dz, dv0);
+      for (int mz = 0; mz < Z; ++mz)
+        for (int a = 0; a < X; ++a) zacc[mz] += Lam[a] * dz[a * Z + mz];
+      for (int d = 0; d < V0; ++d) {
+        double tt = regq * q[sy.U + d];
+        for (int a = 0; a < X; ++a) tt += Lam[a] * dv0[a * V0 + d];
+        g[sy.U + d] = tt;
+      }
+    }
+    double* po = part + ((size_t)c * sy.T + j) * NP;
+    for (int mz = 0; mz < Z; ++mz) po[mz] = zacc[mz];
+    po[Z] = csq, po[Z + 1] = cmax;
+  }
+}
+
 // J w (lmult_by_jacob_constr :822-877): one wave per (chain, block); lanes stride over the block's columns
 // (unit-stride loads of the RM stored rows and of the vector), butterfly reduction, lane 0 adds the dc/du and
 // dc/dn terms.  Result in work.cpad.

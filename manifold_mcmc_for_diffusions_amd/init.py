@@ -416,3 +416,186 @@ def find_initial_states_by_gradient_descent_noisy_system(ctx, rng=None, adam_ste
     xo = ctx.get_state(want_p=False)[2]
     ctx.set_state(q, None, xo, 0)
     return (q, xo, tries, None) if return_status else (q, xo, tries)
+
+
+GD_DRAW_BIT = KEYED_DRAW_BIT | (1 << 62)  # draws of the generic finder: 2^63 | 2^62 | try (disjoint from the noisy finder's)
+GD_OUTCOMES = ("projected", "diverged", "projection failed", "budget")
+
+
+def fhn_x_obs_seq_init(y_seq, seed):
+    """generate_x_obs_seq_init of the FitzHugh-Nagumo scripts ([y, 0.5 N(0, 1)], scripts/fhn_model_*_chmc_experiment.py:105-106)
+    as a pure function of (global chain, try): `gen(chains, tries) -> [n, T, X]` with the hidden component of (chain c, try k)
+    drawn from np.random.default_rng([seed, c, k])."""
+    y = np.asarray(y_seq, dtype=np.float64).reshape((-1, 1))
+
+    def gen(chains, tries):
+        return np.stack([np.concatenate((y, 0.5 * np.random.default_rng([int(seed), int(c), int(k)]).standard_normal(y.shape)), -1)
+                         for c, k in zip(chains, tries)])
+    return gen
+
+
+class _HostRows:
+    """[B, n] fp64 buffers of the finder below when the library's "device" is host memory (the emulation build of the tests)."""
+
+    def __init__(self, shape):
+        self.a = np.zeros(shape)
+
+    def ptr(self):
+        return self.a.ctypes.data
+
+    def get(self, rows):
+        return self.a[rows].copy()
+
+    def put(self, rows, vals):
+        self.a[rows] = vals
+
+    def host(self):
+        return self.a.copy()
+
+
+class _DeviceRows:
+    """The same on the GPU (torch-ROCm tensors; the library works on their pointers)."""
+
+    def __init__(self, shape, dev):
+        import torch
+        self.torch, self.dev = torch, dev
+        self.a = torch.zeros(shape, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def ptr(self):
+        return self.a.data_ptr()
+
+    def _idx(self, rows):
+        return self.torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(self.dev)
+
+    def get(self, rows):                                   # a device-side copy of the rows
+        out = self.a[self._idx(rows)]
+        self.torch.cuda.synchronize(self.dev)
+        return out
+
+    def put(self, rows, vals):                             # vals: rows taken with get(), a host array, or a number
+        if isinstance(vals, np.ndarray):
+            vals = self.torch.from_numpy(np.ascontiguousarray(vals)).to(self.dev)
+        self.a[self._idx(rows)] = vals
+        self.torch.cuda.synchronize(self.dev)              # (the library enqueues on its own stream)
+
+    def host(self):
+        return self.a.cpu().numpy()
+
+
+def find_initial_states_by_gradient_descent(ctx, generate_x_obs_seq_init, seed, chain_offset=0, total_chains=None, tol=1e-9,
+                                            adam_step_size=2e-1, reg_coeff=2e-2, coarse_tol=1e-1, max_iters=1000,
+                                            max_num_tries=10, use_newton=True, log=None, return_status=False):
+    """find_initial_state_by_gradient_descent (sde/mici_extensions.py:1550-1676), the reference's generic finder, for every
+    chain of `ctx` at once and resident on the device: any model, noisy (fixed or variable sigma) or noiseless observations,
+    any num_obs_per_subseq.
+
+    Per try: q ~ N(0, I) over ALL Q components and x_obs_seq_init [T, X]; Adam (jax.example_libraries.optimizers.adam: b1 0.9,
+    b2 0.999, eps 1e-8, bias correction restarting with the try) on
+        1/2 mean(c^2) + 1/2 reg_coeff mean(q^2),   c[t] = x_S(z(u), v_subseq[t]; start x_init[t]) - x_obs_seq_init[t],
+        x_init[0] = generate_x_0(z, v_0), x_init[t] = x_obs_seq_init[t - 1]
+    (:1582-1618).  At every iteration i < max_iters the objective and c are those of the parameters BEFORE the update: a
+    non-finite objective abandons the try; max|c| < coarse_tol sends those parameters to the system's projection solver
+    (Newton if use_newton; state_prev = state = (q, x_obs_seq_init, partition 0), dt = 1, constraint_tol = tol, the other
+    tolerances the solver defaults) -- a ConvergenceError abandons the try, a converged projection with max|constr| < tol is the
+    answer, otherwise Adam goes on.  When a chain has used max_num_tries tries: RuntimeError, the reference's message.
+
+    Rows are chains: a chain runs its tries one after the other in its own row and is frozen once it has its answer.
+    Keyed draws only: try k of global chain c = chain_offset + row starts from the keyed normals (seed, stream c, draw
+    2^63 | 2^62 | k) (chmc_fill_normal_device, filled on the device over all Q columns) and from
+    generate_x_obs_seq_init(chains, tries) -> [n, T, X], which gets GLOBAL chain indices and try numbers and must be a pure
+    function of them (fhn_x_obs_seq_init).  A try then depends on (seed, chain, try) and nothing else: any sharding of
+    `total_chains` chains over contexts gives the same states bit for bit, within one backend.
+    Per Adam iteration: chmc_gd_objective_device and chmc_adam_update_cols_device on device buffers and one [B, 3] read-back;
+    x_obs_seq_init rows go up when a try starts; nothing of size [B, Q] crosses PCIe inside the loop.
+
+    Leaves the found states set on `ctx` (partition 0, zero momentum, x_obs_seq = x_obs_seq_init of the winning try, as the
+    reference and chmc_init_linear_interpolation do; the first switch_partition recomputes x_obs_seq) and returns
+    (q [B, Q], x_obs_seq [B, T, X], tries [B]); with return_status also, per chain, the list of (Adam iteration at which the
+    try ended, outcome) of its tries, outcome one of GD_OUTCOMES."""
+    B, Q, T, X = ctx.B, ctx.Q, ctx.T, ctx.X
+    total = B + chain_offset if total_chains is None else total_chains
+    if chain_offset < 0 or chain_offset + B > total:
+        raise ValueError("chain_offset + the context's chains exceed total_chains")
+    if ctx.L.chmc_backend() == b"hip:gfx950":
+        dev = _torch_device(ctx)
+        if dev is None:
+            raise ValueError("the device-resident finder needs a CUDA-capable torch")
+        new = lambda shape: _DeviceRows(shape, dev)        # noqa: E731
+    else:                                                  # (host emulation build: the library's pointers are host pointers)
+        new = _HostRows
+    q, m, v, g, xo = new((B, Q)), new((B, Q)), new((B, Q)), new((B, Q)), new((B, T * X))
+    chains = chain_offset + np.arange(B)
+    tries = np.ones(B, dtype=np.int64)
+    it_in_try, t_adam = np.zeros(B, dtype=np.int64), np.zeros(B)
+    done = np.zeros(B, dtype=bool)
+    ends = [[] for _ in range(B)]
+    n_obj = n_proj = 0
+    b1, b2, eps = 0.9, 0.999, 1e-8                         # jax.example_libraries.optimizers.adam defaults
+    solver = dict(newton=use_newton, constraint_tol=tol, position_tol=1e-8, divergence_tol=1e10, max_iters=50)
+
+    def begin(rows):
+        """try tries[r] - 1 of the chains in `rows`: keyed start point, x_obs_seq_init, zero moments and gradient"""
+        k = tries[rows] - 1
+        x_init = np.asarray(generate_x_obs_seq_init(chains[rows], k), dtype=np.float64)
+        if x_init.shape != (len(rows), T, X):
+            raise ValueError(f"generate_x_obs_seq_init must return an array of shape ({len(rows)}, {T}, {X}), got {x_init.shape}")
+        ctx.fill_normal_device(seed, rows, chains[rows], np.uint64(GD_DRAW_BIT) | k.astype(np.uint64), Q, q.ptr(), Q)
+        xo.put(rows, x_init.reshape(len(rows), T * X))
+        for buf in (m, v, g):
+            buf.put(rows, 0.0)
+        it_in_try[rows], t_adam[rows] = 0, 0.0
+
+    # a defined state in every row before the first projection call (u = 0 is finite for every model)
+    ctx.set_state(np.zeros((B, Q)), None, np.zeros((B, T, X)), 0)
+    begin(np.arange(B))
+    while not done.all():
+        st = ctx.gd_objective_device(q.ptr(), xo.ptr(), reg_coeff, g.ptr())
+        n_obj += 1
+        active = ~done
+        finite = np.isfinite(st[:, 0]) & (st[:, 2] != 0.0)
+        diverged = active & ~finite
+        with np.errstate(invalid="ignore"):
+            attempt = active & finite & (st[:, 1] < coarse_tol)
+        projected = np.zeros(B, dtype=bool)
+        proj_failed = np.zeros(B, dtype=bool)
+        if attempt.any():
+            rows = np.flatnonzero(attempt)
+            before = q.get(rows)                           # (Adam goes on from these if the projected point is not the answer)
+            r = ctx.gd_project_device(attempt, q.ptr(), xo.ptr(), **solver)
+            n_proj += 1
+            conv = attempt & (r["status"] == 0)
+            proj_failed = attempt & ~conv
+            if conv.any():
+                with np.errstate(invalid="ignore"):
+                    projected = conv & (np.abs(ctx.constr()).max(1) < tol)
+            back = attempt[rows] & ~projected[rows] & conv[rows]
+            if back.any():
+                q.put(rows[back], before[np.flatnonzero(back).tolist()])
+        budget = active & ~diverged & ~proj_failed & ~projected & (it_in_try + 1 >= max_iters)
+        failed = diverged | proj_failed | budget
+        for name, mask in zip(GD_OUTCOMES, (projected, diverged, proj_failed, budget)):
+            for c in np.flatnonzero(mask):
+                ends[c].append((int(it_in_try[c]), name))
+        done |= projected
+        if failed.any():
+            rows = np.flatnonzero(failed)
+            if (tries[rows] >= max_num_tries).any():
+                raise RuntimeError(f"Did not find valid state in {max_num_tries} tries.")
+            tries[rows] += 1
+            begin(rows)
+        step = active & ~failed & ~projected
+        t_adam[step] += 1
+        tt = np.maximum(t_adam, 1.0)
+        coef = np.stack([1.0 / (1 - b2 ** tt), np.where(step, adam_step_size / (1 - b1 ** tt), 0.0)], 1)
+        ctx.adam_update_cols_device(Q, q.ptr(), m.ptr(), v.ptr(), g.ptr(), coef, b1, b2, eps)
+        it_in_try[step] += 1
+        if log is not None and n_obj % 100 == 0:
+            log(f"  gradient descent: {int(done.sum())} of {B} chains on the manifold, {n_obj} Adam iterations, "
+                f"{n_proj} projection calls")
+    q_h, xo_h = q.host(), xo.host().reshape(B, T, X)
+    if log is not None:
+        log(f"  gradient descent: done after {n_obj} Adam iterations and {n_proj} projection calls, tries {tries.tolist()}")
+    if return_status:
+        return q_h, xo_h, tries, dict(ends=ends, adam_iterations=n_obj, projection_calls=n_proj)
+    return q_h, xo_h, tries

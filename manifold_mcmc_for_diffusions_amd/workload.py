@@ -14,18 +14,29 @@ BOARDING_SCHOOL_COUNTS = (3, 8, 28, 75, 221, 281, 255, 235, 190, 125, 70, 28, 12
 class FhnWorkload:
     """FHN chains on one device: B chains of the (T, S, R, sigma) configuration, set up the way
     scripts/fhn_model_noisy_obs_chmc_experiment.py does (simulated data, linear-interpolation initial states,
-    Newton solver with the script tolerances)."""
+    Newton solver with the script tolerances).  init="gradient_descent": the initial states come from the reference's generic
+    finder instead (init.find_initial_states_by_gradient_descent, keyed by (seed, global chain, try), resident on the device)."""
 
     def __init__(self, num_chains, num_steps_per_obs=400, num_obs=100, num_obs_per_subseq=5, sigma=0.1,
                  obs_interval=0.2, device=0, chain_offset=0, total_chains=None, use_gaussian_splitting=False,
-                 num_steps_per_obs_data=10000, seed=SEED, device_init=False):
+                 num_steps_per_obs_data=10000, seed=SEED, device_init=False, init=None, log=None):
         self.B, self.S, self.T, self.R = num_chains, num_steps_per_obs, num_obs, num_obs_per_subseq
         self.sigma, self.obs_interval = sigma, obs_interval
         self.seed, self.chain_offset = seed, chain_offset
         self.y = em.simulate_fhn_observations(num_obs, obs_interval, num_steps_per_obs_data, seed=seed, sigma=sigma)
         self.ctx = ChmcContext("fhn", obs_interval, num_steps_per_obs, num_obs_per_subseq, self.y[:, 0], sigma=sigma,
                                use_gaussian_splitting=use_gaussian_splitting, num_chains=num_chains, device=device)
-        if device_init:  # same states, solved on the device (no [B, Q] host array, no 8 B Q byte upload)
+        if init not in (None, "linear_interpolation", "gradient_descent"):
+            raise ValueError("init must be None, 'linear_interpolation' or 'gradient_descent'")
+        if init == "gradient_descent":
+            from .init import find_initial_states_by_gradient_descent, fhn_x_obs_seq_init
+            _, _, self.init_tries = find_initial_states_by_gradient_descent(
+                self.ctx, fhn_x_obs_seq_init(self.y[:, 0], seed), seed, chain_offset=chain_offset, total_chains=total_chains,
+                log=log)
+            total = num_chains + chain_offset if total_chains is None else total_chains
+            self.rngs = [np.random.default_rng(s) for s in
+                         np.random.SeedSequence(seed).spawn(total)[chain_offset:chain_offset + num_chains]]
+        elif device_init:  # same states, solved on the device (no [B, Q] host array, no 8 B Q byte upload)
             self.rngs = fhn_initial_states_device(self.ctx, em.fhn, self.y, seed=seed, chain_offset=chain_offset,
                                                   total_chains=total_chains)
         else:
