@@ -186,64 +186,39 @@ static void select_partition(chmc_ctx* c, int p) {
   c->sy.order = c->d_order[p];
 }
 
-#define CHMC_DISPATCH(ctx, ...)                   \
-  do {                                            \
-    if ((ctx)->sy.varsig) { /* variable observation noise: dim_u = dim_z + 1 */ \
-      if ((ctx)->model == CHMC_MODEL_FHN) {       \
-        using M = FhnVsModel;                     \
-        if ((ctx)->RMt == 8) {                    \
-          constexpr int RM = 8;                   \
-          __VA_ARGS__                             \
-        } else {                                  \
-          constexpr int RM = 16;                  \
-          __VA_ARGS__                             \
-        }                                         \
-      } else if ((ctx)->RMt == 8) {               \
-        using M = SirVsModel;                     \
-        constexpr int RM = 8;                     \
-        __VA_ARGS__                               \
-      } else {                                    \
-        using M = SirVsModel;                     \
-        constexpr int RM = 16;                    \
-        __VA_ARGS__                               \
-      }                                           \
-    } else if ((ctx)->model == CHMC_MODEL_FHN) {  \
-      using M = FhnModel;                         \
-      if ((ctx)->RMt == 7) {                      \
-        constexpr int RM = 7;                     \
-        __VA_ARGS__                               \
-      } else if ((ctx)->RMt == 6) {               \
-        constexpr int RM = 6;                     \
-        __VA_ARGS__                               \
-      } else if ((ctx)->RMt == 8) {               \
-        constexpr int RM = 8;                     \
-        __VA_ARGS__                               \
-      } else {                                    \
-        constexpr int RM = 16;                    \
-        __VA_ARGS__                               \
-      }                                           \
-    } else if ((ctx)->model == CHMC_MODEL_FHN_NOTEBOOK) { \
-      using M = FhnNbModel;                       \
-      if ((ctx)->RMt == 6) {                      \
-        constexpr int RM = 6;                     \
-        __VA_ARGS__                               \
-      } else if ((ctx)->RMt == 8) {               \
-        constexpr int RM = 8;                     \
-        __VA_ARGS__                               \
-      } else {                                    \
-        constexpr int RM = 16;                    \
-        __VA_ARGS__                               \
-      }                                           \
-    } else if ((ctx)->RMt == 8) {                 \
-      using M = SirModel;                         \
-      constexpr int RM = 8;                       \
-      __VA_ARGS__                                 \
-    } else {                                      \
-      using M = SirModel;                         \
-      constexpr int RM = 16;                      \
-      __VA_ARGS__                                 \
-    }                                             \
-  } while (0)
+// The instantiation of a context: model type and row slots per block (RM), as the tag type `dispatch` hands to its callee.
+template <class M_, int RM_>
+struct Inst {
+  using M = M_;
+  static constexpr int RM = RM_;
+};
+// (model, varsig, RMt) -> (M, RM): calls f(Inst<M, RM>{}) for the context's instantiation.  The launch sites below are generic
+// lambdas (or function templates on <M, RM>) that read the two off the tag.
+template <class F>
+static void dispatch(const chmc_ctx* ctx, F&& f) {
+  const int rmt = ctx->RMt;
+  if (ctx->sy.varsig) {  // variable observation noise: dim_u = dim_z + 1
+    if (ctx->model == CHMC_MODEL_FHN) {
+      if (rmt == 8) f(Inst<FhnVsModel, 8>{});
+      else f(Inst<FhnVsModel, 16>{});
+    } else {
+      if (rmt == 8) f(Inst<SirVsModel, 8>{});
+      else f(Inst<SirVsModel, 16>{});
+    }
+  } else if (ctx->model == CHMC_MODEL_FHN) {
+    if (rmt == 7) f(Inst<FhnModel, 7>{});
+    else if (rmt == 6) f(Inst<FhnModel, 6>{});
+    else if (rmt == 8) f(Inst<FhnModel, 8>{});
+    else f(Inst<FhnModel, 16>{});
+  } else if (ctx->model == CHMC_MODEL_FHN_NOTEBOOK) {
+    if (rmt == 6) f(Inst<FhnNbModel, 6>{});
+    else if (rmt == 8) f(Inst<FhnNbModel, 8>{});
+    else f(Inst<FhnNbModel, 16>{});
+  } else {
+    if (rmt == 8) f(Inst<SirModel, 8>{});
+    else f(Inst<SirModel, 16>{});
+  }
+}
 
 // Kernel families, environment switches and the choice of a kernel per pass: chmc_plan.h.  chmc_create decides the plan, every
 // entry point refreshes the part that hangs on a per-call switch (CHMC_ENTER), the launch sites below switch on it.
@@ -252,102 +227,113 @@ static void refresh_plan(chmc_ctx* c) {
   c->plan_in.call = read_switches();
   c->plan = make_plan(c->plan_in);
 }
+// chain-level Woodbury solve: one wavefront per chain up to 64 blocks
+template <class M, int RM, int SYM, int TGT>
+static void solve_chain(const Sys& sy, const Slots& sl, const Work& w, int which, int qsel, int psel) {
 #ifdef CHMC_WAVE_KERNELS
-#define CHMC_SOLVE_CHAIN(T1, T2, T3, T4, ...)                                                   \
-  do {                                                                                          \
-    if (sy.K <= 64)                                                                             \
-      launch_wave(k_solve_chain_wave<T1, T2, T3, T4>, (long)sy.B, 5, __VA_ARGS__);              \
-    else                                                                                        \
-      launch(KSolveChain<T1, T2, T3, T4>{__VA_ARGS__}, sy.B, 5);                                \
-  } while (0)
-#else
-#define CHMC_SOLVE_CHAIN(T1, T2, T3, T4, ...) launch(KSolveChain<T1, T2, T3, T4>{__VA_ARGS__}, sy.B, 5)
+  if (sy.K <= 64) {
+    launch_wave(k_solve_chain_wave<M, RM, SYM, TGT>, (long)sy.B, 5, sy, sl, w, which, qsel, psel);
+    return;
+  }
 #endif
+  launch(KSolveChain<M, RM, SYM, TGT>{sy, sl, w, which, qsel, psel}, sy.B, 5);
+}
 
 #ifdef CHMC_WAVE_KERNELS
-// (Measured and rejected, round 3: giving every scan workgroup a CU of its own with 56 KB of dynamic LDS padding -- 512
-// chains, S = 800: 439 against 392 us per scan.  The scan's time doubles from 80 to 160 wavefronts because it is then bound
-// by the memory system, not by two wavefronts sharing a SIMD: 10 240 lanes x 32 B per step in 128-byte lines that belong to
-// 64 different streams per wave instruction = 2.8-3.3 TB/s, DESIGN.md section 4.)
-// forward scan (KernelPlan::fwd); GSEL_: guess trajectory for the time-parallel scan (k_fwd_par; 0: none available ->
+// time-parallel forward scan (k_fwd_par) on `waves` wavefronts per workgroup (par_waves_for / CHMC_CHAIN_SCAN_WAVES: 1, 2 or 4)
+template <class M, int RM, class... Args>
+static void fwd_par(int waves, long n, Args... args) {
+  if (waves == 4)
+    launch_blocks(k_fwd_par<M, RM, 4>, n, 256, 7, args...);
+  else if (waves == 2)
+    launch_blocks(k_fwd_par<M, RM, 2>, n, 128, 7, args...);
+  else
+    launch_blocks(k_fwd_par<M, RM, 1>, n, 64, 7, args...);
+}
+#endif
+// forward scan (KernelPlan::fwd); gsel: guess trajectory for the time-parallel scan (k_fwd_par; 0: none available ->
 // sequential scan, KernelPlan::fwd_cold)
-#define CHMC_FWD_PAR(W_, N_, ...)                                                        \
-  do {                                                                                   \
-    if ((W_) == 8)                                                                       \
-      launch_blocks(k_fwd_par<M, RM, 8>, N_, 512, 7, __VA_ARGS__);                       \
-    else if ((W_) == 4)                                                                  \
-      launch_blocks(k_fwd_par<M, RM, 4>, N_, 256, 7, __VA_ARGS__);                       \
-    else if ((W_) == 2)                                                                  \
-      launch_blocks(k_fwd_par<M, RM, 2>, N_, 128, 7, __VA_ARGS__);                       \
-    else                                                                                 \
-      launch_blocks(k_fwd_par<M, RM, 1>, N_, 64, 7, __VA_ARGS__);                        \
-  } while (0)
-#define CHMC_FWD(WHICH_, QSEL_, USENW_, STORE_, GSEL_)                                                           \
-  do {                                                                                                           \
-    stagger_wait(); /* half-batches: this half's scan runs after the other half's latest one */                  \
-    const FwdScan fwd_ = (GSEL_) != 0 ? c->plan.fwd : c->plan.fwd_cold;                                          \
-    if (fwd_ == FwdPar) {                                                                                        \
-      /* few long blocks: Newton on the trajectory, one wavefront per (chain, block); a scan that stores nothing */ \
-      /* (quasi-Newton) iterates on the work trajectory */                                                       \
-      CHMC_FWD_PAR(c->plan.fwd_waves, (long)sy.B * sy.K, sy, c->sl, c->w, WHICH_, QSEL_, USENW_,                 \
-                   (STORE_) ? (STORE_) : 2, GSEL_, c->round);                                                    \
-    } else if (fwd_ == FwdWave) {                                                                                \
-      if (STORE_)                                                                                                \
-        launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B * sy.K + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sy, c->sl, c->w, WHICH_,   \
-                      QSEL_, USENW_, STORE_, c->w, 0, 0);                                                        \
-      else                                                                                                       \
-        launch_blocks(k_fwd_scan<M, RM, false>, ((long)sy.B * sy.K + 63) / 64, 64, 7, sy, c->sl, c->w, WHICH_,   \
-                      QSEL_, USENW_, STORE_, c->w, 0, 0);                                                        \
-    } else {                                                                                                     \
-      launch(KFwd<M, RM>{sy, c->sl, c->w, WHICH_, QSEL_, USENW_, STORE_}, (long)sy.B * sy.K, 7);                 \
-    }                                                                                                            \
-    stagger_record();                                                                                            \
-  } while (0)
-// ... of the chains in the Newton loops of two problems, c->w and W1_, with the same (WHICH_, QSEL_): ONE launch of twice the
-// workgroups (the lock-step round path never scans in parallel in time: KernelPlan::pair_retractions)
-#define CHMC_FWD_PAIR(W1_, WHICH_, QSEL_, STORE_)                                                                \
-  do {                                                                                                           \
-    const long wg_ = ((long)sy.B * sy.K + 63) / 64;                                                              \
-    if (c->plan.fwd_cold == FwdWave) {                                                                           \
-      if (STORE_)                                                                                                \
-        launch_blocks(k_fwd_scan<M, RM, true, true>, 2 * wg_, 64 * (1 + CHMC_SCAN_HELPERS), 7, sy, c->sl, c->w, WHICH_, QSEL_, 1, \
-                      STORE_, W1_, WHICH_, QSEL_);                                                               \
-      else                                                                                                       \
-        launch_blocks(k_fwd_scan<M, RM, false, true>, 2 * wg_, 64, 7, sy, c->sl, c->w, WHICH_, QSEL_, 1, STORE_, W1_, WHICH_,     \
-                      QSEL_);                                                                                    \
-    } else {                                                                                                     \
-      launch(KFwd<M, RM>{sy, c->sl, c->w, WHICH_, QSEL_, 1, STORE_}, (long)sy.B * sy.K, 7);                      \
-      launch(KFwd<M, RM>{sy, c->sl, W1_, WHICH_, QSEL_, 1, STORE_}, (long)sy.B * sy.K, 7);                       \
-    }                                                                                                            \
-  } while (0)
+// (Measured and rejected for the sequential scan, round 3: giving every scan workgroup a CU of its own with 56 KB of dynamic
+// LDS padding -- 512 chains, S = 800: 439 against 392 us per scan.  The scan's time doubles from 80 to 160 wavefronts because
+// it is then bound by the memory system, not by two wavefronts sharing a SIMD: 10 240 lanes x 32 B per step in 128-byte lines
+// that belong to 64 different streams per wave instruction = 2.8-3.3 TB/s, DESIGN.md section 4.)
+template <class M, int RM>
+static void fwd(chmc_ctx* c, int which, int qsel, int use_nw, int store, int gsel) {
+  const Sys& sy = c->sy;
+#ifdef CHMC_WAVE_KERNELS
+  stagger_wait();  // half-batches: this half's scan runs after the other half's latest one
+  const FwdScan scan = gsel != 0 ? c->plan.fwd : c->plan.fwd_cold;
+  if (scan == FwdPar) {
+    // few long blocks: Newton on the trajectory, one wavefront per (chain, block); a scan that stores nothing
+    // (quasi-Newton) iterates on the work trajectory
+    fwd_par<M, RM>(c->plan.fwd_waves, (long)sy.B * sy.K, sy, c->sl, c->w, which, qsel, use_nw, store ? store : 2, gsel, c->round);
+  } else if (scan == FwdWave) {
+    if (store)
+      launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B * sy.K + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sy, c->sl, c->w, which,
+                    qsel, use_nw, store, c->w, 0, 0);
+    else
+      launch_blocks(k_fwd_scan<M, RM, false>, ((long)sy.B * sy.K + 63) / 64, 64, 7, sy, c->sl, c->w, which, qsel, use_nw, store,
+                    c->w, 0, 0);
+  } else {
+    launch(KFwd<M, RM>{sy, c->sl, c->w, which, qsel, use_nw, store}, (long)sy.B * sy.K, 7);
+  }
+  stagger_record();
 #else
-#define CHMC_FWD(WHICH_, QSEL_, USENW_, STORE_, GSEL_) \
-  launch(KFwd<M, RM>{sy, c->sl, c->w, WHICH_, QSEL_, USENW_, STORE_}, (long)sy.B * sy.K, 7)
-#define CHMC_FWD_PAIR(W1_, WHICH_, QSEL_, STORE_)                                             \
-  do { /* (the host emulation: two functor launches in place of the merged one) */           \
-    launch(KFwd<M, RM>{sy, c->sl, c->w, WHICH_, QSEL_, 1, STORE_}, (long)sy.B * sy.K, 7);     \
-    launch(KFwd<M, RM>{sy, c->sl, W1_, WHICH_, QSEL_, 1, STORE_}, (long)sy.B * sy.K, 7);      \
-  } while (0)
+  (void)gsel;
+  launch(KFwd<M, RM>{sy, c->sl, c->w, which, qsel, use_nw, store}, (long)sy.B * sy.K, 7);
 #endif
+}
+// ... of the chains in the Newton loops of two problems, c->w and w1, with the same (which, qsel): ONE launch of twice the
+// workgroups (the lock-step round path never scans in parallel in time: KernelPlan::pair_retractions)
+template <class M, int RM>
+static void fwd_pair(chmc_ctx* c, const Work& w1, int which, int qsel, int store) {
+  const Sys& sy = c->sy;
+#ifdef CHMC_WAVE_KERNELS
+  if (c->plan.fwd_cold == FwdWave) {
+    const long wg = ((long)sy.B * sy.K + 63) / 64;
+    if (store)
+      launch_blocks(k_fwd_scan<M, RM, true, true>, 2 * wg, 64 * (1 + CHMC_SCAN_HELPERS), 7, sy, c->sl, c->w, which, qsel, 1, store,
+                    w1, which, qsel);
+    else
+      launch_blocks(k_fwd_scan<M, RM, false, true>, 2 * wg, 64, 7, sy, c->sl, c->w, which, qsel, 1, store, w1, which, qsel);
+    return;
+  }
+#endif
+  // (and the host emulation: two functor launches in place of the merged one)
+  launch(KFwd<M, RM>{sy, c->sl, c->w, which, qsel, 1, store}, (long)sy.B * sy.K, 7);
+  launch(KFwd<M, RM>{sy, c->sl, w1, which, qsel, 1, store}, (long)sy.B * sy.K, 7);
+}
 
-// J^T lambda from the compact rows (KMuF + KUpdatePB).  One step per work item: two (KUpdatePB<..., NS = 2>) measured
-// 11 % slower (1.20 vs 1.08 ms per step); a full launch moves 0.66 GB in 125 us = 5.2 TB/s, the streaming rate of this part.
-#define CHMC_UPDATE_PB(TGT_, WHICH_, QSEL_, PSEL_)                                                                \
-  do {                                                                                                           \
-    launch(KMuF<RM, M::X, TGT_>{sy, c->sl, c->w, WHICH_}, (long)sy.B * sy.K * sy.NOBS * M::X, 5);                 \
-    launch_colmax(KUpdatePB<RM, M::X, M::V, TGT_, 1>{sy, c->sl, c->w, WHICH_, QSEL_, PSEL_},                      \
-                  sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0), sy.B, 4);                                         \
-  } while (0)
+// J^T lambda from the compact rows: mu_F (KMuF), then the column pass (KUpdatePB), one step per work item; a full launch
+// moves 0.66 GB in 125 us = 5.2 TB/s, the streaming rate of this part.
+template <class M, int RM, int TGT>
+static void mu_f(chmc_ctx* c, int which) {
+  const Sys& sy = c->sy;
+  launch(KMuF<RM, M::X, TGT>{sy, c->sl, c->w, which}, (long)sy.B * sy.K * sy.NOBS * M::X, 5);
+}
+// (flow_rev, fwd_qb, fwd_hfrac: KUpdatePB's members of those names, with its defaults)
+template <class M, int RM, int TGT>
+static void update_pb_columns(chmc_ctx* c, int which, int qsel, int psel, int flow_rev = 0, double* fwd_qb = nullptr,
+                              double fwd_hfrac = 0.0) {
+  const Sys& sy = c->sy;
+  launch_colmax(KUpdatePB<RM, M::X, M::V, TGT>{sy, c->sl, c->w, which, qsel, psel, flow_rev, fwd_qb, fwd_hfrac},
+                sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0), sy.B, 4);
+}
+template <class M, int RM, int TGT>
+static void update_pb(chmc_ctx* c, int which, int qsel, int psel, int flow_rev = 0, double* fwd_qb = nullptr,
+                      double fwd_hfrac = 0.0) {
+  mu_f<M, RM, TGT>(c, which);
+  update_pb_columns<M, RM, TGT>(c, which, qsel, psel, flow_rev, fwd_qb, fwd_hfrac);
+}
 
-// J^T lambda column pass: two columns per work item with 16-byte accesses when every offset is even
-#define CHMC_UPDATE(TGT_, ...)                                                                         \
-  do {                                                                                                 \
-    if (sy.Q % 2 == 0 && sy.NV % 2 == 0 && sy.U % 2 == 0 && sy.V0 % 2 == 0 && sy.V % 2 == 0 &&         \
-        sy.NCOL % 2 == 0)                                                                              \
-      launch_colmax(KUpdate<RM, TGT_, 2>{__VA_ARGS__}, sy.NCOL / 2, sy.B, 4);                          \
-    else                                                                                               \
-      launch_colmax(KUpdate<RM, TGT_, 1>{__VA_ARGS__}, sy.NCOL, sy.B, 4);                              \
-  } while (0)
+// J^T lambda column pass over the stored rows: two columns per work item with 16-byte accesses when every offset is even
+template <int RM, int TGT>
+static void update(const Sys& sy, const Slots& sl, const Work& w, int which, int qsel, int psel) {
+  if (sy.Q % 2 == 0 && sy.NV % 2 == 0 && sy.U % 2 == 0 && sy.V0 % 2 == 0 && sy.V % 2 == 0 && sy.NCOL % 2 == 0)
+    launch_colmax(KUpdate<RM, TGT, 2>{sy, sl, w, which, qsel, psel}, sy.NCOL / 2, sy.B, 4);
+  else
+    launch_colmax(KUpdate<RM, TGT, 1>{sy, sl, w, which, qsel, psel}, sy.NCOL, sy.B, 4);
+}
 
 extern "C" const char* chmc_last_error(void) { return g_err.c_str(); }
 extern "C" const char* chmc_backend(void) { return CHMC_BACKEND_NAME; }
@@ -525,8 +511,9 @@ static void ensure_rows(chmc_ctx* c) {
 #ifdef CHMC_WAVE_KERNELS
   if (!part_plan(c).rebuild_rows || c->rows_fresh) return;
   const Sys& sy = c->sy;
-  CHMC_DISPATCH(c, {
-    launch(KRowsFromPB<RM, M::X, M::V>{sy, c->sl}, (long)sy.B * sy.T * sy.S, 2);
+  dispatch(c, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    launch(KRowsFromPB<decltype(inst)::RM, M::X, M::V>{sy, c->sl}, (long)sy.B * sy.T * sy.S, 2);
   });
   c->rows_fresh = true;
 #else
@@ -538,9 +525,11 @@ static void state_eval_core(chmc_ctx* c, int which, bool with_grad = true, int t
   const PartitionPlan& pp = part_plan(c);
   (void)pp;
   c->rows_fresh = false;
-  CHMC_DISPATCH(c, {
+  dispatch(c, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
 #ifdef CHMC_WAVE_KERNELS
-    CHMC_FWD(which, 0, 0, 1, traj_guess);
+    fwd<M, RM>(c, which, 0, 0, 1, traj_guess);
     const long nbk = (long)sy.B * sy.K;
     if constexpr (RM > 8) {
       switch (pp.state) {
@@ -564,7 +553,7 @@ static void state_eval_core(chmc_ctx* c, int which, bool with_grad = true, int t
     } else {
       switch (pp.state) {
         case StateLean:  // the state sweep at three wavefronts per SIMD (compact rows)
-          launch_blocks(k_newton_lean<M, RM, true, true>, nbk, 64, 2, sy, c->sl, c->w, which, 0);
+          launch_blocks(k_state_lean<M, RM>, nbk, 64, 2, sy, c->sl, c->w, which);
           break;
         case StateRevStoreGramMfma:  // store the rows, then the Gram block from the stored rows on the matrix cores
           launch_wave(k_rev_wave<M, RM, 0, false>, nbk, 2, sy, c->sl, c->w, which, 0);
@@ -580,7 +569,7 @@ static void state_eval_core(chmc_ctx* c, int which, bool with_grad = true, int t
     launch(KStateBlk<M, RM>{sy, c->sl, c->w, which}, (long)sy.B * sy.K, 2);
 #endif
     launch(KStateChain<M>{sy, c->sl, c->w, which}, sy.B);
-    if (!with_grad) break;  // an inner h2-flow step that is not the last needs J and the Gram factors only (mici _step_b)
+    if (!with_grad) return;  // an inner h2-flow step that is not the last needs J and the Gram factors only (mici _step_b)
 #ifdef CHMC_WAVE_KERNELS
     if constexpr (RM > 8)  // 16-row blocks: the block over 16 lanes (a 16 x 16 inverse per lane lives in scratch memory)
       launch_blocks(k_gld_prep_wave<M, RM>, ((long)sy.B * sy.K + 3) / 4, 64, 9, sy, c->sl, c->w, which);
@@ -607,7 +596,7 @@ static void state_eval_core(chmc_ctx* c, int which, bool with_grad = true, int t
         break;
       case GldCompactFwdStored:  // 16-row blocks, large batches: the weights from the compact rows (DPP affine scan)
         if constexpr (RM > 8) {
-          launch_wave(k_gld_fwd_wave<M, RM, true, false>, nbk, 3, sy, c->sl, c->w, which);
+          launch_wave(k_gld_fwd_wave<M, RM, true>, nbk, 3, sy, c->sl, c->w, which);
           launch_wave(k_gld_bwd_wave_ldsrows<M, RM>, nbk, 3, sy, c->sl, c->w, which);
         }
         break;
@@ -649,7 +638,9 @@ static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool ini
   const Sys& sy = c->sy;
   if (init_pg) launch(KInitPg{sy, c->sl, c->w, which}, (long)sy.B * sy.Q, 8);
 #ifdef CHMC_WAVE_KERNELS
-  CHMC_DISPATCH(c, {
+  dispatch(c, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
     // J p -> cpad, J pg -> cpad2 from one read of the compact rows (16-row blocks: PB / LF are written beside the stored
     // rows; 9 instead of 48 doubles per step) or of the stored rows
     const bool compact = c->plan.rows == RowsCompact;
@@ -678,17 +669,15 @@ static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool ini
     w1.lampad = c->w.lampad2;
     w2.cpad = c->w.cpad2;
     launch(KSymBlk<M, RM>{sy, c->sl, w1, which, 0}, (long)sy.B * sy.K, 9);
-    CHMC_SOLVE_CHAIN(M, RM, 1, 1, sy, c->sl, w1, which, 0, 0);  // multipliers of p (and its u columns) -> lampad2
+    solve_chain<M, RM, 1, 1>(sy, c->sl, w1, which, 0, 0);  // multipliers of p (and its u columns) -> lampad2
     launch(KSymBlk<M, RM>{sy, c->sl, w2, which, 0}, (long)sy.B * sy.K, 9);
-    CHMC_SOLVE_CHAIN(M, RM, 1, 1, sy, c->sl, w2, which, 0, 3);  // multipliers of pg (and its u columns) -> lampad
+    solve_chain<M, RM, 1, 1>(sy, c->sl, w2, which, 0, 3);  // multipliers of pg (and its u columns) -> lampad
     if (compact && flow_rev) {
-      launch(KMuF<RM, M::X, 3>{sy, c->sl, c->w, which}, (long)sy.B * sy.K * sy.NOBS * M::X, 5);
-      launch_colmax(KUpdatePB<RM, M::X, M::V, 3, 1>{sy, c->sl, c->w, which, 0, 0, 1, fwd_qb, fwd_hfrac},
-                    sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0), sy.B, 4);
+      update_pb<M, RM, 3>(c, which, 0, 0, 1, fwd_qb, fwd_hfrac);
     } else if (compact) {
-      CHMC_UPDATE_PB(3, which, 0, 0);
+      update_pb<M, RM, 3>(c, which, 0, 0);
     } else {
-      CHMC_UPDATE(3, sy, c->sl, c->w, which, 0, 0);
+      update<RM, 3>(sy, c->sl, c->w, which, 0, 0);
     }
   });
 #else
@@ -701,7 +690,9 @@ static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool ini
 // p -= J^T G^-1 J p with J, G of slot `which`; p selected by (vsel, psel) (project_onto_cotangent_space :1243-1254)
 static void project_momentum(chmc_ctx* c, int which, int vsel, int psel) {
   const Sys& sy = c->sy;
-  CHMC_DISPATCH(c, {
+  dispatch(c, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
     const bool compact = c->plan.rows == RowsCompact;
 #ifdef CHMC_WAVE_KERNELS
     if (compact)
@@ -712,11 +703,11 @@ static void project_momentum(chmc_ctx* c, int which, int vsel, int psel) {
     launch(KJw<RM>{sy, c->sl, c->w, which, vsel | 256}, (long)sy.B * sy.K * RM, 6);
 #endif
     launch(KSymBlk<M, RM>{sy, c->sl, c->w, which, 0}, (long)sy.B * sy.K, 9);
-    CHMC_SOLVE_CHAIN(M, RM, 1, 1, sy, c->sl, c->w, which, 0, psel);
+    solve_chain<M, RM, 1, 1>(sy, c->sl, c->w, which, 0, psel);
     if (compact) {
-      CHMC_UPDATE_PB(1, which, 0, psel);
+      update_pb<M, RM, 1>(c, which, 0, psel);
     } else {
-      CHMC_UPDATE(1, sy, c->sl, c->w, which, 0, psel);
+      update<RM, 1>(sy, c->sl, c->w, which, 0, psel);
     }
   });
 }
@@ -726,34 +717,32 @@ static void project_momentum(chmc_ctx* c, int which, int vsel, int psel) {
 // iteration_scan: the forward scan of the iterate (constraint values; Newton: its trajectory into work.trajw).
 // use_nw 1: the chains of the loop (work.nw).
 static void iteration_scan(chmc_ctx* c, int newton, int prev, int qsel, int fwd_guess, int use_nw) {
-  const Sys& sy = c->sy;
-  CHMC_DISPATCH(c, {
+  dispatch(c, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
     if (newton) {
 #ifdef CHMC_WAVE_KERNELS
-      CHMC_FWD(prev ^ 1, qsel, use_nw, 2, fwd_guess);
+      fwd<M, RM>(c, prev ^ 1, qsel, use_nw, 2, fwd_guess);
       c->diag[7]++;
-#else
-      (void)fwd_guess, (void)use_nw;  // (host emulation: KNewtonBlk integrates the iterate itself)
-#endif
+#endif  // (host emulation: KNewtonBlk integrates the iterate itself)
     } else {
-      CHMC_FWD(prev ^ 1, qsel, use_nw, 0, fwd_guess);
+      fwd<M, RM>(c, prev ^ 1, qsel, use_nw, 0, fwd_guess);
       c->diag[7]++;
     }
   });
 }
 // ... of the iterates of two problems with the same (prev, qsel), c->w and w1, in one launch
 static void iteration_scan_pair(chmc_ctx* c, int newton, int prev, int qsel, const Work& w1) {
-  const Sys& sy = c->sy;
-  CHMC_DISPATCH(c, {
+  dispatch(c, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
     if (newton) {
 #ifdef CHMC_WAVE_KERNELS
-      CHMC_FWD_PAIR(w1, prev ^ 1, qsel, 2);
+      fwd_pair<M, RM>(c, w1, prev ^ 1, qsel, 2);
       c->diag[7] += c->plan.fwd_cold == FwdWave ? 1 : 2;
-#else
-      (void)w1;
 #endif
     } else {
-      CHMC_FWD_PAIR(w1, prev ^ 1, qsel, 0);
+      fwd_pair<M, RM>(c, w1, prev ^ 1, qsel, 0);
 #ifdef CHMC_WAVE_KERNELS
       c->diag[7] += c->plan.fwd_cold == FwdWave ? 1 : 2;
 #else
@@ -772,7 +761,9 @@ static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel) {
   const NewtonSweep sweep = part_plan(c).newton;
   // (these sweeps go on to factor the blocks, solve the chain's core system and form lambda and mu_F)
   const bool solved = newton && (sweep == NewtonIvlFsm || sweep == Newton16IvlCombFactor || sweep == Newton16IvlCombWg);
-  CHMC_DISPATCH(c, {
+  dispatch(c, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
     if (newton) {
 #ifdef CHMC_WAVE_KERNELS
       const long nbk = (long)sy.B * sy.K;
@@ -826,19 +817,19 @@ static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel) {
 #else
       launch(KNewtonBlk<M, RM>{sy, c->sl, c->w, prev, qsel}, (long)sy.B * sy.K, 1);
 #endif
-      if (!solved) CHMC_SOLVE_CHAIN(M, RM, 0, 0, sy, c->sl, c->w, prev, qsel, 0);
+      if (!solved) solve_chain<M, RM, 0, 0>(sy, c->sl, c->w, prev, qsel, 0);
     } else {
       launch(KSymBlk<M, RM>{sy, c->sl, c->w, prev, 1}, (long)sy.B * sy.K, 9);
-      CHMC_SOLVE_CHAIN(M, RM, 1, 0, sy, c->sl, c->w, prev, qsel, 0);
+      solve_chain<M, RM, 1, 0>(sy, c->sl, c->w, prev, qsel, 0);
     }
 #ifdef CHMC_WAVE_KERNELS
     if (c->plan.rows == RowsCompact) {
-      if (!solved) launch(KMuF<RM, M::X, 0>{sy, c->sl, c->w, prev}, (long)sy.B * sy.K * sy.NOBS * M::X, 5);
-      launch_colmax(KUpdatePB<RM, M::X, M::V, 0, 1>{sy, c->sl, c->w, prev, qsel, 0},
-                    sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0), sy.B, 4);
-    } else
+      if (!solved) mu_f<M, RM, 0>(c, prev);  // (the solving sweeps have formed mu_F)
+      update_pb_columns<M, RM, 0>(c, prev, qsel, 0);
+      return;
+    }
 #endif
-    CHMC_UPDATE(0, sy, c->sl, c->w, prev, qsel, 0);
+    update<RM, 0>(sy, c->sl, c->w, prev, qsel, 0);
   });
 }
 
@@ -859,8 +850,8 @@ static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel) {
 // layout with one 16-row block per chain (T <= 14) always runs the batched path of the same plan, so CHMC_RETRACT_KERNEL=1/2
 // changes nothing there.
 // The gate is written twice and the two must agree: chain_kernel_model (run time, on chmc_config::model) decides whether a
-// call takes the per-chain path, kChainKernels (compile time, on the model type CHMC_DISPATCH selects for that id) decides
-// which instantiations exist.  CHMC_DISPATCH maps CHMC_MODEL_SIR to SirModel / SirVsModel and nothing else to them, and both
+// call takes the per-chain path, kChainKernels (compile time, on the model type `dispatch` selects for that id) decides
+// which instantiations exist.  `dispatch` maps CHMC_MODEL_SIR to SirModel / SirVsModel and nothing else to them, and both
 // carry SirModel::ID -- held below, so a model id that drifts from its type's ID does not compile rather than launching nothing.
 static_assert(SirModel::ID == CHMC_MODEL_SIR && SirVsModel::ID == CHMC_MODEL_SIR && FhnModel::ID == CHMC_MODEL_FHN &&
                   FhnVsModel::ID == CHMC_MODEL_FHN && FhnNbModel::ID == CHMC_MODEL_FHN_NOTEBOOK,
@@ -884,7 +875,9 @@ static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ct
 #ifdef CHMC_WAVE_KERNELS
   if (const int waves = retract_waves(c, newton, views)) {
     int* iters_dst = count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf);
-    CHMC_DISPATCH(c, {
+    dispatch(c, [&](auto inst) {
+      using M = typename decltype(inst)::M;
+      constexpr int RM = decltype(inst)::RM;
       if constexpr (kChainKernels<M, RM>) {
         if (waves == 4)
           launch_blocks(k_retract_chain<M, RM, 4>, (long)sy.B, 256, 1, sy, c->sl, c->w, prev, qsel, ctol, ptol, dtol, max_iters,
@@ -1403,10 +1396,14 @@ extern "C" int chmc_get_head(chmc_ctx* ctx, int n, double* out) {
   CHMC_LEAVE("chmc_get_head")
 }
 
+// x at the observation times of every chain's current state, sequentially (KXobs)
+static void update_x_obs(chmc_ctx* ctx) {
+  const Sys& sy = ctx->sy;
+  dispatch(ctx, [&](auto inst) { launch(KXobs<typename decltype(inst)::M>{sy, ctx->sl, ctx->d_xobs}, sy.B); });
+}
 extern "C" int chmc_update_x_obs_seq(chmc_ctx* ctx) {
   CHMC_ENTER("chmc_update_x_obs_seq")
-  const Sys& sy = ctx->sy;
-  CHMC_DISPATCH(ctx, { launch(KXobs<M>{sy, ctx->sl, ctx->d_xobs}, sy.B); });
+  update_x_obs(ctx);
   CHMC_LEAVE("chmc_update_x_obs_seq")
 }
 extern "C" int chmc_switch_partition(chmc_ctx* ctx) {
@@ -1417,15 +1414,15 @@ extern "C" int chmc_switch_partition(chmc_ctx* ctx) {
   const bool par = ctx->plan.pb_allocated && ctx->have_state;
   if (par) {
     const Sys& so = ctx->sy;
-    CHMC_DISPATCH(ctx, { launch_blocks(k_xobs_par<M>, (long)so.B, 64, 0, so, ctx->sl, ctx->d_xobs); });
+    dispatch(ctx, [&](auto inst) {
+      launch_blocks(k_xobs_par<typename decltype(inst)::M>, (long)so.B, 64, 0, so, ctx->sl, ctx->d_xobs);
+    });
   }
   select_partition(ctx, (ctx->part + 1) % ctx->num_partition);
-  const Sys& sy = ctx->sy;
-  if (!par) CHMC_DISPATCH(ctx, { launch(KXobs<M>{sy, ctx->sl, ctx->d_xobs}, sy.B); });
+  if (!par) update_x_obs(ctx);
 #else
   select_partition(ctx, (ctx->part + 1) % ctx->num_partition);
-  const Sys& sy = ctx->sy;
-  CHMC_DISPATCH(ctx, { launch(KXobs<M>{sy, ctx->sl, ctx->d_xobs}, sy.B); });
+  update_x_obs(ctx);
 #endif
   begin_all(ctx, nullptr, nullptr);
   state_eval(ctx, 0);
@@ -1469,7 +1466,11 @@ extern "C" int chmc_constr(chmc_ctx* ctx, double* cvec) {
   if (!cvec) return fail("chmc_constr: null output");
   const Sys& sy = ctx->sy;
   begin_all(ctx, nullptr, nullptr);
-  CHMC_DISPATCH(ctx, { launch(KFwd<M, RM>{sy, ctx->sl, ctx->w, 0, 0, 0, 0}, (long)sy.B * sy.K, 7); });
+  dispatch(ctx, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
+    launch(KFwd<M, RM>{sy, ctx->sl, ctx->w, 0, 0, 0, 0}, (long)sy.B * sy.K, 7);
+  });
   ctx->counters[0]++;
   fetch_padded(ctx, ctx->w.cpad, cvec, 1);
   CHMC_LEAVE("chmc_constr")
@@ -1529,11 +1530,14 @@ extern "C" int chmc_lmult_by_jacob_constr(chmc_ctx* ctx, const double* vct, doub
   ensure_rows(ctx);
   h2d(ctx->w.vin, vct, sizeof(double) * (size_t)sy.B * sy.Q);
   begin_all(ctx, nullptr, nullptr);
+  dispatch(ctx, [&](auto inst) {
+    constexpr int RM = decltype(inst)::RM;
 #ifdef CHMC_WAVE_KERNELS
-  CHMC_DISPATCH(ctx, { launch_wave(k_jw_wave<RM>, (long)sy.B * sy.K, 6, sy, ctx->sl, ctx->w, 0, 2); });
+    launch_wave(k_jw_wave<RM>, (long)sy.B * sy.K, 6, sy, ctx->sl, ctx->w, 0, 2);
 #else
-  CHMC_DISPATCH(ctx, { launch(KJw<RM>{sy, ctx->sl, ctx->w, 0, 2}, (long)sy.B * sy.K * RM, 6); });
+    launch(KJw<RM>{sy, ctx->sl, ctx->w, 0, 2}, (long)sy.B * sy.K * RM, 6);
 #endif
+  });
   fetch_padded(ctx, ctx->w.cpad, out, 1);
   CHMC_LEAVE("chmc_lmult_by_jacob_constr")
 }
@@ -1562,7 +1566,7 @@ extern "C" int chmc_rmult_by_jacob_constr(chmc_ctx* ctx, const double* vct, doub
   pad_rows(ctx, vct, pad);
   h2d(ctx->w.lampad, pad.data(), sizeof(double) * pad.size());
   begin_all(ctx, nullptr, nullptr);
-  CHMC_DISPATCH(ctx, { CHMC_UPDATE(2, sy, ctx->sl, ctx->w, 0, 0, 0); });
+  dispatch(ctx, [&](auto inst) { update<decltype(inst)::RM, 2>(sy, ctx->sl, ctx->w, 0, 0, 0); });
   launch(KJtLamU{sy, ctx->sl, ctx->w}, sy.B);
   d2h(out, ctx->w.pb, sizeof(double) * (size_t)sy.B * sy.Q);
   CHMC_LEAVE("chmc_rmult_by_jacob_constr")
@@ -1575,9 +1579,11 @@ extern "C" int chmc_lmult_by_inv_gram(chmc_ctx* ctx, const double* vct, double* 
   pad_rows(ctx, vct, pad);
   h2d(ctx->w.cpad, pad.data(), sizeof(double) * pad.size());
   begin_all(ctx, nullptr, nullptr);
-  CHMC_DISPATCH(ctx, {
+  dispatch(ctx, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
     launch(KSymBlk<M, RM>{sy, ctx->sl, ctx->w, 0, 0}, (long)sy.B * sy.K, 9);
-    CHMC_SOLVE_CHAIN(M, RM, 1, 2, sy, ctx->sl, ctx->w, 0, 0, 0);
+    solve_chain<M, RM, 1, 2>(sy, ctx->sl, ctx->w, 0, 0, 0);
   });
   fetch_padded(ctx, ctx->w.lampad, out, 1);
   CHMC_LEAVE("chmc_lmult_by_inv_gram")
@@ -1589,15 +1595,17 @@ extern "C" int chmc_normal_space_component(chmc_ctx* ctx, const double* vct, dou
   ensure_rows(ctx);
   h2d(ctx->w.vin, vct, sizeof(double) * (size_t)sy.B * sy.Q);
   begin_all(ctx, nullptr, nullptr);
-  CHMC_DISPATCH(ctx, {
+  dispatch(ctx, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
 #ifdef CHMC_WAVE_KERNELS
     launch_wave(k_jw_wave<RM>, (long)sy.B * sy.K, 6, sy, ctx->sl, ctx->w, 0, 2 | 256);
 #else
     launch(KJw<RM>{sy, ctx->sl, ctx->w, 0, 2 | 256}, (long)sy.B * sy.K * RM, 6);
 #endif
     launch(KSymBlk<M, RM>{sy, ctx->sl, ctx->w, 0, 0}, (long)sy.B * sy.K, 9);
-    CHMC_SOLVE_CHAIN(M, RM, 1, 2, sy, ctx->sl, ctx->w, 0, 0, 0);
-    CHMC_UPDATE(2, sy, ctx->sl, ctx->w, 0, 0, 0);
+    solve_chain<M, RM, 1, 2>(sy, ctx->sl, ctx->w, 0, 0, 0);
+    update<RM, 2>(sy, ctx->sl, ctx->w, 0, 0, 0);
   });
   launch(KJtLamU{sy, ctx->sl, ctx->w}, sy.B);
   d2h(out, ctx->w.pb, sizeof(double) * (size_t)sy.B * sy.Q);
@@ -1639,12 +1647,13 @@ static int nld_core(chmc_ctx* ctx, int use_gaussian_splitting, double* grad_dev)
     h2d(ctx->d_order_ident, id.data(), sizeof(int) * sy.B);
   }
   begin_all(ctx, nullptr, nullptr);  // every chain active
-  CHMC_DISPATCH(ctx, {
-    (void)RM;
+  dispatch(ctx, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
     if (par) {
       Sys sp = sf;
       sp.order = ctx->d_order_ident;
-      CHMC_FWD_PAR(ctx->plan.nld_waves, (long)sy.B, sp, ctx->sl, ctx->w, 0, 1, 0, 2, 1, 0);
+      fwd_par<M, RM>(ctx->plan.nld_waves, (long)sy.B, sp, ctx->sl, ctx->w, 0, 1, 0, 2, 1, 0);
     } else if (ctx->plan.nld == FwdWave)
       launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sf, ctx->sl, ctx->w, 0, 1, 0, 2, ctx->w, 0, 0);
     else
@@ -1810,8 +1819,8 @@ extern "C" int chmc_gd_objective_device(chmc_ctx* ctx, const void* q_dev, const 
   const double *q = (const double*)q_dev, *xo = (const double*)xo_dev;
   double *g = (double*)grad_dev, *cres = ctx->d_gd, *part = ctx->d_gd + ncres;
   double* stat = part + (size_t)tasks * CHMC_GD_NPART(sy.Z);  // [B][2] = 1/2 mean(c^2), max |c|
-  CHMC_DISPATCH(ctx, {
-    (void)RM;
+  dispatch(ctx, [&](auto inst) {
+    using M = typename decltype(inst)::M;
     launch(KGdFwd<M>{sy, q, xo, ctx->w.trajw, cres}, (long)tasks, 7);
 #ifdef CHMC_WAVE_KERNELS
     launch_wave(k_gd_grad_wave<M>, (long)tasks, 0, sy, q, (const double*)ctx->w.trajw, (const double*)cres, reg_coeff, g, part);
@@ -2016,7 +2025,9 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
     if (n_steps_host) h2d(ctx->d_nsteps, n_steps_host, sizeof(int) * sy.B);
     begin_all(ctx, d_dt ? ctx->w.err : nullptr, d_active ? ctx->d_act : nullptr, 1.0);
     dev_zero(ctx->d_itf, sizeof(int) * sy.B), dev_zero(ctx->d_itb, sizeof(int) * sy.B);
-    CHMC_DISPATCH(ctx, {
+    dispatch(ctx, [&](auto inst) {
+      using M = typename decltype(inst)::M;
+      constexpr int RM = decltype(inst)::RM;
       if constexpr (kChainKernels<M, RM>) {
         if (waves == 4)
           launch_blocks(k_traj_chain<M, RM, 4>, (long)sy.B, 256, 1, sy, ctx->sl, ctx->w,
@@ -2038,7 +2049,7 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
   // The step is a sequence of phases per batch; with two half-batches every phase is enqueued for half 0 on its
   // stream, then for half 1 on the other, and the two Newton loops advance in lock step (run_projection).  The halves
   // are chain ranges of the same arrays, so nothing but the streams is shared; the forward scans of the two halves are
-  // kept out of phase (CHMC_FWD), which puts one half's latency-bound scan, factorisations and checks under the other
+  // kept out of phase (fwd), which puts one half's latency-bound scan, factorisations and checks under the other
   // half's reverse sweeps and column passes.
   //
   // mici _step_b with n_inner_step inner steps of dt_i = dt / n_inner_step: work.dt holds dt_i, the two half-kicks of

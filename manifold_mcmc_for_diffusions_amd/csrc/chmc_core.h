@@ -109,7 +109,7 @@ struct Slots {
   // block every row is the interval's frame applied to ONE row-independent matrix per step,
   //     dc_i/dv_s = LF[m][i] . PB[s],   PB[s] = Pf E_s B_s  (X x V),   LF[m][i] = the adjoint row i at the interval's end,
   // so the passes of a Newton iteration over the previous point's Jacobian (J^T lambda in KUpdatePB, the Gram
-  // contraction in k_newton_lean) read X V doubles per step instead of up to RM V.  Null when not in use.
+  // contraction in k_newton_ivl) read X V doubles per step instead of up to RM V.  Null when not in use.
   double* PB[2];  // [B][T S][X V]
   double* LF[2];  // [B][Kmax][NOBS][RM][X]
   int* cur;
@@ -1635,8 +1635,8 @@ struct KMuF {
     if (TGT == 3) w.muF2[(cb * sy.NOBS + m) * X + a] = t2;
   }
 };
-template <int RM, int X, int V, int TGT, int NS = 1>
-struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: both lie in the same observation interval)
+template <int RM, int X, int V, int TGT>
+struct KUpdatePB {  // one step per work item
   static constexpr bool kFinish = false;  // (as KUpdate; the fused convergence check that set it for TGT 0 is gone)
   Sys sy;
   Slots sl;
@@ -1693,8 +1693,8 @@ struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: bo
     double* tgt2 = TGT == 3 ? pick(sl.p, s) + off : nullptr;  // TGT 3: p with the multipliers lampad2
     const int TS = sy.T * sy.S;
     unsigned long long r = 0ULL;
-    if (idx < TS / NS) {
-      const int st0 = idx * NS;
+    if (idx < TS) {
+      const int st0 = idx;
       const int g = st0 / sy.S;  // observation interval
       const int b = sy.obs2blk[g];
       const int m = g - sy.blk[b].obs0;
@@ -1702,34 +1702,31 @@ struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: bo
       const double* pb = pick(sl.PB, s) + ((size_t)c * TS + st0) * (X * V);
       const size_t to = sy.V0 + (size_t)st0 * V;
       const bool wide = V == 2 && !((sy.Q | sy.U | sy.V0) & 1);
-      double old[NS * V], old2[NS * V], pbv[NS * X * V], mu[X], mu2[X];
+      double old[V], old2[V], pbv[X * V], mu[X], mu2[X];
       // all loads first: the work item's bytes in flight hide the memory latency
-      CHMC_UNROLL
-      for (int e = 0; e < NS; ++e) {
-        if (wide) {
-          const double2_ o = *reinterpret_cast<const double2_*>(tgt + to + e * V);
-          old[e * V] = o.x, old[e * V + V - 1] = o.y;
-          if (TGT == 3) {
-            const double2_ o2 = *reinterpret_cast<const double2_*>(tgt2 + to + e * V);
-            old2[e * V] = o2.x, old2[e * V + V - 1] = o2.y;
-          }
-        } else {
-          CHMC_UNROLL
-          for (int k = 0; k < V; ++k) {
-            old[e * V + k] = tgt[to + e * V + k];
-            if (TGT == 3) old2[e * V + k] = tgt2[to + e * V + k];
-          }
-        }
-      }
-      if ((NS * X * V) % 2 == 0) {
-        CHMC_UNROLL
-        for (int k = 0; k < NS * X * V; k += 2) {
-          const double2_ v = ld2_stream(pb + k);
-          pbv[k] = v.x, pbv[k + 1 < NS * X * V ? k + 1 : k] = v.y;
+      if (wide) {
+        const double2_ o = *reinterpret_cast<const double2_*>(tgt + to);
+        old[0] = o.x, old[V - 1] = o.y;
+        if (TGT == 3) {
+          const double2_ o2 = *reinterpret_cast<const double2_*>(tgt2 + to);
+          old2[0] = o2.x, old2[V - 1] = o2.y;
         }
       } else {
         CHMC_UNROLL
-        for (int k = 0; k < NS * X * V; ++k) pbv[k] = pb[k];
+        for (int k = 0; k < V; ++k) {
+          old[k] = tgt[to + k];
+          if (TGT == 3) old2[k] = tgt2[to + k];
+        }
+      }
+      if ((X * V) % 2 == 0) {
+        CHMC_UNROLL
+        for (int k = 0; k < X * V; k += 2) {
+          const double2_ v = ld2_stream(pb + k);
+          pbv[k] = v.x, pbv[k + 1 < X * V ? k + 1 : k] = v.y;
+        }
+      } else {
+        CHMC_UNROLL
+        for (int k = 0; k < X * V; ++k) pbv[k] = pb[k];
       }
       CHMC_UNROLL
       for (int a = 0; a < X; ++a) {
@@ -1737,46 +1734,41 @@ struct KUpdatePB {  // NS: consecutive steps per work item (2 when S is even: bo
         if (TGT == 3) mu2[a] = w.muF2[mo + a];
       }
       CHMC_UNROLL
-      for (int e = 0; e < NS; ++e)
+      for (int k = 0; k < V; ++k) {
+        double tt = 0.0, t2 = 0.0;
+        CHMC_UNROLL
+        for (int a = 0; a < X; ++a) {
+          tt += mu[a] * pbv[a * V + k];
+          if (TGT == 3) t2 += mu2[a] * pbv[a * V + k];
+        }
+        if (TGT == 0) {
+          const unsigned long long vb = absbits(tt);
+          r = vb > r ? vb : r;
+        }
+        old[k] -= tt;
+        if (TGT == 3) old2[k] -= t2;
+      }
+      if (wide) {
+        double2_ o;
+        o.x = old[0], o.y = old[V - 1];
+        *reinterpret_cast<double2_*>(tgt + to) = o;
+        if (TGT == 3) {
+          o.x = old2[0], o.y = old2[V - 1];
+          *reinterpret_cast<double2_*>(tgt2 + to) = o;
+          if (flow_rev) rev_flow2(c, s, off + to, o.x, o.y, old[0], old[V - 1]);
+        }
+      } else {
         CHMC_UNROLL
         for (int k = 0; k < V; ++k) {
-          double tt = 0.0, t2 = 0.0;
-          CHMC_UNROLL
-          for (int a = 0; a < X; ++a) {
-            tt += mu[a] * pbv[e * X * V + a * V + k];
-            if (TGT == 3) t2 += mu2[a] * pbv[e * X * V + a * V + k];
-          }
-          if (TGT == 0) {
-            const unsigned long long vb = absbits(tt);
-            r = vb > r ? vb : r;
-          }
-          old[e * V + k] -= tt;
-          if (TGT == 3) old2[e * V + k] -= t2;
-        }
-      CHMC_UNROLL
-      for (int e = 0; e < NS; ++e) {
-        if (wide) {
-          double2_ o;
-          o.x = old[e * V], o.y = old[e * V + V - 1];
-          *reinterpret_cast<double2_*>(tgt + to + e * V) = o;
+          tgt[to + k] = old[k];
           if (TGT == 3) {
-            o.x = old2[e * V], o.y = old2[e * V + V - 1];
-            *reinterpret_cast<double2_*>(tgt2 + to + e * V) = o;
-            if (flow_rev) rev_flow2(c, s, off + to + e * V, o.x, o.y, old[e * V], old[e * V + V - 1]);
-          }
-        } else {
-          CHMC_UNROLL
-          for (int k = 0; k < V; ++k) {
-            tgt[to + e * V + k] = old[e * V + k];
-            if (TGT == 3) {
-              tgt2[to + e * V + k] = old2[e * V + k];
-              if (flow_rev) rev_flow1(c, s, off + to + e * V + k, old2[e * V + k], old[e * V + k]);
-            }
+            tgt2[to + k] = old2[k];
+            if (flow_rev) rev_flow1(c, s, off + to + k, old2[k], old[k]);
           }
         }
       }
     } else {
-      const int e = idx - TS / NS;
+      const int e = idx - TS;
       double d = 0.0, d2 = 0.0;
       int col;
       if (e < sy.V0) {  // v_0 columns: the first block's stored rows
@@ -2442,15 +2434,6 @@ struct KCommitInner {
       ncommit[c] += 1;
       w.rev[c] = 0ULL;  // the reported reverse-check distance is that of the last inner step
     }
-  }
-};
-struct KCopyPadMasked {  // dst[c][:] = src[c][:] for the chains of the view (block-padded [B][n] arrays)
-  Work w;
-  double* dst;
-  const double* src;
-  int n;
-  CHMC_HD void operator()(int tid) const {
-    if (w.ok[tid / n]) dst[tid] = src[tid];
   }
 };
 

@@ -5,7 +5,7 @@
 // The library has TWO complete sets of kernels for the passes over a point's Jacobian (RowFamily); every other round-1 /
 // round-2 variant has been removed (round 3):
 //   compact rows (default)   Slots::PB / LF; Newton sweep = k_newton_ivl + k_newton_comb (+ k_newton_fsm_wave), state sweep =
-//                            k_newton_lean<.., STATE>, grad-log-det = k_gld_fwd_qx + k_gld_bwd_lean, J p = k_jw_pb,
+//                            k_state_lean, grad-log-det = k_gld_fwd_qx + k_gld_bwd_lean, J p = k_jw_pb,
 //                            J^T lambda = KMuF + KUpdatePB; 16-row blocks: rows stored as well (state sweep
 //                            k_rev_wave_ldsrows + k_gram_rows) unless the blocks are few (interval-parallel sweeps)
 //   stored rows              round 1's kernels over Slots::Jv: k_rev_wave / k_rev_wave_ldsrows, k_gram_rows, k_gld_fwd_wave +
@@ -51,6 +51,8 @@
 #ifndef CHMC_CHAIN_SCAN_WAVES
 #define CHMC_CHAIN_SCAN_WAVES 4  // (chmc_retract.h, likewise)
 #endif
+static_assert(CHMC_CHAIN_SCAN_WAVES == 1 || CHMC_CHAIN_SCAN_WAVES == 2 || CHMC_CHAIN_SCAN_WAVES == 4,
+              "k_fwd_par is launched with 1, 2 or 4 wavefronts per workgroup (fwd_par in chmc_api.inc)");
 #ifndef CHMC_CHAIN_WG4_MAX_PER_CU
 #define CHMC_CHAIN_WG4_MAX_PER_CU 4  // (chains per CU up to which two 4-wavefront workgroups per CU match or beat batched launches)
 #endif
@@ -102,7 +104,7 @@ struct PlanInput {
 enum RowFamily { RowsCompact, RowsStored, RowsStoredMfma };
 enum FwdScan { FwdPar /* k_fwd_par<W> */, FwdWave /* k_fwd_scan */, FwdFunctor /* KFwd; comparator: KFullScan */ };
 enum StateSweep {
-  StateLean,             // k_newton_lean<.., STATE>
+  StateLean,             // k_state_lean
   StateIvlComb,          // k_newton_ivl<STATE> + k_newton_comb<STATE>
   StateIvlCombWg,        // k_newton_ivl<STATE> + k_newton_comb_wg<STATE> (one block per chain; factors the block as well)
   StateLdsrowsGram,      // k_rev_wave_ldsrows + k_gram_rows

@@ -620,16 +620,15 @@ __device__ __forceinline__ void retract_chain_body(const Sys& sy, const Slots& s
     wg_phase_sync();
     CHMC_RPROF(50);
     // ---- q_v -= mu_F[m] . PB[s] (and the v_0 / observation-noise columns), max |delta q|
-    // (Measured and rejected: two consecutive steps per work item (KUpdatePB<.., 2>): 19.6 -> 30.6 us per iteration; the loads of
-    // three steps issued before the first store: 42.5 us -- every variant that holds more than one step's 15 doubles per thread
-    // spills in this kernel, whose 256 registers are set by the scan and the factorisation.)
+    // (One step per work item: every variant that holds more than one step's 15 doubles per thread spills in this kernel,
+    // whose 256 registers are set by the scan and the factorisation; docs/history.md.)
     double err0 = 0.0;
     unsigned long long nb0 = 0ULL;
     const int cu = opaque_u(c);
     if (tid == 0) err0 = w.err[cu], nb0 = w.ndq[cu];  // (left by the combine step; in flight under the update pass)
     unsigned long long r = 0ULL;
     {
-      const KUpdatePB<RM, X, V, 0, 1> upd{sy, sl, w, prev, qsel, 0};
+      const KUpdatePB<RM, X, V, 0> upd{sy, sl, w, prev, qsel, 0};
       for (int idx = tid; idx < ncol; idx += 64 * NW) {
         const unsigned long long v = upd(cu, idx);
         r = v > r ? v : r;
@@ -863,7 +862,7 @@ __global__ void __launch_bounds__(64 * NW, 2)
     wg_phase_sync();
     const int c12 = opaque_u(c);
     {
-      const KUpdatePB<RM, X, V, 3, 1> up3{sy, sl, w, 1, 0, 0};
+      const KUpdatePB<RM, X, V, 3> up3{sy, sl, w, 1, 0, 0};
       for (int idx = tid; idx < ncol; idx += NT) (void)up3(c12, idx);
     }
     wg_phase_sync();

@@ -9,8 +9,8 @@
 //     of the tile (dpp_prefix_products below),
 //   * inside an observation interval every adjoint row is the interval's FRAME (the rows at its end, wave-uniform) times
 //     that row-independent product, so the per-lane work carries no row index: X x Z, X x X running sums, the compact
-//     form PB_s = P_f E_s B_s of the step's Jacobian rows, and the RM-sized products once per interval (k_newton_lean:
-//     Newton iteration and state evaluation; k_newton_ivl / k_newton_comb: the same in two phases for few long blocks;
+//     form PB_s = P_f E_s B_s of the step's Jacobian rows, and the RM-sized products once per interval (k_state_lean:
+//     state evaluation; k_newton_ivl / k_newton_comb: Newton iteration and state evaluation in two phases;
 //     k_rev_wave: the round-1 formulation with the rows in registers, kept for 16-row blocks and as a fallback),
 //   * the passes over a stored Jacobian (J w, J^T lambda, Gram contraction, grad-log-det weights) read the compact rows
 //     (Slots::PB / LF, chmc_core.h).
@@ -203,9 +203,6 @@ __device__ __forceinline__ void dpp_rowaffine_prefix(double* I2, double* g) {
 // GRAM false (16-row blocks): no Gram accumulation -- the rows are stored (MODE 0: into the slot, MODE 1: into
 // work.JvW) and k_gram_rows forms the Gram block from the stored rows.  A 16 x 16 accumulator per lane does not fit
 // the register file: with it the sweep ran out of scratch memory, 25x slower than the 8-row instantiations.
-#ifndef CHMC_REV_ZW
-#define CHMC_REV_ZW 1
-#endif
 template <class M, int RM, int MODE, bool GRAM = true>
 __global__ void __launch_bounds__(256) k_rev_wave(Sys sy, Slots sl, Work w, int which, int qsel) {
   constexpr int X = M::X, V = M::V, Z = M::Z, U = M::U, V0 = M::V0;
@@ -225,7 +222,7 @@ __global__ void __launch_bounds__(256) k_rev_wave(Sys sy, Slots sl, Work w, int 
   // The hot loop therefore carries 8 + 14 (Newton) or 8 + 4 (state) running sums per lane for FitzHugh-Nagumo instead
   // of 28 + 49, does not form the rows at all in a Newton iteration, and the RM-sized products are taken once per
   // interval (flush_frame), where the rows for the next interval are formed as LamF Pf as well.
-  constexpr bool ZW = CHMC_REV_ZW && GRAM;
+  constexpr bool ZW = GRAM;  // the frames carry the Gram accumulation
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (wid >= sy.B * sy.K) return;
@@ -240,17 +237,6 @@ __global__ void __launch_bounds__(256) k_rev_wave(Sys sy, Slots sl, Work w, int 
   const double* traj = (MODE == 1 ? w.trajw : pick(sl.traj, sl_)) + (size_t)c * sy.TRJ + (size_t)(bd.step0 + CHMC_TPAD * b) * X;
   const double* Jr = pick(sl.Jv, sl_) + (size_t)c * RM * NV;  // MODE 1: read; MODE 0: written through Jo
   double* Jo = (MODE == 1 ? w.JvW : pick(sl.Jv, sl_)) + (size_t)c * RM * NV;
-  double* PBo = nullptr;  // compact rows of the evaluated state (MODE 0 with frames): Slots::PB / Slots::LF
-  double* LFo = nullptr;
-  if (MODE == 0 && CHMC_REV_ZW && GRAM) {
-    double* pb0 = pick(sl.PB, sl_);
-    if (pb0) {
-      PBo = pb0 + (size_t)c * sy.T * sy.S * (X * V);
-      LFo = pick(sl.LF, sl_) + cb * sy.NOBS * RM * X;
-    }
-  }
-  // MODE 0, qsel bit 1: the compact form only -- the rows of the step columns are not written (the v_0 columns are)
-  const bool store_rows = !(MODE == 0 && PBo && (qsel & 2));
   ChainConsts<M> cc;
   cc.init(q, sy.dl);
   const double* vbase = q + sy.U + sy.V0 + (size_t)bd.step0 * V;
@@ -436,17 +422,6 @@ __global__ void __launch_bounds__(256) k_rev_wave(Sys sy, Slots sl, Work w, int 
       if (MODE == 0) {
         if (r.valid) {  // the rows of this step, dc_i/dv_s = LamF_i T_s, go straight to memory
           const size_t col0 = colb + (size_t)r.s * V;
-          if (PBo) {  // ... and T_s itself: the compact form of the rows (Slots::PB)
-            double* dst = PBo + (size_t)(bd.step0 + r.s) * (X * V);
-            if ((X * V) % 2 == 0) {
-#pragma unroll
-              for (int k = 0; k + 1 < X * V; k += 2) st_async2(dst + k, T[k], T[k + 1]);
-            } else {
-#pragma unroll
-              for (int k = 0; k < X * V; ++k) st_async(dst + k, T[k]);
-            }
-          }
-          if (store_rows)
 #pragma unroll
           for (int i = 0; i < RM; ++i) {
             double jr0[V];
@@ -601,11 +576,6 @@ __global__ void __launch_bounds__(256) k_rev_wave(Sys sy, Slots sl, Work w, int 
       if (ZW) {
 #pragma unroll
         for (int i = 0; i < RM * X; ++i) LamF[i] = Lam[i];
-        if (MODE == 0 && LFo && lane == 0) {  // the frame of interval j (Slots::LF)
-          double* dst = LFo + (size_t)j * RM * X;
-#pragma unroll
-          for (int i = 0; i < RM * X; ++i) dst[i] = Lam[i];
-        }
       }
     }
     stage1(r1, sc1);  // tile tt - 1 (identity when there is none)
@@ -704,8 +674,8 @@ __global__ void __launch_bounds__(256) k_rev_wave(Sys sy, Slots sl, Work w, int 
   }
 }
 
-// Newton-iteration sweep (k_rev_wave<.., MODE 1>) rebuilt around the interval frames for TWO wavefronts per SIMD.
-// With the frames the hot loop of a Newton iteration carries only X x Z + RM x X running sums per lane, but k_rev_wave
+// The sweep of k_rev_wave rebuilt around the interval frames for TWO OR THREE wavefronts per SIMD.
+// With the frames the hot loop carries only X x Z + X x X running sums per lane, but k_rev_wave
 // still keeps the RM x RM Gram block, the RM x Z dc/dz rows and the adjoint rows per lane (210 registers that are touched
 // once per interval), which pins it at one wavefront per SIMD, where the 6-level shuffle scan of every tile is exposed
 // latency (measured: cutting its HBM bytes by 17 % changed nothing).  Here the per-interval running sums are added up
@@ -715,23 +685,20 @@ __global__ void __launch_bounds__(256) k_rev_wave(Sys sy, Slots sl, Work w, int 
 #ifndef CHMC_LEAN_WAVES
 #define CHMC_LEAN_WAVES 2
 #endif
-// With the compact rows (PBJ) the FitzHugh-Nagumo instantiations need 188 VGPRs; capped at 168 (three wavefronts per
-// SIMD) they spill 13 dwords and still run 7 % faster (newton_blk 1.31 -> 1.21 ms per step).
+// The FitzHugh-Nagumo instantiations need 188 VGPRs; capped at 168 (three wavefronts per SIMD) they spill 13 dwords and
+// still run 7 % faster (newton_blk 1.31 -> 1.21 ms per step).
 #ifndef CHMC_LEAN_WAVES_PB
 #define CHMC_LEAN_WAVES_PB 3
 #endif
-// PBJ: the previous point's rows are read in their compact form (Slots::PB / LF): X V doubles per step instead of RM V,
-// an X x X running sum instead of RM x X, and the frames of the previous point applied once per interval.
-// STATE (with PBJ): the same sweep as the STATE EVALUATION of slot `which` (k_rev_wave<MODE 0> at a third of its
-// registers): the Gram block is that of the point itself (X x X running sum of T T^T, own frames), the compact rows PB / LF
-// and the v_0 columns of the rows are written, dc/du rows go to the slot and dc/dz rows to work.zbP.
+// The kernel is the STATE EVALUATION of slot `which` on the compact rows (k_rev_wave<MODE 0> at a third of its registers):
+// the Gram block is that of the point itself (X x X running sum of T T^T, own frames), the compact rows PB / LF
+// and the v_0 columns of the rows are written, dc/du rows go to the slot and dc/dz rows to work.zbP.  (The Newton
+// iterations that once ran through it run through k_newton_ivl + k_newton_comb below.)
 #define CHMC_IVL_N(X, Z) (2 * (X) * (X) + (X) * (Z))  // per-interval sums Ss, Ws, Pt (k_newton_ivl below)
-template <class M, int RM, bool PBJ = false, bool STATE = false>
-__global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVES_PB : CHMC_LEAN_WAVES)
-    k_newton_lean(Sys sy, Slots sl, Work w, int which, int qsel) {
+template <class M, int RM>
+__global__ void __launch_bounds__(64, (M::X * M::V <= 4) ? CHMC_LEAN_WAVES_PB : CHMC_LEAN_WAVES)
+    k_state_lean(Sys sy, Slots sl, Work w, int which) {
   constexpr int X = M::X, V = M::V, Z = M::Z, U = M::U, V0 = M::V0;
-  static_assert(PBJ || !STATE, "the state evaluation works on the compact rows");
-  constexpr int NJP = STATE ? 1 : (PBJ ? X * V : RM * V), NY = PBJ ? X * X : RM * X;
   static_assert(RM <= 8, "blocks of at most 8 rows");
   __shared__ double LamF[RM * X], Dl[RM * RM], zl[RM * Z], Ys[RM * X], Ws[X * Z], Ss[X * X];
   const int lane = threadIdx.x & 63;
@@ -739,22 +706,19 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
   if (wid >= sy.B * sy.K) return;
   const int cbi = sy.order[wid];  // work order: longest blocks first
   const int c = cbi / sy.K, b = cbi - c * sy.K;
-  if (STATE ? !w.ok[c] : !newton_select(w, c, which, qsel)) return;
+  if (!w.ok[c]) return;
   const BlockDesc bd = sy.blk[b];
   const int sl_ = sl.cur[c] ^ which;
   const size_t cb = (size_t)c * sy.Kmax + b;
   const int S = sy.S, NV = sy.NV;
-  const double* q = (STATE ? pick(sl.q, sl_) : (qsel ? w.qb : pick(sl.q, sl_ ^ 1))) + (size_t)c * sy.Q;
-  const double* traj = (STATE ? pick(sl.traj, sl_) : w.trajw) + (size_t)c * sy.TRJ + (size_t)(bd.step0 + CHMC_TPAD * b) * X;
-  const double* Jr = pick(sl.Jv, sl_) + (size_t)c * RM * NV;
-  const double* PBr = PBJ ? pick(sl.PB, sl_) + ((size_t)c * sy.T * S + bd.step0) * (X * V) : nullptr;
-  const double* LFr = PBJ ? pick(sl.LF, sl_) + cb * sy.NOBS * RM * X : nullptr;
-  double* PBo = STATE ? pick(sl.PB, sl_) + ((size_t)c * sy.T * S + bd.step0) * (X * V) : nullptr;
-  double* LFo = STATE ? pick(sl.LF, sl_) + cb * sy.NOBS * RM * X : nullptr;
+  const double* q = pick(sl.q, sl_) + (size_t)c * sy.Q;
+  const double* traj = pick(sl.traj, sl_) + (size_t)c * sy.TRJ + (size_t)(bd.step0 + CHMC_TPAD * b) * X;
+  double* Jo = pick(sl.Jv, sl_) + (size_t)c * RM * NV;  // (only the rows' v_0 columns are written)
+  double* PBo = pick(sl.PB, sl_) + ((size_t)c * sy.T * S + bd.step0) * (X * V);
+  double* LFo = pick(sl.LF, sl_) + cb * sy.NOBS * RM * X;
   ChainConsts<M> cc;
   cc.init(q, sy.dl);
   const double* vbase = q + sy.U + sy.V0 + (size_t)bd.step0 * V;
-  const size_t colb = (size_t)sy.V0 + (size_t)bd.step0 * V;
   auto lds_sync = [&]() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -763,37 +727,35 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
   for (int e = lane; e < RM * RM; e += 64) Dl[e] = 0.0;
   for (int e = lane; e < RM * Z; e += 64) zl[e] = 0.0;
   lds_sync();
-  double Wacc[X * Z], Yacc[NY], Pf[X * X];
+  double Wacc[X * Z], Yacc[X * X], Pf[X * X];
 #pragma unroll
   for (int i = 0; i < X * Z; ++i) Wacc[i] = 0.0;
 #pragma unroll
-  for (int i = 0; i < NY; ++i) Yacc[i] = 0.0;
+  for (int i = 0; i < X * X; ++i) Yacc[i] = 0.0;
 #pragma unroll
   for (int i = 0; i < X * X; ++i) Pf[i] = (i / X == i % X) ? 1.0 : 0.0;
   // end of an interval: the wave's sums, the RM-sized products (one lane per entry), the rows at the interval's start
   // (jprev: the interval that has just been swept; bd.nobs when nothing has been swept yet)
   auto flush_frame = [&](int jprev) {
 #pragma unroll
-    for (int i = 0; i < NY; ++i) {
+    for (int i = 0; i < X * X; ++i) {
       double v = Yacc[i];
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-      if (lane == i) (PBJ ? Ss : Ys)[i] = v;
+      if (lane == i) Ss[i] = v;
       Yacc[i] = 0.0;
     }
-    if (PBJ) {  // Ys[jj][a] = sum_s T_s[a][:] . (dc_jj/dv_s of the stored point) = sum_a2 Ss[a][a2] LFprev[jj][a2]
-      lds_sync();
-      if (lane < RM * X) {
-        const int jj = lane / X, a = lane - jj * X;
-        double tt = 0.0;
-        if (jprev < bd.nobs) {
-          // (STATE: the point's own frame, still in LamF at this point of the flush)
-          const double* lf = STATE ? LamF + jj * X : LFr + ((size_t)jprev * RM + jj) * X;
+    // Ys[jj][a] = sum_s T_s[a][:] . (dc_jj/dv_s of the point) = sum_a2 Ss[a][a2] LF[jj][a2]
+    lds_sync();
+    if (lane < RM * X) {
+      const int jj = lane / X, a = lane - jj * X;
+      double tt = 0.0;
+      if (jprev < bd.nobs) {
+        const double* lf = LamF + jj * X;  // (the point's own frame, still in LamF at this point of the flush)
 #pragma unroll
-          for (int a2 = 0; a2 < X; ++a2) tt += Ss[a * X + a2] * lf[a2];
-        }
-        Ys[lane] = tt;
+        for (int a2 = 0; a2 < X; ++a2) tt += Ss[a * X + a2] * lf[a2];
       }
+      Ys[lane] = tt;
     }
 #pragma unroll
     for (int i = 0; i < X * Z; ++i) {
@@ -804,17 +766,15 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
       Wacc[i] = 0.0;
     }
     lds_sync();
-    if constexpr (STATE) {
-      // the swept interval's sums for the forward grad-log-det sweep (k_gld_fwd_qx): Ss = sum T T^T, Ws = sum PE Zf, Pt,
-      // in k_newton_ivl's layout
-      if (jprev < bd.nobs && w.ivl) {
-        double* iv = w.ivl + (cb * sy.NOBS + jprev) * CHMC_IVL_N(X, Z);
-        if (lane < X * X) iv[lane] = Ss[lane];
-        if (lane < X * Z) iv[X * X + lane] = Ws[lane];
-        if (lane == 0) {
+    // the swept interval's sums for the forward grad-log-det sweep (k_gld_fwd_qx): Ss = sum T T^T, Ws = sum PE Zf, Pt,
+    // in k_newton_ivl's layout
+    if (jprev < bd.nobs && w.ivl) {
+      double* iv = w.ivl + (cb * sy.NOBS + jprev) * CHMC_IVL_N(X, Z);
+      if (lane < X * X) iv[lane] = Ss[lane];
+      if (lane < X * Z) iv[X * X + lane] = Ws[lane];
+      if (lane == 0) {
 #pragma unroll
-          for (int i = 0; i < X * X; ++i) iv[X * X + X * Z + i] = Pf[i];
-        }
+        for (int i = 0; i < X * X; ++i) iv[X * X + X * Z + i] = Pf[i];
       }
     }
     double nl = 0.0;  // entry `lane` of the rows at the start of the swept interval, LamF Pf
@@ -850,7 +810,7 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
   };
   const int ntile = (S + 63) >> 6;
   struct Raw {
-    double x[X], v[V], jp[NJP];
+    double x[X], v[V];
     bool valid;
   };
   auto fetch = [&](int tt, Raw& r) {
@@ -863,33 +823,11 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
       for (int a = 0; a < X; ++a) r.x[a] = ld_stream(traj + (size_t)s * X + a);
 #pragma unroll
       for (int a = 0; a < V; ++a) r.v[a] = vbase[(size_t)s * V + a];
-      const size_t col = colb + (size_t)s * V;
-      if constexpr (STATE) {
-        r.jp[0] = 0.0;
-      } else if constexpr (PBJ) {
-#pragma unroll
-        for (int k = 0; k < X * V; ++k) r.jp[k] = ld_stream(PBr + (size_t)s * (X * V) + k);
-      } else
-      // Observation row i is structurally zero in the intervals after its own (jj > i): those entries are zeros in HBM.
-      // Branching around their loads would break the load pipelining, so the loads stay and are pointed at a small block
-      // of zeros that lives in the caches: same instructions, 2 of 7 rows' bytes less HBM traffic.
-#pragma unroll
-      for (int i = 0; i < RM; ++i) {
-#if 1  // (zero-block loads: -17 % HBM bytes, -1.7 % time)
-        const double* src = (i < jj && i < bd.ny) ? w.zeros + 2 * lane : Jr + (size_t)i * NV + col;
-#else
-        const double* src = Jr + (size_t)i * NV + col;
-#endif
-#pragma unroll
-        for (int d = 0; d < V; ++d) r.jp[i * V + d] = ld_stream(src + d);
-      }
     } else {
 #pragma unroll
       for (int a = 0; a < X; ++a) r.x[a] = 0.0;
 #pragma unroll
       for (int a = 0; a < V; ++a) r.v[a] = 0.0;
-#pragma unroll
-      for (int i = 0; i < NJP; ++i) r.jp[i] = 0.0;
     }
   };
   Raw r0, r1;
@@ -911,9 +849,7 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
         if (lane < X) LamF[(bd.ny + lane) * X + lane] = 1.0;
       }
       lds_sync();
-      if constexpr (STATE) {  // the frame of interval j (Slots::LF)
-        if (lane < RM * X) LFo[(size_t)j * RM * X + lane] = LamF[lane];
-      }
+      if (lane < RM * X) LFo[(size_t)j * RM * X + lane] = LamF[lane];  // the frame of interval j (Slots::LF)
     }
     double A[X * X], Bm[X * V], Zf[X * Z];
     if (r0.valid) {
@@ -951,48 +887,26 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
         for (int e = 0; e < X; ++e) tt2 += PE[a * X + e] * Zf[e * Z + mz];
         Wacc[a * Z + mz] = tt2;
       }
-    if constexpr (STATE) {
-      if (r0.valid) {  // PB[s] = T_s: the compact form of this step's rows (Slots::PB)
-        const int off0 = (t << 6) + (63 - lane);
-        double* dst = PBo + (size_t)(j * S + off0) * (X * V);
-        if ((X * V) % 2 == 0) {
+    if (r0.valid) {  // PB[s] = T_s: the compact form of this step's rows (Slots::PB)
+      const int off0 = (t << 6) + (63 - lane);
+      double* dst = PBo + (size_t)(j * S + off0) * (X * V);
+      if ((X * V) % 2 == 0) {
 #pragma unroll
-          for (int k = 0; k + 1 < X * V; k += 2) st_async2(dst + k, T[k], T[k + 1]);
-        } else {
+        for (int k = 0; k + 1 < X * V; k += 2) st_async2(dst + k, T[k], T[k + 1]);
+      } else {
 #pragma unroll
-          for (int k = 0; k < X * V; ++k) st_async(dst + k, T[k]);
-        }
+        for (int k = 0; k < X * V; ++k) st_async(dst + k, T[k]);
       }
-#pragma unroll
-      for (int a = 0; a < X; ++a)
-#pragma unroll
-        for (int a2 = 0; a2 < X; ++a2) {
-          double tt2 = Yacc[a * X + a2];
-#pragma unroll
-          for (int d = 0; d < V; ++d) tt2 += T[a * V + d] * T[a2 * V + d];
-          Yacc[a * X + a2] = tt2;
-        }
-    } else if constexpr (PBJ) {
-#pragma unroll
-      for (int a = 0; a < X; ++a)
-#pragma unroll
-        for (int a2 = 0; a2 < X; ++a2) {
-          double tt2 = Yacc[a * X + a2];
-#pragma unroll
-          for (int d = 0; d < V; ++d) tt2 += T[a * V + d] * r0.jp[a2 * V + d];
-          Yacc[a * X + a2] = tt2;
-        }
-    } else {
-#pragma unroll
-      for (int jj = 0; jj < RM; ++jj)
-#pragma unroll
-        for (int a = 0; a < X; ++a) {
-          double tt2 = Yacc[jj * X + a];
-#pragma unroll
-          for (int d = 0; d < V; ++d) tt2 += T[a * V + d] * r0.jp[jj * V + d];
-          Yacc[jj * X + a] = tt2;
-        }
     }
+#pragma unroll
+    for (int a = 0; a < X; ++a)
+#pragma unroll
+      for (int a2 = 0; a2 < X; ++a2) {
+        double tt2 = Yacc[a * X + a2];
+#pragma unroll
+        for (int d = 0; d < V; ++d) tt2 += T[a * V + d] * T[a2 * V + d];
+        Yacc[a * X + a2] = tt2;
+      }
     {
       double Pn[X * X];
       matmul_xx<X>(Pf, I0, Pn);
@@ -1012,8 +926,8 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
       for (int d = 0; d < V0; ++d) {
         double j0 = 0.0, j1 = 0.0;
         for (int a = 0; a < X; ++a) j0 += LamF[i * X + a] * dv0[a * V0 + d], j1 += LamF[jj * X + a] * dv0[a * V0 + d];
-        tt += j0 * (STATE ? j1 : Jr[(size_t)jj * NV + d]);
-        if (STATE && jj == 0) pick(sl.Jv, sl_)[(size_t)c * RM * NV + (size_t)i * NV + d] = j0;  // the rows' v_0 columns
+        tt += j0 * j1;
+        if (jj == 0) Jo[(size_t)i * NV + d] = j0;  // the rows' v_0 columns
       }
       Dl[lane] = tt;
     }
@@ -1035,8 +949,7 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
     double v = Dl[lane];
     if (i == jj) {
       const double sg_ = sy.noisy ? sigma_at(sy, q) : 0.0;
-      if (sy.noisy && i < bd.ny) v += sg_ * sigma_at(sy, pick(sl.q, sl_) + (size_t)c * sy.Q);  // dc_dn_l * dc_dn_r (:772-791)
-      // (STATE: q is the slot's own point, so this is sigma^2)
+      if (sy.noisy && i < bd.ny) v += sg_ * sigma_at(sy, pick(sl.q, sl_) + (size_t)c * sy.Q);  // dc_dn dc_dn^T (:772-791)
       if (i >= bd.nrows) v = 1.0;
     }
     w.Dw[cb * RM * RM + lane] = v;
@@ -1056,11 +969,9 @@ __global__ void __launch_bounds__(64, (PBJ && M::X * M::V <= 4) ? CHMC_LEAN_WAVE
     } else {
       tt = i < bd.ny ? sigma_at(sy, q) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
     }
-    (STATE ? pick(sl.JuP, sl_) : w.JuL)[cb * RM * U + e] = tt;
+    pick(sl.JuP, sl_)[cb * RM * U + e] = tt;
   }
-  if constexpr (STATE) {
-    for (int e = lane; e < RM * Z; e += 64) w.zbP[cb * RM * Z + e] = zl[e];
-  }
+  for (int e = lane; e < RM * Z; e += 64) w.zbP[cb * RM * Z + e] = zl[e];
 }
 
 // The body of k_newton_factor_wave for the block (c, b) on the 16 lanes r = lane & 15 of a 16-lane group (act: this group has a
@@ -1275,7 +1186,7 @@ __device__ __forceinline__ void newton_factor16(const Sys& sy, const Slots& sl, 
 }
 
 // The Newton-iteration sweep in two phases, for layouts with FEW, LONG blocks (SIR single block: B wavefronts of
-// k_newton_lean would each walk the whole chain, 300 us of pure latency per launch however few chains are active).
+// a one-phase sweep would each walk the whole chain, 300 us of pure latency per launch however few chains are active).
 // With the compact rows nothing in the hot loop depends on the adjoint rows, so the observation intervals of a block
 // are independent up to three small matrices each:
 //   phase A  k_newton_ivl : one wavefront per (chain, block, INTERVAL m): the wave's sums over the interval's steps
@@ -1284,14 +1195,14 @@ __device__ __forceinline__ void newton_factor16(const Sys& sy, const Slots& sl, 
 //            interval) -> work.ivl;
 //   phase B  k_newton_comb: one wavefront per (chain, block) walks the intervals backwards with everything RM-sized in
 //            LDS -- frame LamF[m] = rows injected at the interval's end + LamF[m+1] Pt[m+1];
-//            Gram += LamF[m] Ss[m] LFprev[m]^T;  dc/dz rows += LamF[m] Ws[m] -- and finishes as k_newton_lean does
+//            Gram += LamF[m] Ss[m] LFprev[m]^T;  dc/dz rows += LamF[m] Ws[m] -- and finishes as k_state_lean does
 //            (v_0 columns, observation-noise diagonal, identity padding, dc/du rows through generate_z').
 // Any RM <= 16: no per-lane array is indexed by the row.
 // (166 VGPRs for FitzHugh-Nagumo: three wavefronts per SIMD at run time; capped at 128 for four it spills, 3x slower)
 #ifndef CHMC_IVL_WAVES
 #define CHMC_IVL_WAVES 2
 #endif
-// STATE (both phases): the state evaluation of slot `which` in the same two phases (k_newton_lean<.., STATE> for blocks of
+// STATE (both phases): the state evaluation of slot `which` in the same two phases (k_state_lean for blocks of
 // any RM <= 16): phase A also WRITES the compact rows PB[s] = T_s and sums T_s T_s^T; phase B writes the frames LF[m], the
 // symmetric Gram block, the rows' v_0 columns, the dc/du rows of the slot and the dc/dz rows (work.zbP).
 // newton_ivl_body: the sums of observation interval m of block (c, b) by the calling wavefront (which / qsel already
@@ -2526,12 +2437,11 @@ __global__ void __launch_bounds__(256) k_jw_pb(Sys sy, Slots sl, Work w, int whi
 // PBJ (both sweeps): the stored rows are read in their compact form (Slots::PB / LF).  The weights w_i = sum_jj
 // (G^-1)_i,jj dc_jj/dv_s are then  MLF[m][i] . PB[s]  with the per-interval RM x X matrix MLF[m] = (G^-1)_bb LF[m]
 // (wave-uniform, formed once per interval): X V doubles per step instead of RM V, RM X V multiply-adds instead of RM RM V.
-// QX (with PBJ): instead of the tangents the sweep stores Qx_s = sum_i LF[m][i]^T xd_i(s)^T (X x X per step), which is all
-// the row-free backward sweep k_gld_bwd_lean needs of them.
+// Only the forward sweep has that form: blocks of at most 8 rows on the compact rows run k_gld_fwd_qx + k_gld_bwd_lean.
 #ifndef CHMC_GLD_FWD_DPP_MAXROWS
 #define CHMC_GLD_FWD_DPP_MAXROWS 16
 #endif
-template <class M, int RM, bool PBJ = false, bool QX = false>
+template <class M, int RM, bool PBJ = false>
 __global__ void __launch_bounds__(256) k_gld_fwd_wave(Sys sy, Slots sl, Work w, int which) {
   constexpr int X = M::X, V = M::V, Z = M::Z, V0 = M::V0;
   constexpr int URM = 64;  // (the forward sweep is correct fully unrolled at 16 rows as well; the backward sweep is not, see there)
@@ -2565,7 +2475,7 @@ __global__ void __launch_bounds__(256) k_gld_fwd_wave(Sys sy, Slots sl, Work w, 
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   ChainConsts<M> cc;
   cc.init(q, sy.dl);
-  double mlf[PBJ ? RM * X : 1], lf[QX ? RM * X : 1];
+  double mlf[PBJ ? RM * X : 1];
   double xdc[RM * X];  // tangents at the start of the current tile (wave-uniform)
 #pragma unroll URM
   for (int i = 0; i < RM * X; ++i) xdc[i] = 0.0;
@@ -2601,10 +2511,6 @@ __global__ void __launch_bounds__(256) k_gld_fwd_wave(Sys sy, Slots sl, Work w, 
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int e2 = 0; e2 < RM * X; ++e2) mlf[e2] = MLFs[e2];
-      if constexpr (QX) {
-#pragma unroll
-        for (int e2 = 0; e2 < RM * X; ++e2) lf[e2] = LFr[(size_t)j * RM * X + e2];
-      }
     }
     for (int t = 0; t < ntile; ++t) {
       const int off = (t << 6) + lane;
@@ -2716,19 +2622,6 @@ __global__ void __launch_bounds__(256) k_gld_fwd_wave(Sys sy, Slots sl, Work w, 
             for (int d = 0; d < X; ++d) tt += Pex[a * X + d] * xdc[i * X + d];
             xs[i * X + a] = tt;
           }
-        if constexpr (QX) {
-          if (valid) {
-#pragma unroll
-            for (int a1 = 0; a1 < X; ++a1)
-#pragma unroll
-              for (int a2 = 0; a2 < X; ++a2) {
-                double tt = 0.0;
-#pragma unroll
-                for (int i = 0; i < RM; ++i) tt += (i >= j && i < bd.nrows) ? lf[i * X + a1] * xs[i * X + a2] : 0.0;
-                st_async(Xd + (size_t)(a1 * X + a2) * TS + s, tt);
-              }
-          }
-        } else
         if (valid) {  // the tangent of row i is only needed up to that row's own observation time
 #pragma unroll URM
           for (int i = 0; i < RM; ++i)
@@ -2772,7 +2665,7 @@ __global__ void __launch_bounds__(256) k_gld_fwd_wave(Sys sy, Slots sl, Work w, 
 // X pseudo-rows instead of RM rows:
 //     Qx_{s+1}[r] = A_s Qx_s[r] + B_s (PB_s^T C1_m[r]) + Zf_s C2_m[r],   C1_m = LF[m]^T MLF[m] (X x X),  C2_m = LF[m]^T zd (X x Z),
 // started at the interval's first step from Q0_m = LF[m]^T xd(t_m).  The row tangents are only needed at the interval
-// boundaries, where they follow from the state sweep's interval sums (k_newton_lean<.., STATE> leaves Ss, Ws, Pt in work.ivl):
+// boundaries, where they follow from the state sweep's interval sums (k_state_lean leaves Ss, Ws, Pt in work.ivl):
 //     xd_i(t_{m+1}) = Pt_m xd_i(t_m) + Ss_m MLF[m][i]^T + Ws_m zd_i
 // -- a prologue of nobs tiny steps per block (entries over the lanes, everything RM-sized in LDS).  The affine scan of a
 // tile then carries X instead of RM vectors (FitzHugh-Nagumo: 2 instead of 7).  Also writes the rows' terminal tangents
@@ -2980,19 +2873,13 @@ __global__ void __launch_bounds__(256) k_gld_fwd_qx(Sys sy, Slots sl, Work w, in
   }
 }
 
-// (two wavefronts per SIMD for the backward sweep: 256 VGPRs + 344 bytes of scratch, 1.07 -> 1.80 ms per step: not used)
-#ifndef CHMC_GLD_BWD_WAVES
-#define CHMC_GLD_BWD_WAVES 1
-#endif
-template <class M, int RM, bool PBJ = false>
-__global__ void __launch_bounds__(PBJ && CHMC_GLD_BWD_WAVES > 1 ? 64 : 256, PBJ ? CHMC_GLD_BWD_WAVES : 1) k_gld_bwd_wave(Sys sy, Slots sl, Work w, int which) {
+// The backward sweep over the stored rows (the compact rows' backward sweep is k_gld_bwd_lean; 16-row blocks:
+// k_gld_bwd_wave_ldsrows).
+template <class M, int RM>
+__global__ void __launch_bounds__(256, 1) k_gld_bwd_wave(Sys sy, Slots sl, Work w, int which) {
   constexpr int X = M::X, V = M::V, Z = M::Z, U = M::U, V0 = M::V0, NXI = M::NXI;
-#ifdef CHMC_GLD_BWD_URM16
-  constexpr int URM = RM <= 8 ? 64 : CHMC_GLD_BWD_URM16;  // (experiments on the 16-row instantiation)
-#else
   constexpr int URM = RM <= 8 ? 64 : 1;
-#endif
-  __shared__ double sm[4][RM * RM + RM * Z + (PBJ ? RM * X : 0)];
+  __shared__ double sm[4][RM * RM + RM * Z];
   const int lane = threadIdx.x & 63;
   const int wv_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wid = blockIdx.x * (blockDim.x >> 6) + wv_;
@@ -3014,10 +2901,6 @@ __global__ void __launch_bounds__(PBJ && CHMC_GLD_BWD_WAVES > 1 ? 64 : 256, PBJ 
   double* gv = pick(sl.grad, s_) + (size_t)c * sy.Q + sy.U;
   double* Mb = sm[wv_];
   double* zd = sm[wv_] + RM * RM;
-  double* MLFs = sm[wv_] + RM * RM + RM * Z;
-  const double* PBr = PBJ ? pick(sl.PB, s_) + ((size_t)c * TS + bd.step0) * (X * V) : nullptr;
-  const double* LFr = PBJ ? pick(sl.LF, s_) + cb * sy.NOBS * RM * X : nullptr;
-  double mlf[PBJ ? RM * X : 1];
   for (int i = lane; i < RM * RM; i += 64) Mb[i] = w.gMb[cb * RM * RM + i];
   for (int i = lane; i < RM * Z; i += 64) zd[i] = w.gzd[cb * RM * Z + i];
   __builtin_amdgcn_wave_barrier();
@@ -3053,20 +2936,6 @@ __global__ void __launch_bounds__(PBJ && CHMC_GLD_BWD_WAVES > 1 ? 64 : 256, PBJ 
         for (int a = 0; a < X; ++a)
           if (i == bd.ny + a) Lam[i * X + a] = 1.0;
     }
-    if constexpr (PBJ) {  // MLF[j] = (G^-1)_bb LF[j]
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      if (lane < RM * X) {
-        const int i = lane / X, a = lane - i * X;
-        double t2 = 0.0;
-        for (int jj = 0; jj < RM; ++jj) t2 += Mb[i * RM + jj] * LFr[((size_t)j * RM + jj) * X + a];
-        MLFs[lane] = t2;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int e2 = 0; e2 < RM * X; ++e2) mlf[e2] = MLFs[e2];
-    }
     for (int t = ntile - 1; t >= 0; --t) {
       const int off = (t << 6) + (63 - lane);  // LATER steps in LOWER lanes: the suffix scans become DPP prefix scans
       const bool valid = off < S;
@@ -3100,17 +2969,12 @@ __global__ void __launch_bounds__(PBJ && CHMC_GLD_BWD_WAVES > 1 ? 64 : 256, PBJ 
         double Sm[X * NXI];
 #pragma unroll
         for (int i = 0; i < X * NXI; ++i) Sm[i] = 0.0;
-        double jp[PBJ ? X * V : RM * V];
-        if constexpr (PBJ) {
-#pragma unroll
-          for (int k = 0; k < X * V; ++k) jp[k] = valid ? ld_stream(PBr + (size_t)s * (X * V) + k) : 0.0;
-        } else {
+        double jp[RM * V];
 #pragma unroll URM
-          for (int i = 0; i < RM; ++i) {
-            const bool act = valid && i >= j && i < bd.nrows;
+        for (int i = 0; i < RM; ++i) {
+          const bool act = valid && i >= j && i < bd.nrows;
 #pragma unroll
-            for (int d = 0; d < V; ++d) jp[i * V + d] = act ? Jv[(size_t)i * NV + col + d] : 0.0;
-          }
+          for (int d = 0; d < V; ++d) jp[i * V + d] = act ? Jv[(size_t)i * NV + col + d] : 0.0;
         }
 #pragma unroll URM
         for (int i = 0; i < RM; ++i) {
@@ -3127,13 +2991,8 @@ __global__ void __launch_bounds__(PBJ && CHMC_GLD_BWD_WAVES > 1 ? 64 : 256, PBJ 
 #pragma unroll
           for (int d = 0; d < V; ++d) {
             double tt = 0.0;
-            if constexpr (PBJ) {
-#pragma unroll
-              for (int a = 0; a < X; ++a) tt += mlf[i * X + a] * jp[a * V + d];
-            } else {
 #pragma unroll URM
-              for (int jj = 0; jj < RM; ++jj) tt += Mb[i * RM + jj] * jp[jj * V + d];
-            }
+            for (int jj = 0; jj < RM; ++jj) tt += Mb[i * RM + jj] * jp[jj * V + d];
             dir[X + d] = tt;
           }
 #pragma unroll

@@ -1,7 +1,7 @@
 """Layouts at the edges of the kernel plan (csrc/chmc_plan.h) against the C oracle, on the GPU:
 
   * more than 64 blocks per chain: a Newton round is k_newton_ivl + k_newton_comb, KNewtonFactor, the lane-per-chain
-    KSolveChain (the `else` of CHMC_SOLVE_CHAIN) and KMuF as launches of their own, and all six call sites of the
+    KSolveChain (the K > 64 arm of solve_chain()) and KMuF as launches of their own, and all six call sites of the
     chain solve take KSolveChain;
   * exactly 64 blocks per chain: every lane of k_newton_fsm_wave / k_solve_chain_wave owns a block;
   * K = [64, 65]: one context switches between the two paths, per-block arrays strided by Kmax = 65;
@@ -158,7 +158,7 @@ def test_block_count_boundary(name):
 @pytest.mark.parametrize("name", list(TILE_EDGE))
 def test_tile_boundary(name):
     """S = 63, 64, 65 and 128 steps per observation: the last 64-lane tile of an interval one lane short, full, one lane
-    over (k_newton_ivl, k_gld_*_ivl, k_newton_lean, k_gld_fwd_qx / k_gld_bwd_lean, k_jw_pb)."""
+    over (k_newton_ivl, k_gld_*_ivl, k_state_lean, k_gld_fwd_qx / k_gld_bwd_lean, k_jw_pb)."""
     _hip()
     cfg = CASES[name]
     case = build_case(cfg)

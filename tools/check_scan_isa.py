@@ -128,7 +128,7 @@ def check_kernel(name, body):
     return problems
 
 
-NO_SPILL = ("k_newton_leanINS_8FhnModelELi7ELb0", "k_rev_waveINS_8FhnModelELi7E", "k_gld_fwd_waveINS_8FhnModelELi7E",
+NO_SPILL = ("k_rev_waveINS_8FhnModelELi7E", "k_gld_fwd_waveINS_8FhnModelELi7E",
             "k_gld_bwd_waveINS_8FhnModelELi7E", "k_gld_fwd_qxINS_8FhnModelELi7E")  # the hot instantiations of the headline configuration
 
 
@@ -178,7 +178,7 @@ def main():
             continue  # (its stores belong to the helper wavefront and are waited for by the compiler; audited above)
         e = next(i for i in range(s, len(lines)) if lines[i].strip().startswith((".amdhsa_kernel", ".section")))
         probs, n_st, n_scr = audit_stores(name, lines[s:e])
-        if not n_st and "k_newton_lean" not in name and not any(k in name for k in NO_SPILL):
+        if not n_st and "k_state_lean" not in name and not any(k in name for k in NO_SPILL):
             continue
         n_audit += 1
         print(("FAIL " if probs else "ok   ") + f"{name}  [{n_st} untracked stores, {n_scr} scratch instructions]")

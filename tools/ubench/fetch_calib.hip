@@ -21,7 +21,7 @@ __global__ void __launch_bounds__(256) calib_coalesced_16B(const d2_t* a, double
   if (v.x + v.y == 1.2345e301) sink[0] = v.x;
 }
 // (b) 8 B per lane coalesced: a wavefront reads 512 contiguous bytes per instruction (the wave-scan kernels'
-//     per-step loads: k_newton_ivl, k_newton_lean, k_gld_*, k_jw_pb with X V = 4 read 8 B per lane and operand)
+//     per-step loads: k_newton_ivl, k_state_lean, k_gld_*, k_jw_pb with X V = 4 read 8 B per lane and operand)
 __global__ void __launch_bounds__(256) calib_coalesced_8B(const double* a, double* sink, long n) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
