@@ -109,6 +109,12 @@ def step_job(spec, q, p, x_obs, part, dt, newton, n_inner, project):
     return out
 
 
+def nld_job(spec, q, gaussian):
+    """Value and gradient of the unconstrained comparator target (oracle/py/neg_log_dens.py) for one chain at q [U + NV]."""
+    from oracle.py.neg_log_dens import neg_log_dens_and_grad
+    return neg_log_dens_and_grad(spec["model"], spec["obs_interval"], spec["S"], spec["y"], spec["sigma"], q, bool(gaussian))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # submitting side
 
