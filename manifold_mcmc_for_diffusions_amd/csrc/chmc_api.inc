@@ -221,119 +221,14 @@ static void dispatch(const chmc_ctx* ctx, F&& f) {
 }
 
 // Kernel families, environment switches and the choice of a kernel per pass: chmc_plan.h.  chmc_create decides the plan, every
-// entry point refreshes the part that hangs on a per-call switch (CHMC_ENTER), the launch sites below switch on it.
+// entry point refreshes the part that hangs on a per-call switch (CHMC_ENTER), the passes (chmc_passes.inc) switch on it.
 static const PartitionPlan& part_plan(const chmc_ctx* c) { return c->plan.part[c->part]; }
 static void refresh_plan(chmc_ctx* c) {
   c->plan_in.call = read_switches();
   c->plan = make_plan(c->plan_in);
 }
-// chain-level Woodbury solve: one wavefront per chain up to 64 blocks
-template <class M, int RM, int SYM, int TGT>
-static void solve_chain(const Sys& sy, const Slots& sl, const Work& w, int which, int qsel, int psel) {
-#ifdef CHMC_WAVE_KERNELS
-  if (sy.K <= 64) {
-    launch_wave(k_solve_chain_wave<M, RM, SYM, TGT>, (long)sy.B, 5, sy, sl, w, which, qsel, psel);
-    return;
-  }
-#endif
-  launch(KSolveChain<M, RM, SYM, TGT>{sy, sl, w, which, qsel, psel}, sy.B, 5);
-}
-
-#ifdef CHMC_WAVE_KERNELS
-// time-parallel forward scan (k_fwd_par) on `waves` wavefronts per workgroup (par_waves_for / CHMC_CHAIN_SCAN_WAVES: 1, 2 or 4)
-template <class M, int RM, class... Args>
-static void fwd_par(int waves, long n, Args... args) {
-  if (waves == 4)
-    launch_blocks(k_fwd_par<M, RM, 4>, n, 256, 7, args...);
-  else if (waves == 2)
-    launch_blocks(k_fwd_par<M, RM, 2>, n, 128, 7, args...);
-  else
-    launch_blocks(k_fwd_par<M, RM, 1>, n, 64, 7, args...);
-}
-#endif
-// forward scan (KernelPlan::fwd); gsel: guess trajectory for the time-parallel scan (k_fwd_par; 0: none available ->
-// sequential scan, KernelPlan::fwd_cold)
-// (Measured and rejected for the sequential scan, round 3: giving every scan workgroup a CU of its own with 56 KB of dynamic
-// LDS padding -- 512 chains, S = 800: 439 against 392 us per scan.  The scan's time doubles from 80 to 160 wavefronts because
-// it is then bound by the memory system, not by two wavefronts sharing a SIMD: 10 240 lanes x 32 B per step in 128-byte lines
-// that belong to 64 different streams per wave instruction = 2.8-3.3 TB/s, DESIGN.md section 4.)
-template <class M, int RM>
-static void fwd(chmc_ctx* c, int which, int qsel, int use_nw, int store, int gsel) {
-  const Sys& sy = c->sy;
-#ifdef CHMC_WAVE_KERNELS
-  stagger_wait();  // half-batches: this half's scan runs after the other half's latest one
-  const FwdScan scan = gsel != 0 ? c->plan.fwd : c->plan.fwd_cold;
-  if (scan == FwdPar) {
-    // few long blocks: Newton on the trajectory, one wavefront per (chain, block); a scan that stores nothing
-    // (quasi-Newton) iterates on the work trajectory
-    fwd_par<M, RM>(c->plan.fwd_waves, (long)sy.B * sy.K, sy, c->sl, c->w, which, qsel, use_nw, store ? store : 2, gsel, c->round);
-  } else if (scan == FwdWave) {
-    if (store)
-      launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B * sy.K + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sy, c->sl, c->w, which,
-                    qsel, use_nw, store, c->w, 0, 0);
-    else
-      launch_blocks(k_fwd_scan<M, RM, false>, ((long)sy.B * sy.K + 63) / 64, 64, 7, sy, c->sl, c->w, which, qsel, use_nw, store,
-                    c->w, 0, 0);
-  } else {
-    launch(KFwd<M, RM>{sy, c->sl, c->w, which, qsel, use_nw, store}, (long)sy.B * sy.K, 7);
-  }
-  stagger_record();
-#else
-  (void)gsel;
-  launch(KFwd<M, RM>{sy, c->sl, c->w, which, qsel, use_nw, store}, (long)sy.B * sy.K, 7);
-#endif
-}
-// ... of the chains in the Newton loops of two problems, c->w and w1, with the same (which, qsel): ONE launch of twice the
-// workgroups (the lock-step round path never scans in parallel in time: KernelPlan::pair_retractions)
-template <class M, int RM>
-static void fwd_pair(chmc_ctx* c, const Work& w1, int which, int qsel, int store) {
-  const Sys& sy = c->sy;
-#ifdef CHMC_WAVE_KERNELS
-  if (c->plan.fwd_cold == FwdWave) {
-    const long wg = ((long)sy.B * sy.K + 63) / 64;
-    if (store)
-      launch_blocks(k_fwd_scan<M, RM, true, true>, 2 * wg, 64 * (1 + CHMC_SCAN_HELPERS), 7, sy, c->sl, c->w, which, qsel, 1, store,
-                    w1, which, qsel);
-    else
-      launch_blocks(k_fwd_scan<M, RM, false, true>, 2 * wg, 64, 7, sy, c->sl, c->w, which, qsel, 1, store, w1, which, qsel);
-    return;
-  }
-#endif
-  // (and the host emulation: two functor launches in place of the merged one)
-  launch(KFwd<M, RM>{sy, c->sl, c->w, which, qsel, 1, store}, (long)sy.B * sy.K, 7);
-  launch(KFwd<M, RM>{sy, c->sl, w1, which, qsel, 1, store}, (long)sy.B * sy.K, 7);
-}
-
-// J^T lambda from the compact rows: mu_F (KMuF), then the column pass (KUpdatePB), one step per work item; a full launch
-// moves 0.66 GB in 125 us = 5.2 TB/s, the streaming rate of this part.
-template <class M, int RM, int TGT>
-static void mu_f(chmc_ctx* c, int which) {
-  const Sys& sy = c->sy;
-  launch(KMuF<RM, M::X, TGT>{sy, c->sl, c->w, which}, (long)sy.B * sy.K * sy.NOBS * M::X, 5);
-}
-// (flow_rev, fwd_qb, fwd_hfrac: KUpdatePB's members of those names, with its defaults)
-template <class M, int RM, int TGT>
-static void update_pb_columns(chmc_ctx* c, int which, int qsel, int psel, int flow_rev = 0, double* fwd_qb = nullptr,
-                              double fwd_hfrac = 0.0) {
-  const Sys& sy = c->sy;
-  launch_colmax(KUpdatePB<RM, M::X, M::V, TGT>{sy, c->sl, c->w, which, qsel, psel, flow_rev, fwd_qb, fwd_hfrac},
-                sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0), sy.B, 4);
-}
-template <class M, int RM, int TGT>
-static void update_pb(chmc_ctx* c, int which, int qsel, int psel, int flow_rev = 0, double* fwd_qb = nullptr,
-                      double fwd_hfrac = 0.0) {
-  mu_f<M, RM, TGT>(c, which);
-  update_pb_columns<M, RM, TGT>(c, which, qsel, psel, flow_rev, fwd_qb, fwd_hfrac);
-}
-
-// J^T lambda column pass over the stored rows: two columns per work item with 16-byte accesses when every offset is even
-template <int RM, int TGT>
-static void update(const Sys& sy, const Slots& sl, const Work& w, int which, int qsel, int psel) {
-  if (sy.Q % 2 == 0 && sy.NV % 2 == 0 && sy.U % 2 == 0 && sy.V0 % 2 == 0 && sy.V % 2 == 0 && sy.NCOL % 2 == 0)
-    launch_colmax(KUpdate<RM, TGT, 2>{sy, sl, w, which, qsel, psel}, sy.NCOL / 2, sy.B, 4);
-  else
-    launch_colmax(KUpdate<RM, TGT, 1>{sy, sl, w, which, qsel, psel}, sy.NCOL, sy.B, 4);
-}
+// One function per pass: the only text that differs between the library and the host emulation.
+#include "chmc_passes.inc"
 
 extern "C" const char* chmc_last_error(void) { return g_err.c_str(); }
 extern "C" const char* chmc_backend(void) { return CHMC_BACKEND_NAME; }
@@ -423,9 +318,7 @@ extern "C" int chmc_create(const chmc_config* cfg, chmc_ctx** out) {
       for (auto& bl : c->hblk[p]) in.longest = bl.nsteps > in.longest ? bl.nsteps : in.longest;
     in.chain_steps = sy.T * sy.S, in.s_tiles8 = sy.S % 8 == 0;
     in.V = sy.V, in.even_dims = !((sy.Q | sy.U | sy.V0 | sy.NV) & 1), in.gaussian = sy.gaussian;
-#ifdef CHMC_WAVE_KERNELS
-    in.wave_kernels = true;
-#endif
+    in.wave_kernels = kWaveKernels;
     in.sw = in.call = read_switches();
     c->plan = make_plan(in);
   }
@@ -508,7 +401,6 @@ static void begin_all(chmc_ctx* c, const double* d_dt, const int* d_active, doub
 // With the compact rows the state sweeps that need no stored rows do not write the rows of the step columns at all
 // (PartitionPlan::rebuild_rows): the per-operator entry points that hand rows to the caller rebuild them on demand.
 static void ensure_rows(chmc_ctx* c) {
-#ifdef CHMC_WAVE_KERNELS
   if (!part_plan(c).rebuild_rows || c->rows_fresh) return;
   const Sys& sy = c->sy;
   dispatch(c, [&](auto inst) {
@@ -516,102 +408,18 @@ static void ensure_rows(chmc_ctx* c) {
     launch(KRowsFromPB<decltype(inst)::RM, M::X, M::V>{sy, c->sl}, (long)sy.B * sy.T * sy.S, 2);
   });
   c->rows_fresh = true;
-#else
-  (void)c;
-#endif
 }
 static void state_eval_core(chmc_ctx* c, int which, bool with_grad = true, int traj_guess = 0) {
   const Sys& sy = c->sy;
-  const PartitionPlan& pp = part_plan(c);
-  (void)pp;
   c->rows_fresh = false;
   dispatch(c, [&](auto inst) {
     using M = typename decltype(inst)::M;
     constexpr int RM = decltype(inst)::RM;
-#ifdef CHMC_WAVE_KERNELS
     fwd<M, RM>(c, which, 0, 0, 1, traj_guess);
-    const long nbk = (long)sy.B * sy.K;
-    if constexpr (RM > 8) {
-      switch (pp.state) {
-        case StateIvlComb:  // few long 16-row blocks: interval-parallel sums, then one combine per block (compact rows only)
-          launch_blocks(k_newton_ivl<M, true>, nbk * sy.NOBS, 64, 2, sy, c->sl, c->w, which, 0);
-          launch_blocks(k_newton_comb<M, RM, true>, nbk, 64, 2, sy, c->sl, c->w, which, 0);
-          break;
-        case StateIvlCombWg:  // one block per chain: the per-chain kernels' combine (all threads) + 16-lane Cholesky, E, C_b
-          launch_blocks(k_newton_ivl<M, true>, nbk * sy.NOBS, 64, 2, sy, c->sl, c->w, which, 0);
-          launch_blocks(k_newton_comb_wg<M, RM, CHMC_RETRACT_WAVES, true>, (long)sy.B, 64 * CHMC_RETRACT_WAVES, 2, sy, c->sl,
-                        c->w, which, 0);
-          break;
-        case StateLdsrowsGramMfma:  // store the rows, then the Gram block from the stored rows
-          launch_blocks(k_rev_wave_ldsrows<M, RM, 0>, nbk, 64, 2, sy, c->sl, c->w, which, 0);
-          launch_blocks(k_gram_rows_mfma<RM>, nbk, 64, 2, sy, c->sl, c->w, which, 0, 0), c->diag[0]++;
-          break;
-        default:  // StateLdsrowsGram
-          launch_blocks(k_rev_wave_ldsrows<M, RM, 0>, nbk, 64, 2, sy, c->sl, c->w, which, 0);
-          launch_wave(k_gram_rows<RM, 4>, nbk * (RM / 4), 2, sy, c->sl, c->w, which, 0, 0), c->diag[1]++;
-      }
-    } else {
-      switch (pp.state) {
-        case StateLean:  // the state sweep at three wavefronts per SIMD (compact rows)
-          launch_blocks(k_state_lean<M, RM>, nbk, 64, 2, sy, c->sl, c->w, which);
-          break;
-        case StateRevStoreGramMfma:  // store the rows, then the Gram block from the stored rows on the matrix cores
-          launch_wave(k_rev_wave<M, RM, 0, false>, nbk, 2, sy, c->sl, c->w, which, 0);
-          launch_blocks(k_gram_rows_mfma<RM>, nbk, 64, 2, sy, c->sl, c->w, which, 0, 0), c->diag[0]++;
-          break;
-        default:  // StateRevWave
-          launch_wave(k_rev_wave<M, RM, 0>, nbk, 2, sy, c->sl, c->w, which, 0);
-      }
-    }
-    if (pp.state != StateIvlCombWg)  // (k_newton_comb_wg<.., STATE> has factored the block)
-      launch(KStateFactor<M, RM>{sy, c->sl, c->w, which}, nbk, 9);
-#else
-    launch(KStateBlk<M, RM>{sy, c->sl, c->w, which}, (long)sy.B * sy.K, 2);
-#endif
+    state_sweep<M, RM>(c, which);
     launch(KStateChain<M>{sy, c->sl, c->w, which}, sy.B);
     if (!with_grad) return;  // an inner h2-flow step that is not the last needs J and the Gram factors only (mici _step_b)
-#ifdef CHMC_WAVE_KERNELS
-    if constexpr (RM > 8)  // 16-row blocks: the block over 16 lanes (a 16 x 16 inverse per lane lives in scratch memory)
-      launch_blocks(k_gld_prep_wave<M, RM>, ((long)sy.B * sy.K + 3) / 4, 64, 9, sy, c->sl, c->w, which);
-    else
-      launch(KGldPrep<M, RM>{sy, c->sl, c->w, which}, (long)sy.B * sy.K, 9);
-    switch (pp.gld) {
-      case GldQxLean:  // blocks of at most 8 rows: row-free backward sweep on Qx written by the forward sweep
-        if constexpr (RM <= 8) {
-          // forward sweep on X pseudo-rows (Qx directly; the row tangents only at the interval boundaries, from the state
-          // sweep's interval sums in work.ivl)
-          launch_wave(k_gld_fwd_qx<M, RM>, nbk, 3, sy, c->sl, c->w, which);
-          launch_blocks(k_gld_bwd_lean<M, RM>, nbk, 64, 3, sy, c->sl, c->w, which);
-        }
-        break;
-      case GldIvl:  // few long 16-row blocks: the row-free sweeps, every observation interval on its own wavefront
-        if constexpr (RM > 8) {
-          const long niv = nbk * sy.NOBS;
-          launch_wave(k_gld_ivl_prologue<M, RM>, nbk, 3, sy, c->sl, c->w, which);
-          launch_wave(k_gld_fwd_ivl<M, RM>, niv, 3, sy, c->sl, c->w, which);
-          launch_wave(k_gld_bwd_ivl<M, RM, 0>, niv, 3, sy, c->sl, c->w, which);
-          launch_wave(k_gld_bwd_ivl<M, RM, 1>, niv, 3, sy, c->sl, c->w, which);
-          launch_blocks(k_gld_ivl_finish<M, RM>, (nbk + 63) / 64, 64, 3, sy, c->sl, c->w, which);
-        }
-        break;
-      case GldCompactFwdStored:  // 16-row blocks, large batches: the weights from the compact rows (DPP affine scan)
-        if constexpr (RM > 8) {
-          launch_wave(k_gld_fwd_wave<M, RM, true>, nbk, 3, sy, c->sl, c->w, which);
-          launch_wave(k_gld_bwd_wave_ldsrows<M, RM>, nbk, 3, sy, c->sl, c->w, which);
-        }
-        break;
-      case GldStored:
-        launch_wave(k_gld_fwd_wave<M, RM>, nbk, 3, sy, c->sl, c->w, which);
-        if constexpr (RM > 8) {
-          launch_wave(k_gld_bwd_wave_ldsrows<M, RM>, nbk, 3, sy, c->sl, c->w, which);
-        } else {
-          launch_wave(k_gld_bwd_wave<M, RM>, nbk, 3, sy, c->sl, c->w, which);
-        }
-        break;
-    }
-#else
-    launch(KGldBlk<M, RM>{sy, c->sl, c->w, which}, (long)sy.B * sy.K, 3);
-#endif
+    gld_sweeps<M, RM>(c, which);
     launch(KGldChain<M>{sy, c->sl, c->w, which}, sy.B);
   });
   c->counters[0]++, c->counters[1]++, c->counters[3]++, c->counters[4] += with_grad ? 1 : 0;
@@ -637,54 +445,7 @@ static void project_momentum_and_kick_direction(chmc_ctx* c, int which, bool ini
                                                 bool flow_rev = false, double* fwd_qb = nullptr, double fwd_hfrac = 0.0) {
   const Sys& sy = c->sy;
   if (init_pg) launch(KInitPg{sy, c->sl, c->w, which}, (long)sy.B * sy.Q, 8);
-#ifdef CHMC_WAVE_KERNELS
-  dispatch(c, [&](auto inst) {
-    using M = typename decltype(inst)::M;
-    constexpr int RM = decltype(inst)::RM;
-    // J p -> cpad, J pg -> cpad2 from one read of the compact rows (16-row blocks: PB / LF are written beside the stored
-    // rows; 9 instead of 48 doubles per step) or of the stored rows
-    const bool compact = c->plan.rows == RowsCompact;
-    switch (part_plan(c).jp) {
-      case JpPbWg:  // one block per chain: the interval sums over the wavefronts of a workgroup (k_traj_chain's form)
-        if constexpr (RM > 8)
-          launch_blocks(k_jw_pb_wg<RM, M::X, M::V, CHMC_RETRACT_WAVES>, (long)sy.B, 64 * CHMC_RETRACT_WAVES, 6, sy, c->sl, c->w,
-                        which);
-        break;
-      case JpPb:
-        if constexpr (RM <= 8 && M::V == 2) {
-          if (fix_in_jw) {
-            launch_wave(k_jw_pb<RM, M::X, M::V, true, true>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, 256);
-            break;
-          }
-        }
-        launch_wave(k_jw_pb<RM, M::X, M::V, true>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, 256);
-        break;
-      case JpWave:
-        launch_wave(k_jw_wave<RM, true>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, 256);
-        break;
-    }
-    // two Woodbury solves on views of the work arrays instead of copies between them: the first writes the multipliers of
-    // p straight into lampad2, the second takes J pg from cpad2
-    Work w1 = c->w, w2 = c->w;
-    w1.lampad = c->w.lampad2;
-    w2.cpad = c->w.cpad2;
-    launch(KSymBlk<M, RM>{sy, c->sl, w1, which, 0}, (long)sy.B * sy.K, 9);
-    solve_chain<M, RM, 1, 1>(sy, c->sl, w1, which, 0, 0);  // multipliers of p (and its u columns) -> lampad2
-    launch(KSymBlk<M, RM>{sy, c->sl, w2, which, 0}, (long)sy.B * sy.K, 9);
-    solve_chain<M, RM, 1, 1>(sy, c->sl, w2, which, 0, 3);  // multipliers of pg (and its u columns) -> lampad
-    if (compact && flow_rev) {
-      update_pb<M, RM, 3>(c, which, 0, 0, 1, fwd_qb, fwd_hfrac);
-    } else if (compact) {
-      update_pb<M, RM, 3>(c, which, 0, 0);
-    } else {
-      update<RM, 3>(sy, c->sl, c->w, which, 0, 0);
-    }
-  });
-#else
-  (void)fix_in_jw, (void)flow_rev, (void)fwd_qb, (void)fwd_hfrac;
-  project_momentum(c, which, 0, 0);
-  project_momentum(c, which, 4, 3);
-#endif
+  project_pair(c, which, fix_in_jw, flow_rev, fwd_qb, fwd_hfrac);
 }
 
 // p -= J^T G^-1 J p with J, G of slot `which`; p selected by (vsel, psel) (project_onto_cotangent_space :1243-1254)
@@ -693,22 +454,10 @@ static void project_momentum(chmc_ctx* c, int which, int vsel, int psel) {
   dispatch(c, [&](auto inst) {
     using M = typename decltype(inst)::M;
     constexpr int RM = decltype(inst)::RM;
-    const bool compact = c->plan.rows == RowsCompact;
-#ifdef CHMC_WAVE_KERNELS
-    if (compact)
-      launch_wave(k_jw_pb<RM, M::X, M::V>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, vsel | 256);
-    else
-      launch_wave(k_jw_wave<RM>, (long)sy.B * sy.K, 6, sy, c->sl, c->w, which, vsel | 256);  // J M^-1 p
-#else
-    launch(KJw<RM>{sy, c->sl, c->w, which, vsel | 256}, (long)sy.B * sy.K * RM, 6);
-#endif
+    jw<M, RM>(c, which, vsel | 256, c->plan.rows == RowsCompact);
     launch(KSymBlk<M, RM>{sy, c->sl, c->w, which, 0}, (long)sy.B * sy.K, 9);
     solve_chain<M, RM, 1, 1>(sy, c->sl, c->w, which, 0, psel);
-    if (compact) {
-      update_pb<M, RM, 1>(c, which, 0, psel);
-    } else {
-      update<RM, 1>(sy, c->sl, c->w, which, 0, psel);
-    }
+    jt_lambda<M, RM, 1>(c, which, 0, psel);
   });
 }
 
@@ -718,37 +467,13 @@ static void project_momentum(chmc_ctx* c, int which, int vsel, int psel) {
 // use_nw 1: the chains of the loop (work.nw).
 static void iteration_scan(chmc_ctx* c, int newton, int prev, int qsel, int fwd_guess, int use_nw) {
   dispatch(c, [&](auto inst) {
-    using M = typename decltype(inst)::M;
-    constexpr int RM = decltype(inst)::RM;
-    if (newton) {
-#ifdef CHMC_WAVE_KERNELS
-      fwd<M, RM>(c, prev ^ 1, qsel, use_nw, 2, fwd_guess);
-      c->diag[7]++;
-#endif  // (host emulation: KNewtonBlk integrates the iterate itself)
-    } else {
-      fwd<M, RM>(c, prev ^ 1, qsel, use_nw, 0, fwd_guess);
-      c->diag[7]++;
-    }
+    c->diag[7] += fwd<typename decltype(inst)::M, decltype(inst)::RM>(c, prev ^ 1, qsel, use_nw, newton ? 2 : 0, fwd_guess);
   });
 }
 // ... of the iterates of two problems with the same (prev, qsel), c->w and w1, in one launch
 static void iteration_scan_pair(chmc_ctx* c, int newton, int prev, int qsel, const Work& w1) {
   dispatch(c, [&](auto inst) {
-    using M = typename decltype(inst)::M;
-    constexpr int RM = decltype(inst)::RM;
-    if (newton) {
-#ifdef CHMC_WAVE_KERNELS
-      fwd_pair<M, RM>(c, w1, prev ^ 1, qsel, 2);
-      c->diag[7] += c->plan.fwd_cold == FwdWave ? 1 : 2;
-#endif
-    } else {
-      fwd_pair<M, RM>(c, w1, prev ^ 1, qsel, 0);
-#ifdef CHMC_WAVE_KERNELS
-      c->diag[7] += c->plan.fwd_cold == FwdWave ? 1 : 2;
-#else
-      c->diag[7] += 2;
-#endif
-    }
+    c->diag[7] += fwd_pair<typename decltype(inst)::M, decltype(inst)::RM>(c, w1, prev ^ 1, qsel, newton ? 2 : 0);
   });
   c->diag[6]++;
 }
@@ -758,78 +483,18 @@ static void iteration_scan_pair(chmc_ctx* c, int newton, int prev, int qsel, con
 // of 6, but update 116 -> 177 us per launch and 44.8 k -> 41.9 k steps/s; that code was removed, see docs/history.md.)
 static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel) {
   const Sys& sy = c->sy;
-  const NewtonSweep sweep = part_plan(c).newton;
-  // (these sweeps go on to factor the blocks, solve the chain's core system and form lambda and mu_F)
-  const bool solved = newton && (sweep == NewtonIvlFsm || sweep == Newton16IvlCombFactor || sweep == Newton16IvlCombWg);
   dispatch(c, [&](auto inst) {
     using M = typename decltype(inst)::M;
     constexpr int RM = decltype(inst)::RM;
+    bool solved = false;  // the sweep has solved the chain's core system and formed lambda and mu_F as well
     if (newton) {
-#ifdef CHMC_WAVE_KERNELS
-      const long nbk = (long)sy.B * sy.K;
-      if constexpr (RM > 8) {
-        switch (sweep) {
-          // two-phase sweep on the compact rows: interval-parallel sums, then one combine per block
-          case Newton16IvlCombWg:  // (the per-chain kernels' combine + LU on 16 lanes: the same bits as k_retract_chain)
-            launch_blocks(k_newton_ivl<M>, nbk * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
-            launch_blocks(k_newton_comb_wg<M, RM, CHMC_RETRACT_WAVES, false>, (long)sy.B, 64 * CHMC_RETRACT_WAVES, 1, sy,
-                          c->sl, c->w, prev, qsel);
-            break;
-          case Newton16IvlCombFactor:  // one block per chain (the SIR single-block layout)
-            launch_blocks(k_newton_ivl<M>, nbk * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
-            launch_blocks(k_newton_comb<M, RM, false, true>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
-            break;
-          case Newton16IvlComb:
-            launch_blocks(k_newton_ivl<M>, nbk * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
-            launch_blocks(k_newton_comb<M, RM>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
-            break;
-          case Newton16LdsrowsGramMfma:
-            launch_blocks(k_rev_wave_ldsrows<M, RM, 1>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
-            launch_blocks(k_gram_rows_mfma<RM>, nbk, 64, 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[0]++;
-            break;
-          default:  // Newton16LdsrowsGram
-            launch_blocks(k_rev_wave_ldsrows<M, RM, 1>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
-            launch_wave(k_gram_rows<RM, 4>, nbk * (RM / 4), 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[1]++;
-        }
-        // rows over 16 lanes (a 16 x 16 matrix per lane lives in scratch memory)
-        if (!solved) launch_blocks(k_newton_factor_wave<M, RM>, (nbk + 3) / 4, 64, 9, sy, c->sl, c->w, prev, qsel);
-      } else {
-        switch (sweep) {
-          // two phases (interval-parallel sums + per-block combine): 25 600 seven-tile wavefronts balance better over the
-          // SIMDs than 5 120 thirty-five-tile ones and the hot loop has no per-interval flush
-          case NewtonIvlFsm:
-          case NewtonIvlComb:
-            launch_blocks(k_newton_ivl<M>, nbk * sy.NOBS, 64, 1, sy, c->sl, c->w, prev, qsel);
-            launch_blocks(k_newton_comb<M, RM>, nbk, 64, 1, sy, c->sl, c->w, prev, qsel);
-            break;
-          case NewtonRevStoreGramMfma:  // the iterate's rows into work.JvW, Gram block against the stored rows by MFMA
-            launch_wave(k_rev_wave<M, RM, 1, false>, nbk, 1, sy, c->sl, c->w, prev, qsel);
-            launch_blocks(k_gram_rows_mfma<RM>, nbk, 64, 1, sy, c->sl, c->w, prev, 1, qsel), c->diag[0]++;
-            break;
-          default:  // NewtonRevWave
-            launch_wave(k_rev_wave<M, RM, 1>, nbk, 1, sy, c->sl, c->w, prev, qsel);
-        }
-        if (solved)  // block LU, Woodbury solve, u-columns and mu_F in one launch (wave per chain)
-          launch_blocks(k_newton_fsm_wave<M, RM>, (long)sy.B, 64, 5, sy, c->sl, c->w, prev, qsel), c->diag[4]++;
-        else
-          launch(KNewtonFactor<M, RM>{sy, c->sl, c->w, prev}, nbk, 9), c->diag[5]++;
-      }
-#else
-      launch(KNewtonBlk<M, RM>{sy, c->sl, c->w, prev, qsel}, (long)sy.B * sy.K, 1);
-#endif
+      solved = newton_sweep<M, RM>(c, prev, qsel);
       if (!solved) solve_chain<M, RM, 0, 0>(sy, c->sl, c->w, prev, qsel, 0);
     } else {
       launch(KSymBlk<M, RM>{sy, c->sl, c->w, prev, 1}, (long)sy.B * sy.K, 9);
       solve_chain<M, RM, 1, 0>(sy, c->sl, c->w, prev, qsel, 0);
     }
-#ifdef CHMC_WAVE_KERNELS
-    if (c->plan.rows == RowsCompact) {
-      if (!solved) mu_f<M, RM, 0>(c, prev);  // (the solving sweeps have formed mu_F)
-      update_pb_columns<M, RM, 0>(c, prev, qsel, 0);
-      return;
-    }
-#endif
-    update<RM, 0>(sy, c->sl, c->w, prev, qsel, 0);
+    jt_lambda<M, RM, 0>(c, prev, qsel, 0, solved);
   });
 }
 
@@ -846,19 +511,6 @@ static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel) {
 // same segmentation, k_newton_comb_wg, k_jw_pb_wg: tests/test_hip_parity.py::test_per_chain_kernels_equal_the_batched_path_
 // bitwise), so which of the two runs is a pure scheduling decision:
 // chain_kernel_waves (chmc_plan.h).
-// The per-chain kernels are instantiated for the SIR models only: they are sized to SIR's 75 KB of LDS.  A FitzHugh-Nagumo
-// layout with one 16-row block per chain (T <= 14) always runs the batched path of the same plan, so CHMC_RETRACT_KERNEL=1/2
-// changes nothing there.
-// The gate is written twice and the two must agree: chain_kernel_model (run time, on chmc_config::model) decides whether a
-// call takes the per-chain path, kChainKernels (compile time, on the model type `dispatch` selects for that id) decides
-// which instantiations exist.  `dispatch` maps CHMC_MODEL_SIR to SirModel / SirVsModel and nothing else to them, and both
-// carry SirModel::ID -- held below, so a model id that drifts from its type's ID does not compile rather than launching nothing.
-static_assert(SirModel::ID == CHMC_MODEL_SIR && SirVsModel::ID == CHMC_MODEL_SIR && FhnModel::ID == CHMC_MODEL_FHN &&
-                  FhnVsModel::ID == CHMC_MODEL_FHN && FhnNbModel::ID == CHMC_MODEL_FHN_NOTEBOOK,
-              "chain_kernel_model and kChainKernels gate the per-chain kernels on the same models");
-static bool chain_kernel_model(const chmc_ctx* c) { return c->model == CHMC_MODEL_SIR; }
-template <class M, int RM>
-constexpr bool kChainKernels = RM == 16 && M::ID == CHMC_MODEL_SIR;
 static int retract_waves(const chmc_ctx* c, int newton, const void* views) {
   return chain_kernel_waves(c->plan, part_plan(c).retract_chain && chain_kernel_model(c), c->sy.B, c->num_cus, newton != 0,
                             views != nullptr);
@@ -872,26 +524,17 @@ static int traj_waves(const chmc_ctx* c, int n_inner, int newton) {
 static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ctol, double ptol, double dtol,
                           int max_iters, const ViewSave* views = nullptr, int count_dir = -1) {
   const Sys& sy = c->sy;
-#ifdef CHMC_WAVE_KERNELS
+  // (read at every use: d_itf / d_itb are those of the half-batch view that is active then)
+  auto iters_dst = [&] { return count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf); };
   if (const int waves = retract_waves(c, newton, views)) {
-    int* iters_dst = count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf);
     dispatch(c, [&](auto inst) {
-      using M = typename decltype(inst)::M;
-      constexpr int RM = decltype(inst)::RM;
-      if constexpr (kChainKernels<M, RM>) {
-        if (waves == 4)
-          launch_blocks(k_retract_chain<M, RM, 4>, (long)sy.B, 256, 1, sy, c->sl, c->w, prev, qsel, ctol, ptol, dtol, max_iters,
-                        iters_dst);
-        else
-          launch_blocks(k_retract_chain<M, RM, CHMC_RETRACT_WAVES>, (long)sy.B, 64 * CHMC_RETRACT_WAVES, 1, sy, c->sl, c->w, prev,
-                        qsel, ctol, ptol, dtol, max_iters, iters_dst);
-      }
+      retract_chain<typename decltype(inst)::M, decltype(inst)::RM>(waves, (long)sy.B, sy, c->sl, c->w, prev, qsel, ctol, ptol,
+                                                                     dtol, max_iters, iters_dst());
     });
     c->counters[6]++;  // (one launch that lasts as long as its slowest chain iterates)
     c->diag[2]++;
     return 0;
   }
-#endif
   const int nh = views ? 2 : 1;
   auto enter = [&](int h) {
     if (views) set_half(c, *views, h);
@@ -904,19 +547,14 @@ static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ct
   // Time-parallel scans with one block per chain do not wait for a chain they cannot settle within a few sweeps: the chain
   // sits the round out (mask 2, k_fwd_par) and its scan goes on in the next round's launch.  Rounds are therefore not
   // iterations: the loop gets up to 64 / CHMC_PAR_MAXS_ROUND + 1 rounds per iteration (KCheck enforces max_iters per chain).
-#ifdef CHMC_WAVE_KERNELS
-  const bool carry = c->plan.par_scan && sy.K == 1;
-#else
-  const bool carry = false;
-#endif
+  const bool carry = c->plan.fwd == FwdPar && sy.K == 1;
   const int max_rounds = carry ? 12 * (max_iters + 1) : max_iters;
   auto iteration = [&](int poll_slot) {  // poll_slot >= 0: the round's count of active chains goes to that pinned slot
     iteration_scan(c, newton, prev, qsel, fwd_guess, 1);
     iteration_after_scan(c, newton, prev, qsel);
     // (KCheck also adds a finished loop's iteration count to the step's counter -- KAddIters folded in -- and clears the
     // next round's counter: no memset between the rounds)
-    const KCheck chk{c->w, ctol, ptol, dtol, max_iters, sy.B, count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf),
-                     c->round & 3};
+    const KCheck chk{c->w, ctol, ptol, dtol, max_iters, sy.B, iters_dst(), c->round & 3};
     // (the count reaches the pinned poll slot from the check's last workgroup: no copy packet behind it; A/B on one box,
     // three interleaved runs each: configs[1] 46.3-46.8 k -> 46.7-47.1 k steps/s, SIR unchanged)
     if (poll_slot >= 0) launch_publish(chk, sy.B, c->w.n_active + (c->round & 3), poll_slot);
@@ -977,7 +615,7 @@ static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ct
   }
   for (int h = 0; h < nh; ++h) {  // a chain the host left in the loop is a failure, never a silent success
     enter(h);
-    if (sy.B > 0) launch(KNewtonEnd{c->w, count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf)}, sy.B);
+    if (sy.B > 0) launch(KNewtonEnd{c->w, iters_dst()}, sy.B);
   }
   c->round = 0;
   return 0;
@@ -1408,22 +1046,12 @@ extern "C" int chmc_update_x_obs_seq(chmc_ctx* ctx) {
 }
 extern "C" int chmc_switch_partition(chmc_ctx* ctx) {
   CHMC_ENTER("chmc_switch_partition")
-#ifdef CHMC_WAVE_KERNELS
   // the stored trajectories (valid for the partition we are leaving) seed a time-parallel pass over the whole chain
   // (the stored-rows family keeps round 1's sequential pass: the A/B test then covers both)
   const bool par = ctx->plan.pb_allocated && ctx->have_state;
-  if (par) {
-    const Sys& so = ctx->sy;
-    dispatch(ctx, [&](auto inst) {
-      launch_blocks(k_xobs_par<typename decltype(inst)::M>, (long)so.B, 64, 0, so, ctx->sl, ctx->d_xobs);
-    });
-  }
+  if (par) dispatch(ctx, [&](auto inst) { xobs_par<typename decltype(inst)::M>(ctx); });
   select_partition(ctx, (ctx->part + 1) % ctx->num_partition);
   if (!par) update_x_obs(ctx);
-#else
-  select_partition(ctx, (ctx->part + 1) % ctx->num_partition);
-  update_x_obs(ctx);
-#endif
   begin_all(ctx, nullptr, nullptr);
   state_eval(ctx, 0);
   ctx->mom_tangent = false;  // the momentum was tangent to the other partition's constraint set
@@ -1530,14 +1158,7 @@ extern "C" int chmc_lmult_by_jacob_constr(chmc_ctx* ctx, const double* vct, doub
   ensure_rows(ctx);
   h2d(ctx->w.vin, vct, sizeof(double) * (size_t)sy.B * sy.Q);
   begin_all(ctx, nullptr, nullptr);
-  dispatch(ctx, [&](auto inst) {
-    constexpr int RM = decltype(inst)::RM;
-#ifdef CHMC_WAVE_KERNELS
-    launch_wave(k_jw_wave<RM>, (long)sy.B * sy.K, 6, sy, ctx->sl, ctx->w, 0, 2);
-#else
-    launch(KJw<RM>{sy, ctx->sl, ctx->w, 0, 2}, (long)sy.B * sy.K * RM, 6);
-#endif
-  });
+  dispatch(ctx, [&](auto inst) { jw<typename decltype(inst)::M, decltype(inst)::RM>(ctx, 0, 2, false); });
   fetch_padded(ctx, ctx->w.cpad, out, 1);
   CHMC_LEAVE("chmc_lmult_by_jacob_constr")
 }
@@ -1598,11 +1219,7 @@ extern "C" int chmc_normal_space_component(chmc_ctx* ctx, const double* vct, dou
   dispatch(ctx, [&](auto inst) {
     using M = typename decltype(inst)::M;
     constexpr int RM = decltype(inst)::RM;
-#ifdef CHMC_WAVE_KERNELS
-    launch_wave(k_jw_wave<RM>, (long)sy.B * sy.K, 6, sy, ctx->sl, ctx->w, 0, 2 | 256);
-#else
-    launch(KJw<RM>{sy, ctx->sl, ctx->w, 0, 2 | 256}, (long)sy.B * sy.K * RM, 6);
-#endif
+    jw<M, RM>(ctx, 0, 2 | 256, false);
     launch(KSymBlk<M, RM>{sy, ctx->sl, ctx->w, 0, 0}, (long)sy.B * sy.K, 9);
     solve_chain<M, RM, 1, 2>(sy, ctx->sl, ctx->w, 0, 0, 0);
     update<RM, 2>(sy, ctx->sl, ctx->w, 0, 0, 0);
@@ -1621,7 +1238,7 @@ extern "C" int chmc_project_onto_cotangent_space(chmc_ctx* ctx) {
 // conditioned_diffusion_neg_log_dens_and_grad (:82-205) for the positions staged in work.qb; values into ctx->d_ham [B],
 // gradient (optional) into grad_dev [B][U + NV]
 static int nld_core(chmc_ctx* ctx, int use_gaussian_splitting, double* grad_dev) {
-#ifdef CHMC_WAVE_KERNELS
+  if (!ctx->plan_in.wave_kernels) return fail("chmc_neg_log_dens_and_grad: not available in the host emulation build");
   const Sys& sy = ctx->sy;
   const int QH = sy.U + sy.NV;
   // the whole chain as ONE block of T observations: the forward-scan kernel then integrates the full trajectory
@@ -1648,24 +1265,9 @@ static int nld_core(chmc_ctx* ctx, int use_gaussian_splitting, double* grad_dev)
   }
   begin_all(ctx, nullptr, nullptr);  // every chain active
   dispatch(ctx, [&](auto inst) {
-    using M = typename decltype(inst)::M;
-    constexpr int RM = decltype(inst)::RM;
-    if (par) {
-      Sys sp = sf;
-      sp.order = ctx->d_order_ident;
-      fwd_par<M, RM>(ctx->plan.nld_waves, (long)sy.B, sp, ctx->sl, ctx->w, 0, 1, 0, 2, 1, 0);
-    } else if (ctx->plan.nld == FwdWave)
-      launch_blocks(k_fwd_scan<M, RM, true>, ((long)sy.B + 63) / 64, 64 * (1 + CHMC_SCAN_HELPERS), 7, sf, ctx->sl, ctx->w, 0, 1, 0, 2, ctx->w, 0, 0);
-    else
-      launch(KFullScan<M>{sy, ctx->w.qb, ctx->w.trajw, QH}, sy.B, 7);
-    launch_wave(k_nld_grad_wave<M>, (long)sy.B, 0, sy, ctx->w.qb, ctx->w.trajw, QH, use_gaussian_splitting, ctx->d_ham,
-                grad_dev);
+    nld_sweeps<typename decltype(inst)::M, decltype(inst)::RM>(ctx, sf, QH, use_gaussian_splitting, grad_dev);
   });
   return 0;
-#else
-  (void)ctx, (void)use_gaussian_splitting, (void)grad_dev;
-  return fail("chmc_neg_log_dens_and_grad: not available in the host emulation build");
-#endif
 }
 extern "C" int chmc_neg_log_dens_and_grad(chmc_ctx* ctx, const double* q, int use_gaussian_splitting, double* value,
                                           double* grad) {
@@ -1822,11 +1424,7 @@ extern "C" int chmc_gd_objective_device(chmc_ctx* ctx, const void* q_dev, const 
   dispatch(ctx, [&](auto inst) {
     using M = typename decltype(inst)::M;
     launch(KGdFwd<M>{sy, q, xo, ctx->w.trajw, cres}, (long)tasks, 7);
-#ifdef CHMC_WAVE_KERNELS
-    launch_wave(k_gd_grad_wave<M>, (long)tasks, 0, sy, q, (const double*)ctx->w.trajw, (const double*)cres, reg_coeff, g, part);
-#else
-    launch(KGdGrad<M>{sy, q, ctx->w.trajw, cres, reg_coeff, g, part}, (long)tasks);
-#endif
+    gd_grad<M>(ctx, (long)tasks, q, cres, reg_coeff, g, part);
     launch(KGdReduce<M>{sy, q, part, reg_coeff, g, stat}, sy.B);
   });
   launch_rowsum(KAdamRow{q, g, sy.Q}, sy.Q, sy.B, 2, ctx->w.part, 8);
@@ -2019,25 +1617,15 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
     ctx->last_active_null = true;
   }
   if (n_inner > 1) ensure_array(ctx, ctx->d_q0), ensure_array(ctx, ctx->d_p0), ensure_array(ctx, ctx->d_ncommit);
-#ifdef CHMC_WAVE_KERNELS
   if (const int waves = traj_waves(ctx, n_inner, newton)) {
     ensure_array(ctx, ctx->d_nsteps), ensure_array(ctx, ctx->d_ndone);
     if (n_steps_host) h2d(ctx->d_nsteps, n_steps_host, sizeof(int) * sy.B);
     begin_all(ctx, d_dt ? ctx->w.err : nullptr, d_active ? ctx->d_act : nullptr, 1.0);
     dev_zero(ctx->d_itf, sizeof(int) * sy.B), dev_zero(ctx->d_itb, sizeof(int) * sy.B);
     dispatch(ctx, [&](auto inst) {
-      using M = typename decltype(inst)::M;
-      constexpr int RM = decltype(inst)::RM;
-      if constexpr (kChainKernels<M, RM>) {
-        if (waves == 4)
-          launch_blocks(k_traj_chain<M, RM, 4>, (long)sy.B, 256, 1, sy, ctx->sl, ctx->w,
-                        n_steps_host ? ctx->d_nsteps : nullptr, n_steps_all, ctol, ptol, dtol, max_iters, rev_tol, ctx->d_itf,
-                        ctx->d_itb, want_n_done ? ctx->d_ndone : nullptr);
-        else
-          launch_blocks(k_traj_chain<M, RM, CHMC_RETRACT_WAVES>, (long)sy.B, 64 * CHMC_RETRACT_WAVES, 1, sy, ctx->sl, ctx->w,
-                        n_steps_host ? ctx->d_nsteps : nullptr, n_steps_all, ctol, ptol, dtol, max_iters, rev_tol, ctx->d_itf,
-                        ctx->d_itb, want_n_done ? ctx->d_ndone : nullptr);
-      }
+      traj_chain<typename decltype(inst)::M, decltype(inst)::RM>(
+          waves, (long)sy.B, sy, ctx->sl, ctx->w, n_steps_host ? ctx->d_nsteps : nullptr, n_steps_all, ctol, ptol, dtol, max_iters,
+          rev_tol, ctx->d_itf, ctx->d_itb, want_n_done ? ctx->d_ndone : nullptr);
     });
     ctx->rows_fresh = false;
     ctx->diag[3]++;
@@ -2045,7 +1633,6 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
     ctx->counters[0] += ns, ctx->counters[1] += ns, ctx->counters[3] += ns, ctx->counters[4] += ns, ctx->counters[6] += 2 * ns;
     return 0;
   }
-#endif
   // The step is a sequence of phases per batch; with two half-batches every phase is enqueued for half 0 on its
   // stream, then for half 1 on the other, and the two Newton loops advance in lock step (run_projection).  The halves
   // are chain ranges of the same arrays, so nothing but the streams is shared; the forward scans of the two halves are
@@ -2216,7 +1803,6 @@ extern "C" int chmc_leapfrog_steps(chmc_ctx* ctx, const double* dt, const int* a
   if (!n_steps && n_steps_all < 0) return fail("chmc_leapfrog_steps: negative number of steps");
   const Sys& sy = ctx->sy;
   const int B = sy.B;
-#ifdef CHMC_WAVE_KERNELS
   if (traj_waves(ctx, n_inner, newton)) {
     // one launch: every chain walks its own steps in its own workgroup (k_traj_chain) and stops at its first failed step
     int longest = n_steps_all;
@@ -2241,7 +1827,6 @@ extern "C" int chmc_leapfrog_steps(chmc_ctx* ctx, const double* dt, const int* a
     (void)tot;
     CHMC_LEAVE("chmc_leapfrog_steps")
   }
-#endif
   // chmc_leapfrog_step's batched steps; a chain whose step fails sits out the rest of the call
   std::vector<int> act(B), left(B), nd(B, 0), st_out(B, 0), itf(B, 0), itb(B, 0), st(B), f(B), b(B);
   std::vector<double> rv(B, 0.0), r1(B);

@@ -1,6 +1,6 @@
 // Which kernel runs for which pass: decided here, once per context, from the layout and the environment switches.
-// Plain host C++ (no device code, no HIP): chmc_api.inc stores the KernelPlan in the context and its launch sites switch
-// on it; tests/test_kernel_plan.py states the table on the CPU through tests/emu/plan_probe.cpp.
+// Plain host C++ (no device code, no HIP): chmc_api.inc stores the KernelPlan in the context, its sequencing and the passes
+// of chmc_passes.inc (the launch sites) switch on it; tests/test_kernel_plan.py states the table on the CPU through tests/emu/plan_probe.cpp.
 //
 // The library has TWO complete sets of kernels for the passes over a point's Jacobian (RowFamily); every other round-1 /
 // round-2 variant has been removed (round 3):
@@ -52,7 +52,7 @@
 #define CHMC_CHAIN_SCAN_WAVES 4  // (chmc_retract.h, likewise)
 #endif
 static_assert(CHMC_CHAIN_SCAN_WAVES == 1 || CHMC_CHAIN_SCAN_WAVES == 2 || CHMC_CHAIN_SCAN_WAVES == 4,
-              "k_fwd_par is launched with 1, 2 or 4 wavefronts per workgroup (fwd_par in chmc_api.inc)");
+              "k_fwd_par is launched with 1, 2 or 4 wavefronts per workgroup (fwd_par in chmc_passes.inc)");
 #ifndef CHMC_CHAIN_WG4_MAX_PER_CU
 #define CHMC_CHAIN_WG4_MAX_PER_CU 4  // (chains per CU up to which two 4-wavefront workgroups per CU match or beat batched launches)
 #endif

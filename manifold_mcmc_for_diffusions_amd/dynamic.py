@@ -21,7 +21,7 @@ All random choices come from `TreeUniforms`, keyed by (seed, transition, purpose
 index, so they do not depend on how chains are sharded or on the order in which an implementation asks for them.  The
 chains' arithmetic is sharding-independent bit for bit as well: the library chooses its kernels (time-parallel or
 sequential forward scan, interval-parallel or stored-rows 16-row sweeps, the per-chain retraction kernel) from the layout
-alone -- blocks per chain, block length, rows -- never from the number of chains in the context (csrc/chmc_api.inc
+alone -- blocks per chain, block length, rows -- never from the number of chains in the context (csrc/chmc_plan.h
 few_long_blocks; GPU test test_results_do_not_depend_on_the_shard_size).
 """
 import numpy as np

@@ -60,6 +60,26 @@ def test_no_fallback_without_gpu():
         _lib._LIB = saved
 
 
+def test_sequencing_is_one_text_for_both_builds():
+    """csrc/chmc_api.inc (sequencing, C ABI) is compiled identically by the library and by the host emulation of tests/emu/:
+    it has no CHMC_WAVE_KERNELS outside the RCCL block that closes it and names no __global__ kernel (k_*); every choice of
+    a kernel per pass lives in csrc/chmc_passes.inc under one #ifdef."""
+    csrc = os.path.join(ROOT, "manifold_mcmc_for_diffusions_amd", "csrc")
+
+    def code(name):
+        txt = open(os.path.join(csrc, name)).read()
+        return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+
+    api = code("chmc_api.inc")
+    sequencing, rccl_opens, _ = api.rpartition("#ifdef CHMC_WAVE_KERNELS\n#include <dlfcn.h>\n#include <rccl/rccl.h>")
+    assert rccl_opens, "the RCCL block no longer closes chmc_api.inc: check the whole file instead"
+    assert "CHMC_WAVE_KERNELS" not in sequencing
+    assert re.findall(r"\bk_[a-z0-9_]+", api) == []
+    assert '#include "chmc_passes.inc"' in sequencing
+    assert len(re.findall(r"^\s*#\s*if.*\bCHMC_WAVE_KERNELS\b", code("chmc_passes.inc"), flags=re.M)) == 1
+    assert len(re.findall(r"^\s*#\s*ifdef\s+CHMC_WAVE_KERNELS\b", code("chmc_passes.inc"), flags=re.M)) == 1
+
+
 def test_product_does_not_import_the_oracle():
     pkg = os.path.join(ROOT, "manifold_mcmc_for_diffusions_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -1,6 +1,7 @@
 """CPU-side tests of the library's HOST logic (kernel sequencing of csrc/chmc_api.inc, masks, status codes,
 partition tables, padded layouts) through a TEST-ONLY host emulation build (tests/emu): every device functor is
-run in a plain loop.  The emulation library is never loadable through the package (the loader only knows
+run in a plain loop.  The emulation compiles the same text of chmc_api.inc as the library; only the pass layer
+(csrc/chmc_passes.inc) gives it generic functors where the library launches wave kernels.  The emulation library is never loadable through the package (the loader only knows
 libchmc_hip.so); it is injected here explicitly.  The GPU parity tests proper are in test_hip_parity.py."""
 import ctypes
 import os

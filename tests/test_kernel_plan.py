@@ -6,7 +6,8 @@ fresh process per switch setting: the library reads its switches from the enviro
 Expected values: `DEFAULT_PLANS` is written out by hand, and `parent_plan` transcribes the predicates of the commit
 before the plan module existed (compact_rows, gram_mfma, compact_family, gram_mfma8, compact16, lean16, chain16,
 rows_skipped, row_split_choice, few_long_blocks, par_waves_for, chain16_layout, step_fusions, mom_fix_in_jw,
-rev_flow_in_update, retract_waves, traj_kernel of csrc/chmc_api.inc) and the ladders of its launch sites, one to one."""
+rev_flow_in_update, retract_waves, traj_kernel of csrc/chmc_api.inc) and the ladders of its launch sites (now the passes of
+csrc/chmc_passes.inc), one to one."""
 import json
 import os
 import subprocess
