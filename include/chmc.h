@@ -365,7 +365,7 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *   out80[65]      launches of the vector-FMA Gram kernel over stored rows (16-row blocks)
  *   out80[66]      launches of the per-chain retraction kernel (k_retract_chain: one 16-row block per chain, SIR models only)
  *   out80[67]      launches of the per-chain trajectory kernel (k_traj_chain: whole leapfrog steps of such a chain)
- *   out80[68]      launches of k_newton_fsm_wave (blocks of at most 8 rows, at most 64 blocks per chain: block LU, Woodbury
+ *   out80[68]      launches of k_newton_fsm_wave or of its form for two problems (blocks of at most 8 rows, at most 64 blocks per chain: block LU, Woodbury
  *                  solve and mu_F of a Newton round in one launch, a wavefront per chain)
  *   out80[69]      launches of KNewtonFactor for blocks of at most 8 rows (the unfused Newton round: more than 64 blocks per
  *                  chain, or the stored-rows families; the chain solve and mu_F follow as launches of their own)
@@ -374,7 +374,10 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *                  CHMC_PAIR_RETRACT=0 switches the pairing off)
  *   out80[71]      forward-scan launches of the lock-step Newton loops (a merged launch counts once)
  *   out80[72]      rounds those loops enqueued, counted per problem: with the hand-scheduled scan, [71] = [72] - [70]
- *   out80[73 .. 79] reserved (0)
+ *   out80[73]      rounds among those of [70] whose passes behind the scan served both problems as well: interval sums,
+ *                  combine, solve and J^T lambda update one launch each for the pair (compact rows in blocks of at most 8 row
+ *                  slots, at most 64 blocks per chain; CHMC_PAIR_PASSES=0 keeps one launch per problem and pass)
+ *   out80[74 .. 79] reserved (0)
  * Synchronises the context's stream. */
 int chmc_get_diagnostics(chmc_ctx* ctx, long long* out80);
 

@@ -340,6 +340,36 @@ __global__ void __launch_bounds__(256) k_colmax(F f, int ncol, int rev) {
     if (v) atomicMax(tgt, v);
   }
 }
+// ... for two problems on the same columns (KUpdatePBPair): f.active(c) is a mask of the problems chain c takes part in, the
+// workgroup returns only when it is out of both; f(c, col, mask, v) returns one bit pattern per problem, each max-reduced
+// into its own f.red(c, p) exactly as above
+template <class F>
+__global__ void __launch_bounds__(256) k_colmax_pair(F f, int ncol, int rev) {
+  const int c = rev ? gridDim.y - 1 - blockIdx.y : blockIdx.y;
+  const int act = f.active(c);  // uniform per workgroup
+  if (!act) return;
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  unsigned long long v[2] = {0ULL, 0ULL};
+  if (col < ncol) f(c, col, act, v);
+  __shared__ unsigned long long sm[2][4];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long o = __shfl_xor(v[p], off, 64);
+      v[p] = o > v[p] ? o : v[p];
+    }
+    if ((threadIdx.x & 63) == 0) sm[p][threadIdx.x >> 6] = v[p];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      unsigned long long m = v[p];
+      for (int i = 1; i < 4; ++i) m = sm[p][i] > m ? sm[p][i] : m;
+      if (((act >> p) & 1) && m) atomicMax(f.red(c, p), m);
+    }
+  }
+}
 // One ticket word per poll slot: the check kernels of the two half-batches (CHMC_HALVES=2: slots 2 h + (round & 1)) run on
 // different streams and may overlap, so they must not draw tickets from one counter (a workgroup of the wrong launch would
 // then publish a partial count and the other half's count would never arrive).  Launches that share a slot are ordered by
@@ -382,6 +412,24 @@ static void launch_colmax(F f, int ncol, int B, int cls = 0) {
     note(hipEventRecord(r.a, g_stream));
   }
   hipLaunchKernelGGL(k_colmax<F>, dim3((unsigned)((ncol + 255) / 256), (unsigned)B), dim3(256), 0, g_stream, f, ncol,
+                     next_chain_direction());
+  note(hipGetLastError());
+  if (prof) {
+    note(hipEventRecord(r.b, g_stream));
+    g_prof_pending.push_back(r);
+    if (g_prof_pending.size() > 4096) prof_drain();
+  }
+}
+template <class F>
+static void launch_colmax_pair(F f, int ncol, int B, int cls = 0) {
+  if (ncol <= 0 || B <= 0) return;
+  ProfRec r;
+  const bool prof = g_prof_on_for(cls);
+  if (prof) {
+    r.a = prof_event(), r.b = prof_event(), r.cls = cls;
+    note(hipEventRecord(r.a, g_stream));
+  }
+  hipLaunchKernelGGL(k_colmax_pair<F>, dim3((unsigned)((ncol + 255) / 256), (unsigned)B), dim3(256), 0, g_stream, f, ncol,
                      next_chain_direction());
   note(hipGetLastError());
   if (prof) {

@@ -60,7 +60,9 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   long long diag[16] = {0};  // launches by kernel family: [0] k_gram_rows_mfma, [1] k_gram_rows, [2] k_retract_chain, [3] k_traj_chain,
                               // [4] k_newton_fsm_wave, [5] KNewtonFactor (blocks of at most 8 rows), [6] rounds whose forward scan
                               // served two problems (one k_fwd_scan<.., PAIR> launch), [7] forward-scan launches of the
-                              // lock-step Newton loops, [8] rounds enqueued by them, per problem
+                              // lock-step Newton loops, [8] rounds enqueued by them, per problem, [9] rounds of a paired loop
+                              // whose passes behind the scan served two problems as well (KernelPlan::pair_passes: interval
+                              // sums, combine, solve and J^T lambda update one launch each; a subset of [6])
   // Paired retractions (KernelPlan::pair_retractions): the second problem of run_projection_pair -- the forward retraction of
   // the NEXT step -- works in a Work of its own: every array a round's kernels, KNewtonBegin, KCheck or KNewtonEnd write
   // (pair_alloc), everything they only read shared with `w`.  Whole batch only, allocated on first use.
@@ -497,6 +499,17 @@ static void iteration_after_scan(chmc_ctx* c, int newton, int prev, int qsel) {
     jt_lambda<M, RM, 0>(c, prev, qsel, 0, solved);
   });
 }
+// ... of a Newton round of two problems with the same (prev, qsel), c->w and w1, every pass one launch for both
+// (KernelPlan::pair_passes)
+static void iteration_after_scan_pair(chmc_ctx* c, int prev, int qsel, const Work& w1) {
+  dispatch(c, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    constexpr int RM = decltype(inst)::RM;
+    newton_sweep_pair<M, RM>(c, w1, prev, qsel);
+    jt_lambda_pair<M, RM>(c, w1, prev, qsel);
+  });
+  c->diag[9]++;
+}
 
 // Newton / quasi-Newton loop (:999-1135), every chain of the batch in lock step.  Leaves per-chain iters / err / ndq / nstat
 // in the work arrays.
@@ -653,10 +666,11 @@ static void pair_alloc(chmc_ctx* c) {
 // The reverse retraction of step i (problem 0: run_projection(.., 1, 1, .., 1) exactly, on c->w) and the forward retraction of
 // step i + 1 (problem 1, on c->pw: its iterate pw.qb holds the forward-flowed point, KPairFlow) in ONE lock-step loop.  Both are
 // Newton loops against the proposal slot's point (prev = 1) on an iterate in a work array (qsel = 1).  A round is one forward
-// scan for both problems (iteration_scan_pair; the single form once one of them has finished), then each problem's own
-// sweep, solve, update and check, on the one stream.  Each problem keeps the read-backs, the speculation and the predicted stop
-// of a loop of its own (run_projection), counted per problem: poll slots 2 p + parity, proj_rounds / proj_stable of its
-// direction -- so a problem is enqueued for exactly the rounds its own loop would have been, and counters[6] counts a round
+// scan for both problems (iteration_scan_pair; the single form once one of them has finished), then sweep, solve and update
+// -- one launch per pass for both where the plan has pair_passes and both problems still iterate
+// (iteration_after_scan_pair), otherwise each problem's own -- and each problem's own check, on the one stream.  Each
+// problem keeps the read-backs, the speculation and the predicted stop of a loop of its own (run_projection), counted per
+// problem: poll slots 2 p + parity, proj_rounds / proj_stable of its direction -- so a problem is enqueued for exactly the rounds its own loop would have been, and counters[6] counts a round
 // once per problem that had work.
 static int run_projection_pair(chmc_ctx* c, int newton, double ctol, double ptol, double dtol, int max_iters) {
   const Sys& sy = c->sy;
@@ -679,9 +693,12 @@ static int run_projection_pair(chmc_ctx* c, int newton, double ctol, double ptol
         done[p] = stopped[p] = true;
     if (done[0] && done[1]) break;
     c->round = it;
-    if (!done[0] && !done[1]) {
+    const bool both = !done[0] && !done[1];
+    const bool merged = both && newton && c->plan.pair_passes;  // every pass behind the scan once for both as well
+    if (both) {
       enter(0);
       iteration_scan_pair(c, newton, prev, qsel, wk[1]);
+      if (merged) iteration_after_scan_pair(c, prev, qsel, wk[1]);
     } else {
       enter(done[0] ? 1 : 0);
       iteration_scan(c, newton, prev, qsel, it == 0 ? 2 : 1, 1);
@@ -689,7 +706,7 @@ static int run_projection_pair(chmc_ctx* c, int newton, double ctol, double ptol
     for (int p = 0; p < 2; ++p) {
       if (done[p]) continue;
       enter(p);
-      iteration_after_scan(c, newton, prev, qsel);
+      if (!merged) iteration_after_scan(c, newton, prev, qsel);
       const KCheck chk{c->w, ctol, ptol, dtol, max_iters, sy.B, iters_dst[p], it & 3};
       if (it >= 1) launch_publish(chk, sy.B, c->w.n_active + (it & 3), 2 * p + (it & 1));
       else launch(chk, sy.B);

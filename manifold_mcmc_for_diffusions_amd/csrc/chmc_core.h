@@ -1807,6 +1807,123 @@ struct KUpdatePB {  // one step per work item
     return r;
   }
 };
+// KUpdatePB<.., 0> for the two problems of a paired Newton round (KernelPlan::pair_passes): both update their iterate
+// against the SAME compact rows, so a work item loads PB[s] once and applies mu_F of `w` to the iterate of `w` and mu_F of
+// `w1` to that of `w1`.  Every expression is the single form's (same contraction, same bits); a chain takes part per
+// problem (active: bit p set when it is in problem p's loop), and a problem a chain is out of is neither read nor written.
+// Column-max launch with two reductions (launch_colmax_pair): operator() returns max |delta| per problem in r[2].
+template <int RM, int X, int V>
+struct KUpdatePBPair {
+  Sys sy;
+  Slots sl;
+  Work w, w1;
+  int which, qsel;
+  CHMC_HD int active(int c) const {
+    int p_ = 0, q_ = 0;
+    return (newton_select(w, c, p_, q_) ? 1 : 0) | (newton_select(w1, c, p_, q_) ? 2 : 0);
+  }
+  CHMC_HD unsigned long long* red(int c, int p) const { return p ? &w1.ndq[c] : &w.ndq[c]; }
+  CHMC_FI CHMC_HD void operator()(int c, int idx, int act, unsigned long long (&r)[2]) const {
+    const int s = sl.cur[c] ^ which;
+    const size_t off = (size_t)c * sy.Q + sy.U;
+    double* tgt[2] = {(qsel ? w.qb : pick(sl.q, s ^ 1)) + off, (qsel ? w1.qb : pick(sl.q, s ^ 1)) + off};
+    const bool on[2] = {(act & 1) != 0, (act & 2) != 0};
+    const int TS = sy.T * sy.S;
+    r[0] = r[1] = 0ULL;
+    if (idx < TS) {
+      const int st0 = idx;
+      const int g = st0 / sy.S;  // observation interval
+      const int b = sy.obs2blk[g];
+      const int m = g - sy.blk[b].obs0;
+      const size_t mo = (((size_t)c * sy.Kmax + b) * sy.NOBS + m) * X;
+      const double* pb = pick(sl.PB, s) + ((size_t)c * TS + st0) * (X * V);
+      const size_t to = sy.V0 + (size_t)st0 * V;
+      const bool wide = V == 2 && !((sy.Q | sy.U | sy.V0) & 1);
+      double old[2][V], pbv[X * V], mu[2][X];
+      // all loads first: the work item's bytes in flight hide the memory latency
+      CHMC_UNROLL
+      for (int p = 0; p < 2; ++p) {
+        if (!on[p]) continue;
+        if (wide) {
+          const double2_ o = *reinterpret_cast<const double2_*>(tgt[p] + to);
+          old[p][0] = o.x, old[p][V - 1] = o.y;
+        } else {
+          CHMC_UNROLL
+          for (int k = 0; k < V; ++k) old[p][k] = tgt[p][to + k];
+        }
+      }
+      if ((X * V) % 2 == 0) {
+        CHMC_UNROLL
+        for (int k = 0; k < X * V; k += 2) {
+          const double2_ v = ld2_stream(pb + k);
+          pbv[k] = v.x, pbv[k + 1 < X * V ? k + 1 : k] = v.y;
+        }
+      } else {
+        CHMC_UNROLL
+        for (int k = 0; k < X * V; ++k) pbv[k] = pb[k];
+      }
+      CHMC_UNROLL
+      for (int a = 0; a < X; ++a) {
+        if (on[0]) mu[0][a] = w.muF[mo + a];
+        if (on[1]) mu[1][a] = w1.muF[mo + a];
+      }
+      CHMC_UNROLL
+      for (int p = 0; p < 2; ++p) {
+        if (!on[p]) continue;
+        CHMC_UNROLL
+        for (int k = 0; k < V; ++k) {
+          double tt = 0.0;
+          CHMC_UNROLL
+          for (int a = 0; a < X; ++a) tt += mu[p][a] * pbv[a * V + k];
+          const unsigned long long vb = absbits(tt);
+          r[p] = vb > r[p] ? vb : r[p];
+          old[p][k] -= tt;
+        }
+        if (wide) {
+          double2_ o;
+          o.x = old[p][0], o.y = old[p][V - 1];
+          *reinterpret_cast<double2_*>(tgt[p] + to) = o;
+        } else {
+          CHMC_UNROLL
+          for (int k = 0; k < V; ++k) tgt[p][to + k] = old[p][k];
+        }
+      }
+    } else {
+      const int e = idx - TS;
+      CHMC_UNROLL
+      for (int p = 0; p < 2; ++p) {
+        if (!on[p]) continue;
+        const double* lampad = p ? w1.lampad : w.lampad;
+        double d = 0.0;
+        int col;
+        if (e < sy.V0) {  // v_0 columns: the first block's stored rows
+          col = e;
+          const int b = sy.obs2blk[0];
+          const double* lam = lampad + ((size_t)c * sy.Kmax + b) * RM;
+          const double* Jv = pick(sl.Jv, s) + (size_t)c * RM * sy.NV + col;
+          const int nr = sy.blk[b].nrows;
+          for (int i = 0; i < RM; ++i)
+            if (i < nr) {
+              const double jv = Jv[(size_t)i * sy.NV];
+              d += jv * lam[i];
+            }
+        } else {  // observation-noise columns: dc/dn = sigma on the y rows (:601-608)
+          const int t = e - sy.V0;
+          col = sy.NV + t;
+          const int b = sy.obs2blk[t];
+          const int j = t - sy.blk[b].obs0;
+          if (j < sy.blk[b].ny) {
+            const double sg = sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q);
+            d = sg * lampad[((size_t)c * sy.Kmax + b) * RM + j];
+          }
+        }
+        r[p] = absbits(d);
+        const double gn = tgt[p][col] - d;
+        tgt[p][col] = gn;
+      }
+    }
+  }
+};
 
 // ------------------------------------------------------------------------------------------
 // find_initial_state_by_linear_interpolation (:1479-1547), batched: one work item per (chain, time step).  The path

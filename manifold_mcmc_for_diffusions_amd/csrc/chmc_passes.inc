@@ -254,6 +254,28 @@ static bool newton_sweep(chmc_ctx* c, int prev, int qsel) {
   }
   return solved;
 }
+// ... and J^T lambda update of the iterates of two problems, c->w and w1, against the rows of the same slot `prev`
+// (KernelPlan::pair_passes: compact rows, at most 8 row slots, NewtonIvlFsm -- the sweep has solved and formed mu_F): one
+// launch per pass for both.  Interval sums: a workgroup of two wavefronts per interval, one per problem, on the same PB
+// lines; combine and solve: both problems' wavefronts in one grid; update: one work item per step loads PB once for both
+// iterates (96 instead of 128 bytes per step and pair).
+template <class M, int RM>
+static void newton_sweep_pair(chmc_ctx* c, const Work& w1, int prev, int qsel) {
+  const Sys& sy = c->sy;
+  const long nbk = (long)sy.B * sy.K;
+  if constexpr (RM <= 8) {
+    launch_blocks(k_newton_ivl_pair<M>, nbk * sy.NOBS, 128, 1, sy, c->sl, c->w, prev, qsel, w1);
+    launch_blocks(k_newton_comb_pair<M, RM>, 2 * nbk, 64, 1, sy, c->sl, c->w, prev, qsel, w1);
+    launch_blocks(k_newton_fsm_wave_pair<M, RM>, 2 * (long)sy.B, 64, 5, sy, c->sl, c->w, prev, qsel, w1), c->diag[4]++;
+  }
+}
+template <class M, int RM>
+static void jt_lambda_pair(chmc_ctx* c, const Work& w1, int prev, int qsel) {
+  const Sys& sy = c->sy;
+  if constexpr (RM <= 8)
+    launch_colmax_pair(KUpdatePBPair<RM, M::X, M::V>{sy, c->sl, c->w, w1, prev, qsel}, sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0),
+                       sy.B, 4);
+}
 
 // J v -> cpad for the vector `vsel` selects, from the compact rows or from the stored rows of slot `which`
 template <class M, int RM>
@@ -394,6 +416,24 @@ template <class M, int RM>
 static bool newton_sweep(chmc_ctx* c, int prev, int qsel) {
   launch(KNewtonBlk<M, RM>{c->sy, c->sl, c->w, prev, qsel}, (long)c->sy.B * c->sy.K, 1);
   return false;
+}
+// (two calls of the single pass each in place of the merged launches; no emulation plan has pair_passes)
+template <class M, int RM>
+static void newton_sweep_pair(chmc_ctx* c, const Work& w1, int prev, int qsel) {
+  const Work w0 = c->w;
+  for (int p = 0; p < 2; ++p) {
+    c->w = p ? w1 : w0;
+    if (!newton_sweep<M, RM>(c, prev, qsel)) solve_chain<M, RM, 0, 0>(c->sy, c->sl, c->w, prev, qsel, 0);
+  }
+  c->w = w0;
+}
+template <class M, int RM>
+static void jt_lambda_pair(chmc_ctx* c, const Work& w1, int prev, int qsel) {
+  const Work w0 = c->w;
+  jt_lambda<M, RM, 0>(c, prev, qsel, 0);
+  c->w = w1;
+  jt_lambda<M, RM, 0>(c, prev, qsel, 0);
+  c->w = w0;
 }
 template <class M, int RM>
 static void jw(chmc_ctx* c, int which, int vsel, bool) {

@@ -41,6 +41,8 @@
 //                           step i and the forward retraction of step i + 1 advance round for round in one loop with one
 //                           forward-scan launch per round for both (KernelPlan::pair_retractions).  Default: paired while the
 //                           merged launch still has a compute unit per workgroup (pair_this_call); both give the same bits
+//   CHMC_PAIR_PASSES=0      a paired loop launches every pass behind the scan once per problem instead of once for both
+//                           (KernelPlan::pair_passes; the A/B partner of the merged passes, same bits)
 #pragma once
 #include <climits>
 #include <cstdlib>
@@ -65,6 +67,7 @@ struct Switches {
   int par_scan = kSwitchUnset, par_waves = kSwitchUnset, row_split = 0, halves = 1;
   bool no_fwd_scan = false, step_fusions = true;
   int retract_kernel = kSwitchUnset, pair_retract = kSwitchUnset;
+  bool pair_passes = true;
 };
 inline Switches read_switches() {
   auto env = [](const char* name, int unset) {
@@ -79,6 +82,7 @@ inline Switches read_switches() {
   s.no_fwd_scan = getenv("CHMC_NO_FWD_SCAN") != nullptr, s.step_fusions = env("CHMC_STEP_FUSIONS", 1) != 0;
   s.retract_kernel = env("CHMC_RETRACT_KERNEL", kSwitchUnset);
   s.pair_retract = env("CHMC_PAIR_RETRACT", kSwitchUnset);
+  s.pair_passes = env("CHMC_PAIR_PASSES", 1) != 0;
   return s;
 }
 
@@ -97,8 +101,8 @@ struct PlanInput {
   bool gaussian;         // Gaussian splitting
   bool wave_kernels;     // CHMC_WAVE_KERNELS: without them every pass is a generic functor over the stored rows
   Switches sw;           // as read by chmc_create
-  Switches call;         // as read on entry to the current call: no_fwd_scan, step_fusions, retract_kernel, pair_retract; the
-                         // comparator's scan
+  Switches call;         // as read on entry to the current call: no_fwd_scan, step_fusions, retract_kernel, pair_retract,
+                         // pair_passes; the comparator's scan
 };
 
 enum RowFamily { RowsCompact, RowsStored, RowsStoredMfma };
@@ -164,6 +168,13 @@ struct KernelPlan {
   // call pairs is then pair_this_call's choice.
   bool pair_retractions;
   int pair_retract;         // CHMC_PAIR_RETRACT of this call
+  // A round of a paired loop in which both problems still iterate runs the passes behind the scan ONCE for both as well
+  // (newton_sweep_pair, jt_lambda_pair in chmc_passes.inc): both are Newton sweeps and J^T lambda updates against the same
+  // compact rows Slots::PB / LF of the proposal slot, so one work item / workgroup serves both iterates from one read of
+  // them, and the latency-bound combine and solve kernels carry both problems' wavefronts in one grid.  Compact rows in
+  // blocks of at most 8 row slots with the one-launch solve (NewtonIvlFsm: at most 64 blocks per chain) in every partition;
+  // every other plan, and CHMC_PAIR_PASSES=0, keeps one launch per problem and pass.  Same bits either way.
+  bool pair_passes;
   PartitionPlan part[2];
 };
 
@@ -254,6 +265,8 @@ inline KernelPlan make_plan(const PlanInput& in) {
     pp.traj_chain = pp.retract_chain && ivl16;
     if (pp.retract_chain) pl.pair_retractions = false;
   }
+  pl.pair_passes = pl.pair_retractions && in.call.pair_passes && in.wave_kernels && pl.rows == RowsCompact && in.rmt <= 8;
+  for (int p = 0; p < in.num_partition; ++p) pl.pair_passes = pl.pair_passes && pl.part[p].newton == NewtonIvlFsm;
   return pl;
 }
 

@@ -1346,6 +1346,24 @@ __global__ void __launch_bounds__(64, CHMC_IVL_WAVES) k_newton_ivl(Sys sy, Slots
   if (m >= bd.nobs) return;
   newton_ivl_body<M, STATE>(sy, sl, w, which, qsel, c, b, m, bd);
 }
+// ... of the iterates of two problems against the same previous point (KernelPlan::pair_passes): a workgroup of two
+// wavefronts per (chain, block, interval), wavefront 0 on the iterate of w0, wavefront 1 on that of w1.  Both ask for the same
+// lines of Slots::PB at the same time on one compute unit; everything else a wavefront touches is its own problem's.  Nothing
+// is shared between the two (no LDS, no barrier): each returns on its own when its chain is out of its problem's loop.
+template <class M>
+__global__ void __launch_bounds__(128, CHMC_IVL_WAVES) k_newton_ivl_pair(Sys sy, Slots sl, Work w0, int which, int qsel, Work w1) {
+  const int wid = blockIdx.x;
+  if (wid >= sy.B * sy.K * sy.NOBS) return;
+  const bool second = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) != 0;
+  const Work w = second ? w1 : w0;
+  const int m = wid % sy.NOBS;
+  const int cbi = sy.order[wid / sy.NOBS];
+  const int c = cbi / sy.K, b = cbi - c * sy.K;
+  if (!newton_select(w, c, which, qsel)) return;
+  const BlockDesc bd = sy.blk[b];
+  if (m >= bd.nobs) return;
+  newton_ivl_body<M, false>(sy, sl, w, which, qsel, c, b, m, bd);
+}
 
 // FACTOR (Newton mode, one 16-row block per chain): the block's LU, Woodbury solve, multipliers and mu_F
 // (k_newton_factor_wave<.., FUSE>) follow in the same launch, fed from the LDS copies of the Gram block and the dc/du rows.
@@ -1505,6 +1523,21 @@ __global__ void __launch_bounds__(64) k_newton_comb(Sys sy, Slots sl, Work w, in
   if (STATE ? !w.ok[c] : !newton_select(w, c, which, qsel)) return;
   const BlockDesc bd = sy.blk[b];
   newton_comb_body<M, RM, STATE, FACTOR>(sy, sl, w, which, qsel, c, b, bd);
+}
+// ... for two problems in one grid, split as k_fwd_scan<.., PAIR> splits its own: the first B K workgroups combine the
+// interval sums of w0, the next B K those of w1 (latency bound: twice the wavefronts take about as long as one set)
+template <class M, int RM>
+__global__ void __launch_bounds__(64) k_newton_comb_pair(Sys sy, Slots sl, Work w0, int which, int qsel, Work w1) {
+  const int n = sy.B * sy.K;
+  const bool second = (int)blockIdx.x >= n;
+  const int wid = second ? (int)blockIdx.x - n : (int)blockIdx.x;
+  if (wid >= n) return;
+  const Work w = second ? w1 : w0;
+  const int cbi = sy.order[wid];
+  const int c = cbi / sy.K, b = cbi - c * sy.K;
+  if (!newton_select(w, c, which, qsel)) return;
+  const BlockDesc bd = sy.blk[b];
+  newton_comb_body<M, RM, false, false>(sy, sl, w, which, qsel, c, b, bd);
 }
 
 // Reverse sweep for 16-row blocks with the row-indexed state in LDS (see k_gld_bwd_wave_ldsrows: at 16 rows the fully
@@ -4366,14 +4399,13 @@ __global__ void __launch_bounds__(64) k_gld_prep_wave(Sys sy, Slots sl, Work w, 
 // the iterate (k_solve_chain_wave<.., 0, 0>), and lane b applies its multipliers to its interval frames (KMuF<RM, X, 0>).
 // What the three kernels passed through HBM (tpad, Ew, Cb, sb) stays in registers; results are bitwise theirs.
 // Three launches of 9-21 us each become one: sym_blk + solve_chain 0.45 -> see DESIGN.md.
+// newton_fsm_body: chain c by the calling wavefront (a chain of the launch: newton_select holds); shared by k_newton_fsm_wave
+// and its form for two problems.
 template <class M, int RM>
-__global__ void __launch_bounds__(64) k_newton_fsm_wave(Sys sy, Slots sl, Work w, int prev, int qsel) {
+__device__ __forceinline__ void newton_fsm_body(const Sys& sy, const Slots& sl, const Work& w, int prev, int qsel, int c) {
   constexpr int U = M::U, X = M::X;
   static_assert(RM <= 8, "one block per lane: the RM x RM matrix lives in registers");
   const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x;
-  if (c >= sy.B) return;
-  if (!newton_select(w, c, prev, qsel)) return;
   const int sp = sl.cur[c] ^ prev;
   const bool has = lane < sy.K;
   const size_t cb = (size_t)c * sy.Kmax + (has ? lane : 0);
@@ -4507,6 +4539,24 @@ __global__ void __launch_bounds__(64) k_newton_fsm_wave(Sys sy, Slots sl, Work w
         }
     }
   }
+}
+template <class M, int RM>
+__global__ void __launch_bounds__(64) k_newton_fsm_wave(Sys sy, Slots sl, Work w, int prev, int qsel) {
+  const int c = blockIdx.x;
+  if (c >= sy.B) return;
+  if (!newton_select(w, c, prev, qsel)) return;
+  newton_fsm_body<M, RM>(sy, sl, w, prev, qsel, c);
+}
+// ... for two problems in one grid (KernelPlan::pair_passes): the first B workgroups serve the chains of w0, the next B those
+// of w1 -- one wavefront per chain and problem, pure latency, so both sets take about as long as one
+template <class M, int RM>
+__global__ void __launch_bounds__(64) k_newton_fsm_wave_pair(Sys sy, Slots sl, Work w0, int prev, int qsel, Work w1) {
+  const bool second = (int)blockIdx.x >= sy.B;
+  const int c = second ? (int)blockIdx.x - sy.B : (int)blockIdx.x;
+  if (c >= sy.B) return;
+  const Work w = second ? w1 : w0;
+  if (!newton_select(w, c, prev, qsel)) return;
+  newton_fsm_body<M, RM>(sy, sl, w, prev, qsel, c);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
