@@ -43,8 +43,22 @@ def notebook_data():
     return dict(T=T, S=S, obs_interval=dt_obs, y=x_seq[S - 1::S, 0].copy(), z_ref=z, x_0_ref=x_0, q_ref=q_ref)
 
 
+def print_path_posterior(pp, pool, path, y, per_obs, verbose=True):
+    """Posterior mean +- sd of the observed channel at the observation times beside the data."""
+    if not verbose:
+        return
+    print(f"path posterior: {pool['n']} draws pooled over the chains, {pp.NP} points per path -> {path}")
+    print("     t      y    E[obs(x(t))] +- sd    hidden component E[x_1(t)] +- sd")
+    for k, yk in enumerate(y):
+        p = (k + 1) * per_obs
+        print(f"  {pp.times[p]:6.2f} {yk:7.3f}   {pool['mean'][p, -1]:7.3f} +- {pool['sd'][p, -1]:.3f}         "
+              f"{pool['mean'][p, 1]:7.3f} +- {pool['sd'][p, 1]:.3f}")
+
+
 def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=20200710, verbose=True,
-        transition="static", init="linear-interpolation"):
+        transition="static", init="linear-interpolation", path_posterior=None):
+    """path_posterior: a stride (a divisor of the steps per observation); the posterior moments of the latent path x(t) at every
+    stride-th step are accumulated over the main phase and written to `path_posterior.npz` next to the traces."""
     if init not in ("linear-interpolation", "gradient-descent"):
         raise ValueError("init must be linear-interpolation or gradient-descent")
     d = notebook_data()
@@ -97,10 +111,15 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
         return {"σ": z[:, 0], "ϵ": z[:, 1], "γ": z[:, 2], "β": z[:, 3], "x_0": m.generate_x_0(z, head[:, 4:6])}
 
     tmp = out_dir or os.path.join(ROOT, "gpurun_out", "fhn_notebook_run")
+    pp = None
+    if path_posterior:
+        from manifold_mcmc_for_diffusions_amd.paths import PathPosterior
+        pp = PathPosterior(ctx, int(path_posterior))
     t0 = time.time()
     if transition == "dynamic":
         from manifold_mcmc_for_diffusions_amd.dynamic import sample_dynamic_chmc
         res = sample_dynamic_chmc(ctx, n_iter, 0.1, seed=seed, n_adapt=n_warm, trace_dir=tmp, trace_func=trace_func,
+                                  path_posterior=pp,
                                   solver=dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10,
                                               max_iters=50, reverse_check_tol=2e-8),
                                   callback=(lambda it, h, a, e, st: (it % 50 == 0) and print(
@@ -109,12 +128,14 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
         res["fail_rate"] = res["integrator_error"]
     else:
       res = sample_static_chmc(ctx, n_iter, n_step, 0.1, seed=seed, n_adapt=n_warm, trace_dir=tmp, trace_func=trace_func,
-                             jitter_length=True,
+                             jitter_length=True, path_posterior=pp,
                              solver=dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10,
                                          max_iters=50, reverse_check_tol=2e-8),  # cell 33
                              callback=(lambda it, h, a, e: (it % 50 == 0) and print(
                                  f"  iter {it:4d} accept {a:.2f} step {e:.3f}", flush=True)) if verbose else None)
     el = time.time() - t0
+    if pp is not None:
+        print_path_posterior(pp, res["path_posterior"], pp.save(tmp), d["y"], d["S"] // pp.stride, verbose)
     ctx.close()
     ref = json.load(open(TABLE))
     # A chain that (almost) never moves in the main phase is not exploring a mode, it is stuck on an unusable start that
@@ -185,5 +206,10 @@ if __name__ == "__main__":
         i = a.index("--init")
         init = a[i + 1]
         del a[i:i + 2]
-    run(*(int(x) for x in a[:4]), init=init, out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
+    stride = None
+    if "--path-posterior" in a:
+        i = a.index("--path-posterior")
+        stride = int(a[i + 1])
+        del a[i:i + 2]
+    run(*(int(x) for x in a[:4]), init=init, path_posterior=stride, out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
         transition=a[5] if len(a) > 5 else "static")

@@ -4,7 +4,10 @@ data, as scripts/sir_model_chmc_experiment.py of the reference sets it up (14 da
 one sub-sequence of 14 observations, sigma_y = 1): batched initial states by the Adam-based finder of the noisy system
 (sde/mici_extensions.py:1679-1801), then batched constrained HMC.
 usage: sir_boarding_school_chmc.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir]
-       [--keyed-init] [--chain-offset N] [--total-chains N]
+       [--keyed-init] [--chain-offset N] [--total-chains N] [--path-posterior STRIDE]
+--path-posterior STRIDE: accumulate the posterior moments of the latent path (S, I and the contact rate at every STRIDE-th step,
+and the observed count) over the main phase; `path_posterior.npz` is written next to the traces and the infected-curve band
+is printed beside the data.
 --keyed-init: the finder's start and restart points are keyed by (seed, global chain, try) instead of drawn from one generator
 for the batch, and the sampler's streams by the global chain: this process runs chains chain-offset .. chain-offset + chains
 - 1 of a job of total-chains chains, and any split of the job into such processes gives every chain the same states."""
@@ -20,13 +23,14 @@ from manifold_mcmc_for_diffusions_amd.context import ChmcContext  # noqa: E402
 from manifold_mcmc_for_diffusions_amd.sampling import sample_static_chmc  # noqa: E402
 
 a = sys.argv[1:]
-opts = {"--keyed-init": False, "--chain-offset": 0, "--total-chains": None}
+opts = {"--keyed-init": False, "--chain-offset": 0, "--total-chains": None, "--path-posterior": None}
 for name in list(opts):
     if name in a:
         i = a.index(name)
         opts[name] = True if name == "--keyed-init" else int(a[i + 1])
         del a[i:i + (1 if name == "--keyed-init" else 2)]
 keyed, chain_offset, total_chains = opts["--keyed-init"], opts["--chain-offset"], opts["--total-chains"]
+path_stride = opts["--path-posterior"]
 B = int(a[0]) if len(a) > 0 else 256
 n_iter = int(a[1]) if len(a) > 1 else 300
 n_warm = int(a[2]) if len(a) > 2 else 100
@@ -56,8 +60,12 @@ def trace_func(head, ham):  # scripts/sir_model_chmc_experiment.py:75-94
             "hamiltonian": ham}
 
 
+pp = None
+if path_stride:
+    from manifold_mcmc_for_diffusions_amd.paths import PathPosterior
+    pp = PathPosterior(ctx, path_stride)
 t0 = time.time()
-res = sample_static_chmc(ctx, n_iter, n_step, 0.05, seed=7, n_adapt=n_warm, n_head=5, jitter_length=True,
+res = sample_static_chmc(ctx, n_iter, n_step, 0.05, seed=7, n_adapt=n_warm, n_head=5, jitter_length=True, path_posterior=pp,
                          chain_offset=chain_offset, total_chains=total_chains if keyed else None,
                          trace_dir=out_dir or os.path.join(ROOT, "gpurun_out", "sir_run"), trace_func=trace_func,
                          callback=lambda it, h, acc, e: (it % 25 == 0) and print(
@@ -69,3 +77,11 @@ print(f"{n_iter} transitions x <= {n_step} steps x {B} chains in {el:.1f} s; fin
       f"{res['fail_rate'][n_warm:].mean():.3f}")
 for k in ("α₀", "β", "γ", "ζ", "ϵ"):
     print(f"  {k:3s} mean {sm['mean'][k]:8.4f} sd {sm['sd'][k]:7.4f}  r_hat {sm['r_hat'][k]:.3f} ess {sm['ess_bulk'][k]:7.0f}")
+if pp is not None:
+    pool, per_obs = res["path_posterior"], ctx.S // pp.stride
+    trace_dir = os.path.dirname(next(iter(res["trace_files"].values())))  # next to the traces
+    print(f"path posterior: {pool['n']} draws pooled over the chains, {pp.NP} points per path -> {pp.save(trace_dir)}")
+    print("   day  count   E[I(t)] +- sd")
+    for k, yk in enumerate(y):
+        p = (k + 1) * per_obs
+        print(f"  {pp.times[p]:5.1f} {yk:6.0f}   {pool['mean'][p, -1]:7.1f} +- {pool['sd'][p, -1]:.1f}")

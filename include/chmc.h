@@ -187,6 +187,29 @@ int chmc_update_x_obs_seq(chmc_ctx* ctx);
 /* SwitchPartitionTransition.sample (:1279-1282): partition = (partition + 1) % num_partition, update x_obs_seq,
  * re-evaluate the state caches */
 int chmc_switch_partition(chmc_ctx* ctx);
+/* The latent path x(t) of every chain: generate_from_model's x_seq (FitzHugh-Nagumo_example.ipynb:316-335), the one function
+ * of that notebook the samplers' head traces cannot give.  For a stride >= 1 that divides num_steps_per_obs,
+ * NP = num_obs * num_steps_per_obs / stride + 1 points per chain: point 0 is x_0 = generate_x_0(generate_z(u), v_0), point p
+ * the state after step p * stride of the recursion from x_0 over the whole chain; observation time t (1-based) is point
+ * t * num_steps_per_obs / stride.  x_seq is [B][NP][X].
+ *   q != NULL (host [B][Q]): the path of those positions, one sequential recursion per chain.
+ *   q == NULL: the path of the chains' current states.  Where the library keeps the compact rows (CHMC_COMPACT_ROWS, the
+ *   default) the stored trajectories of the states seed a time-parallel pass over the whole chain, as in
+ *   chmc_switch_partition; the result equals the sequential recursion to rounding.  sweeps (host [B], may be NULL): sweeps
+ *   that pass needed per chain, 0 where the sequential recursion ran.
+ * Errors: stride < 1 or not a divisor of num_steps_per_obs; no state set (q == NULL). */
+int chmc_generate_x_seq(chmc_ctx* ctx, const double* q, int stride, double* x_seq, int* sweeps);
+/* The same for the current states into a caller-held device buffer x_seq_dev [B][NP][X] (FitzHugh-Nagumo_example.ipynb:316-335). */
+int chmc_generate_x_seq_device(chmc_ctx* ctx, int stride, void* x_seq_dev, int* sweeps);
+/* Running posterior moments of the path (the bands the notebook draws from stored generate_from_model outputs,
+ * FitzHugh-Nagumo_example.ipynb:316-335 and :401, without storing the draws): the path of the current states goes to the
+ * scratch buffer x_seq_dev [B][NP][X], then every chain with mask[c] != 0 (host [B]; NULL = all) folds it into its moments by
+ * Welford's recurrence over the X state components and obs_func(x) (X + 1 channels):
+ *   n[c] += 1;  d = v - mean;  mean += d / n[c];  m2 += d (v - mean).
+ * n_dev [B] (long long), mean_dev, m2_dev [B][NP][X + 1] are the caller's device buffers, zero before the first call; the
+ * buffers of chains with mask[c] == 0 are not touched. */
+int chmc_path_stats_update_device(chmc_ctx* ctx, int stride, const int* mask, void* x_seq_dev, void* n_dev, void* mean_dev,
+                                  void* m2_dev);
 
 /* ---- per-op entry points, evaluated at the current state ------------------------------------------------
  * Internally the library keeps the dc/dv rows of a state in a compact factored form (per step a row-independent X x V
@@ -377,7 +400,10 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *   out80[73]      rounds among those of [70] whose passes behind the scan served both problems as well: interval sums,
  *                  combine, solve and J^T lambda update one launch each for the pair (compact rows in blocks of at most 8 row
  *                  slots, at most 64 blocks per chain; CHMC_PAIR_PASSES=0 keeps one launch per problem and pass)
- *   out80[74 .. 79] reserved (0)
+ *   out80[74]      launches of the time-parallel path scan (k_path_par: chmc_generate_x_seq* / chmc_path_stats_update_device
+ *                  on the current states with the compact rows allocated)
+ *   out80[75]      launches of the sequential path scan (KPath: a caller's q, or CHMC_COMPACT_ROWS=0)
+ *   out80[76 .. 79] reserved (0)
  * Synchronises the context's stream. */
 int chmc_get_diagnostics(chmc_ctx* ctx, long long* out80);
 

@@ -61,6 +61,9 @@ SYMBOLS = [
     ("chmc_get_head", C.c_int, [C.c_void_p, C.c_int, dp]),
     ("chmc_update_x_obs_seq", C.c_int, [C.c_void_p]),
     ("chmc_switch_partition", C.c_int, [C.c_void_p]),
+    ("chmc_generate_x_seq", C.c_int, [C.c_void_p, dp, C.c_int, dp, ip]),
+    ("chmc_generate_x_seq_device", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, ip]),
+    ("chmc_path_stats_update_device", C.c_int, [C.c_void_p, C.c_int, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("chmc_constr", C.c_int, [C.c_void_p, dp]),
     ("chmc_jacob_constr_blocks", C.c_int, [C.c_void_p, dp, dp]),
     ("chmc_chol_gram_blocks", C.c_int, [C.c_void_p, dp, dp]),

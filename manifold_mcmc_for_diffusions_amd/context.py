@@ -43,6 +43,7 @@ class ChmcContext:
         self.variable_sigma = isinstance(sigma, str)
         self.sigma = sigma
         self.device = int(device)
+        self._obs_interval = float(obs_interval)
         self.partition = 0
         self.blocks = []
         keys = ("obs0", "nobs", "first", "last", "row0", "nrows", "ny", "col0", "ncols", "step0", "nsteps", "_")
@@ -227,6 +228,38 @@ class ChmcContext:
     def switch_partition(self):
         check(self.L.chmc_switch_partition(self.h), "chmc_switch_partition")
         self.partition = (self.partition + 1) % self.num_partition
+
+    # ---- the latent path (chmc_generate_x_seq*, chmc_path_stats_update_device; paths.py keeps the running moments)
+    def path_points(self, stride=1):
+        """(NP, times): the number of points of a path at `stride` and their times p * stride * delta (time 0: x_0)."""
+        stride = int(stride)
+        if stride < 1 or self.S % stride:
+            raise ValueError(f"stride must be at least 1 and divide num_steps_per_obs = {self.S}")
+        n_p = self.T * self.S // stride + 1
+        return n_p, np.arange(n_p) * (stride * self._obs_interval / self.S)
+
+    def generate_x_seq(self, stride=1, q=None, return_sweeps=False):
+        """x_seq [B, NP, X] of generate_from_model (FitzHugh-Nagumo_example.ipynb:316-335): the latent path of the current
+        states, or of the positions `q` [B, Q].  return_sweeps: also the sweeps of the time-parallel pass per chain (0 where
+        the sequential recursion ran)."""
+        n_p = self.T * self.S // max(int(stride), 1) + 1
+        q = None if q is None else self._bq(q, "q")
+        out = np.empty((self.B, n_p, self.X))
+        sw = np.zeros(self.B, dtype=np.int32)
+        check(self.L.chmc_generate_x_seq(self.h, ptr(q), int(stride), ptr(out), iptr(sw)), "chmc_generate_x_seq")
+        return (out, sw) if return_sweeps else out
+
+    def generate_x_seq_device(self, stride, x_seq_dev_ptr, return_sweeps=False):
+        sw = np.zeros(self.B, dtype=np.int32) if return_sweeps else None
+        check(self.L.chmc_generate_x_seq_device(self.h, int(stride), C.c_void_p(x_seq_dev_ptr), iptr(sw)),
+              "chmc_generate_x_seq_device")
+        return sw
+
+    def path_stats_update_device(self, stride, x_seq_dev_ptr, n_dev_ptr, mean_dev_ptr, m2_dev_ptr, mask=None):
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        check(self.L.chmc_path_stats_update_device(self.h, int(stride), iptr(m), C.c_void_p(x_seq_dev_ptr),
+                                                   C.c_void_p(n_dev_ptr), C.c_void_p(mean_dev_ptr), C.c_void_p(m2_dev_ptr)),
+              "chmc_path_stats_update_device")
 
     # ---- per-op
     @property
@@ -472,7 +505,8 @@ class ChmcContext:
         return dict(par_scan=v[:64], gram_mfma_launches=int(v[64]), gram_valu_launches=int(v[65]),
                     retract_kernel_launches=int(v[66]), traj_kernel_launches=int(v[67]),
                     newton_fsm_launches=int(v[68]), newton_factor8_launches=int(v[69]), pair_scan_rounds=int(v[70]),
-                    newton_scan_launches=int(v[71]), newton_rounds=int(v[72]), extra=v[68:80])
+                    newton_scan_launches=int(v[71]), newton_rounds=int(v[72]), path_par_launches=int(v[74]),
+                    path_seq_launches=int(v[75]), extra=v[68:80])
 
     def counters(self):
         out = (C.c_longlong * 8)()

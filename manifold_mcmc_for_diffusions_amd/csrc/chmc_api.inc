@@ -49,6 +49,9 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   double* d_m0 = nullptr;    // [3][U][U] M_0, M_0^-1, chol(M_0) of the block metric
   double *d_tree_part = nullptr, *d_tree_out = nullptr;  // chmc_tree_leaf: workgroup partials, per-chain results
   int* d_tree_mask = nullptr;                            // [2][B] run, take
+  int* d_path_ints = nullptr;       // chmc_generate_x_seq* / chmc_path_stats_update_device: [2][B] sweeps, mask
+  double* d_path_out = nullptr;     // chmc_generate_x_seq: staging of the host form's output, d_path_cap doubles
+  size_t d_path_cap = 0;
   TreeState tree{};                                      // chmc_tree_begin / _subtree / _step: per-chain tree decisions
   bool have_tree = false;
   bool rows_fresh = false;  // Slots::Jv holds the full rows of the current states (see ensure_rows)
@@ -62,7 +65,8 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
                               // served two problems (one k_fwd_scan<.., PAIR> launch), [7] forward-scan launches of the
                               // lock-step Newton loops, [8] rounds enqueued by them, per problem, [9] rounds of a paired loop
                               // whose passes behind the scan served two problems as well (KernelPlan::pair_passes: interval
-                              // sums, combine, solve and J^T lambda update one launch each; a subset of [6])
+                              // sums, combine, solve and J^T lambda update one launch each; a subset of [6]), [10] launches of
+                              // the time-parallel path scan, [11] of the sequential one (KPath)
   // Paired retractions (KernelPlan::pair_retractions): the second problem of run_projection_pair -- the forward retraction of
   // the NEXT step -- works in a Work of its own: every array a round's kernels, KNewtonBegin, KCheck or KNewtonEnd write
   // (pair_alloc), everything they only read shared with `w`.  Whole batch only, allocated on first use.
@@ -1073,6 +1077,58 @@ extern "C" int chmc_switch_partition(chmc_ctx* ctx) {
   state_eval(ctx, 0);
   ctx->mom_tangent = false;  // the momentum was tangent to the other partition's constraint set
   CHMC_LEAVE("chmc_switch_partition")
+}
+
+// the latent path (include/chmc.h): path_scan picks the pass; q_dev null = current states
+static int path_check(chmc_ctx* ctx, const char* fn, int stride, bool current) {
+  if (stride < 1 || ctx->sy.S % stride != 0)
+    return fail(std::string(fn) + ": stride must be at least 1 and divide num_steps_per_obs");
+  if (current && !ctx->have_state) return fail(std::string(fn) + ": no state has been set");
+  return 0;
+}
+static void path_run(chmc_ctx* ctx, const double* q_dev, int stride, double* out_dev, int* sweeps) {
+  if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)ctx->sy.B);
+  dispatch(ctx, [&](auto inst) { path_scan<typename decltype(inst)::M>(ctx, q_dev, stride, out_dev, sweeps ? ctx->d_path_ints : nullptr); });
+  if (sweeps) d2h(sweeps, ctx->d_path_ints, sizeof(int) * ctx->sy.B);
+}
+extern "C" int chmc_generate_x_seq(chmc_ctx* ctx, const double* q, int stride, double* x_seq, int* sweeps) {
+  CHMC_ENTER("chmc_generate_x_seq")
+  if (!x_seq) return fail("chmc_generate_x_seq: null output");
+  if (path_check(ctx, "chmc_generate_x_seq", stride, q == nullptr)) return -1;
+  const Sys& sy = ctx->sy;
+  const size_t n = (size_t)sy.B * (sy.T * sy.S / stride + 1) * sy.X;
+  if (ctx->d_path_cap < n) ctx->d_path_out = alloc<double>(ctx, n), ctx->d_path_cap = n;
+  if (q) h2d(ctx->w.qb, q, sizeof(double) * (size_t)sy.B * sy.Q);
+  path_run(ctx, q ? ctx->w.qb : nullptr, stride, ctx->d_path_out, sweeps);
+  d2h(x_seq, ctx->d_path_out, sizeof(double) * n);
+  CHMC_LEAVE("chmc_generate_x_seq")
+}
+extern "C" int chmc_generate_x_seq_device(chmc_ctx* ctx, int stride, void* x_seq_dev, int* sweeps) {
+  CHMC_ENTER("chmc_generate_x_seq_device")
+  if (!x_seq_dev) return fail("chmc_generate_x_seq_device: null output");
+  if (path_check(ctx, "chmc_generate_x_seq_device", stride, true)) return -1;
+  path_run(ctx, nullptr, stride, (double*)x_seq_dev, sweeps);
+  CHMC_LEAVE("chmc_generate_x_seq_device")
+}
+extern "C" int chmc_path_stats_update_device(chmc_ctx* ctx, int stride, const int* mask, void* x_seq_dev, void* n_dev,
+                                             void* mean_dev, void* m2_dev) {
+  CHMC_ENTER("chmc_path_stats_update_device")
+  if (!x_seq_dev || !n_dev || !mean_dev || !m2_dev) return fail("chmc_path_stats_update_device: null argument");
+  if (path_check(ctx, "chmc_path_stats_update_device", stride, true)) return -1;
+  const Sys& sy = ctx->sy;
+  const int NP = sy.T * sy.S / stride + 1;
+  path_run(ctx, nullptr, stride, (double*)x_seq_dev, nullptr);
+  int* d_mask = nullptr;
+  if (mask) h2d(d_mask = ctx->d_path_ints + sy.B, mask, sizeof(int) * sy.B);
+  dispatch(ctx, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    const KPathWelford<M> f{NP, 0, d_mask, (const double*)x_seq_dev, (long long*)n_dev, (double*)mean_dev, (double*)m2_dev};
+    KPathWelford<M> g = f;
+    g.phase = 1;
+    launch(f, sy.B, 8);
+    launch(g, (long)sy.B * NP, 8);
+  });
+  CHMC_LEAVE("chmc_path_stats_update_device")
 }
 
 // padded [B][Kmax][RM] <-> packed [B][C] conversion of block-row vectors (host side, small)

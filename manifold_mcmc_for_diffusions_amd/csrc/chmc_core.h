@@ -720,6 +720,74 @@ struct KXobs {
   }
 };
 
+// generate_from_model's x_seq (FitzHugh-Nagumo_example.ipynb:316-335): the latent path of every chain, one work item per
+// chain, the plain recursion from x_0.  Point 0 is x_0, point p the state after step p * stride; out [B][T S / stride + 1][X].
+// qext: caller's positions [B][Q], or null for the chains' current states.
+template <class M>
+struct KPath {
+  Sys sy;
+  Slots sl;
+  const double* qext;
+  int stride;
+  double* out;
+  CHMC_HD void operator()(int c) const {
+    constexpr int X = M::X, V = M::V;
+    const double* q = (qext ? qext : pick(sl.q, sl.cur[c])) + (size_t)c * sy.Q;
+    ChainConsts<M> cc;
+    cc.init(q, sy.dl);
+    double x[X], xn[X];
+    M::gx0(cc.z, q + sy.U, x);
+    const double* v = q + sy.U + sy.V0;
+    const int L = sy.T * sy.S;
+    double* o = out + (size_t)c * (L / stride + 1) * X;
+    for (int a = 0; a < X; ++a) o[a] = x[a];
+    int left = stride;
+    for (int s = 0; s < L; ++s) {
+      M::step(cc.k, x, v + (size_t)s * V, xn);
+      for (int a = 0; a < X; ++a) x[a] = xn[a];
+      if (--left == 0) {
+        o += X;
+        for (int a = 0; a < X; ++a) o[a] = x[a];
+        left = stride;
+      }
+    }
+  }
+};
+
+// Running moments of the paths (Welford): channels are the X state components and obs(x).  phase 0: one work item per
+// chain counts the draw, n[c] += 1; phase 1 (a launch behind it): one work item per (chain, point) folds the point of
+// x [B][NP][X] into mean / m2 [B][NP][X + 1] with the new count.  Chains with mask[c] == 0 are not touched (null: all).
+template <class M>
+struct KPathWelford {
+  int NP, phase;
+  const int* mask;
+  const double* x;
+  long long* n;
+  double *mean, *m2;
+  CHMC_HD void operator()(int tid) const {
+    constexpr int X = M::X, XC = X + 1;
+    const int c = phase ? tid / NP : tid;
+    if (mask && !mask[c]) return;
+    if (!phase) {
+      n[c] += 1;
+      return;
+    }
+    const double* xp = x + (size_t)tid * X;
+    double v[XC];
+    for (int a = 0; a < X; ++a) v[a] = xp[a];
+    v[X] = M::obs(xp);
+    const double nn = (double)n[c];
+    double* mp = mean + (size_t)tid * XC;
+    double* sp = m2 + (size_t)tid * XC;
+    for (int a = 0; a < XC; ++a) {
+      const double d = v[a] - mp[a];
+      const double mu = mp[a] + d / nn;
+      mp[a] = mu;
+      sp[a] += d * (v[a] - mu);
+    }
+  }
+};
+
 // Forward half of conditioned_diffusion_neg_log_dens_and_grad (:82-205, the unconstrained-HMC comparator of the
 // reference's experiments) when the steps per observation do not tile by 8 (otherwise k_fwd_scan runs the whole
 // chain as one block): the full T * S-step scan of one chain from q = [u | v_0 | v_seq], storing the trajectory.

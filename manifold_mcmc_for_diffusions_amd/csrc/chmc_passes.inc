@@ -42,6 +42,14 @@ static void jt_lambda(chmc_ctx* c, int which, int qsel, int psel, bool have_mu_f
                 sy.T * sy.S + sy.V0 + (sy.noisy ? sy.T : 0), sy.B, 4);
 }
 
+// the latent path by the plain recursion, one work item per chain (KPath): of the caller's positions `q`, or of the current
+// states (null) where no time-parallel pass is available; it reports no sweeps (0)
+template <class M>
+static void path_seq(chmc_ctx* c, const double* q, int stride, double* out, int* sweeps) {
+  if (sweeps) dev_zero(sweeps, sizeof(int) * c->sy.B);
+  launch(KPath<M>{c->sy, c->sl, q, stride, out}, c->sy.B, 7), c->diag[11]++;
+}
+
 #ifdef CHMC_WAVE_KERNELS
 constexpr bool kWaveKernels = true;  // PlanInput::wave_kernels of every context of this build
 // chain-level Woodbury solve: one wavefront per chain up to 64 blocks
@@ -334,6 +342,14 @@ template <class M>
 static void xobs_par(chmc_ctx* c) {
   launch_blocks(k_xobs_par<M>, (long)c->sy.B, 64, 0, c->sy, c->sl, c->d_xobs);
 }
+// chmc_generate_x_seq*: the latent path of the current states by the time-parallel pass where chmc_switch_partition has one
+// (compact rows allocated and a state set: the stored trajectories seed it), else -- and for a caller's q, which has no
+// stored trajectory -- by the plain recursion
+template <class M>
+static void path_scan(chmc_ctx* c, const double* q, int stride, double* out, int* sweeps) {
+  if (q || !(c->plan.pb_allocated && c->have_state)) return path_seq<M>(c, q, stride, out, sweeps);
+  launch_blocks(k_path_par<M>, (long)c->sy.B, 64, 7, c->sy, c->sl, stride, out, sweeps), c->diag[10]++;
+}
 // the comparator target (nld_core): forward scan of the whole chain as the one block of `sf` (KernelPlan::nld), adjoint sweep
 template <class M, int RM>
 static void nld_sweeps(chmc_ctx* c, const Sys& sf, int QH, int use_gaussian_splitting, double* grad_dev) {
@@ -452,6 +468,10 @@ static void gd_grad(chmc_ctx* c, long tasks, const double* q, const double* cres
 // per-chain kernels
 template <class M>
 static void xobs_par(chmc_ctx*) { no_wave_kernels("the partition switch's time-parallel pass"); }
+template <class M>
+static void path_scan(chmc_ctx* c, const double* q, int stride, double* out, int* sweeps) {
+  path_seq<M>(c, q, stride, out, sweeps);
+}
 template <class M, int RM>
 static void nld_sweeps(chmc_ctx*, const Sys&, int, int, double*) { no_wave_kernels("the comparator target"); }
 template <class M, int RM, class... Args>

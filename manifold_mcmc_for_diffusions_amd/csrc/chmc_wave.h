@@ -4796,6 +4796,266 @@ __global__ void __launch_bounds__(64) k_xobs_par(Sys sy, Slots sl, double* xobs_
   }
 }
 
+// generate_from_model's x_seq (FitzHugh-Nagumo_example.ipynb:316-335) of every chain's CURRENT state: point 0 is x_0, point p
+// the state after step p * stride of the whole chain's recursion; out [B][NP = T S / stride + 1][X].  One wavefront per chain.
+// Phase 1 settles the 64 segment start states by multiple shooting from the stored trajectory -- k_xobs_par's sweeps, its
+// settled criterion and its sequential fallback, written out again here so that kernel's code stays what it is.  Phase 2 is
+// a plain pass: every lane integrates its segment once more from its settled start state (within 1e-13 relative of the
+// sequential recursion's state there) and emits the states whose step index is a multiple of `stride`.
+// Emit: a lane's points are contiguous in `out`, but the 64 lanes write 64 regions, and a lane-per-region store instruction
+// touches 64 lines for 16 or 24 bytes each.  A lane therefore parks its doubles in its row of an LDS ring, indexed by the
+// global double index modulo the ring, and after every 8-step window the wavefront writes out the 128-byte lines that are
+// complete: 8 lanes per line, 16 bytes each, 8 whole lines per store instruction.  Only the doubles before a region's first
+// line boundary and behind its last one (fewer than 16 each, twice per lane and call) are stored by the lane itself.
+// Row stride RING + 1 doubles: ds_write_b64 banks are (a / 4) % 32, rows that are 2 (RING + 1) = 2 (mod 32) dwords apart put 16
+// lanes that write the same ring slot on 16 different bank pairs.
+// CHMC_PATH_DIRECT_STORES (build switch, A/B only): every double is stored by its lane, no ring.  Measured at stride 1
+// (profiles/path_posterior_timing.txt): slower for X = 3 (SIR, 1 024 chains: 83.6 against 78.3 us), faster for X = 2, where a
+// point is one 16-byte store (configs[1]: 148 against 251 us -- the flush below costs about 1.4 us per window).
+// sweeps (may be null): sweeps to convergence per chain, 0 for the sequential fallback.
+#ifdef CHMC_PATH_DIRECT_STORES
+constexpr bool kPathRing = false;
+#else
+constexpr bool kPathRing = true;
+#endif
+template <class M>
+__global__ void __launch_bounds__(64) k_path_par(Sys sy, Slots sl, int stride, double* x_seq, int* sweeps) {
+  constexpr int X = M::X, V = M::V, MAXS = 8, CH = 8;
+  constexpr int RING = X <= 2 ? 32 : 64, RS = RING + 1, MAXL = (15 + CH * X) / 16;
+  static_assert(16 + CH * X <= RING, "a window's doubles and an open line fit the ring");
+  __shared__ double ring[64 * RS];
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x;
+  if (c >= sy.B) return;
+  const int s_ = sl.cur[c];
+  const int S = sy.S, L = sy.T * sy.S;
+  const int NP = L / stride + 1;
+  const double* q = pick(sl.q, s_) + (size_t)c * sy.Q;
+  const double* trj = pick(sl.traj, s_) + (size_t)c * sy.TRJ;
+  const double* vbase = q + sy.U + sy.V0;
+  double* out = x_seq + (size_t)c * NP * X;
+  ChainConsts<M> cc;
+  cc.init(q, sy.dl);
+  double x0[X];
+  M::gx0(cc.z, q + sy.U, x0);
+  const int m = (L + 63) >> 6;
+  const int s0 = lane * m, s1 = (s0 + m < L ? s0 + m : L);
+  const bool have = s0 < L;
+  double Ul[X];
+  {
+    const int b0 = have ? sy.obs2blk[s0 / S] : 0;  // step s of block b sits at trajectory entry s + CHMC_TPAD b
+#pragma unroll
+    for (int a = 0; a < X; ++a) Ul[a] = lane == 0 ? x0[a] : (have ? trj[(size_t)(s0 + CHMC_TPAD * b0) * X + a] : 0.0);
+  }
+  // noise increments of eight steps, requested one window ahead (addresses past the chain are clamped to its last step)
+  auto fetch = [&](int base, double* dst) {
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      int sj = base + j;
+      sj = sj < L ? sj : L - 1;
+#pragma unroll
+      for (int a = 0; a < V; ++a) dst[j * V + a] = vbase[(size_t)sj * V + a];
+    }
+  };
+  // ---- phase 1: settle the segment start states
+  bool converged = false;
+  int nsweep = 0;
+  for (int sweep = 0; sweep < MAXS && !converged; ++sweep) {
+    double x[X], P[X * X];
+#pragma unroll
+    for (int a = 0; a < X; ++a) x[a] = Ul[a];
+#pragma unroll
+    for (int i = 0; i < X * X; ++i) P[i] = (i / X == i % X) ? 1.0 : 0.0;
+    double vb[2][CH * V];
+    auto run = [&](int base, const double* src) {
+#pragma unroll
+      for (int j = 0; j < CH; ++j) {
+        const int s = base + j;
+        if (s < s1) {
+          double vv[V], A[X * X], Bm[X * V], xn[X], Pn[X * X];
+#pragma unroll
+          for (int a = 0; a < V; ++a) vv[a] = src[j * V + a];
+          M::jac_ab(cc.k, x, vv, A, Bm);
+          M::step(cc.k, x, vv, xn);
+          matmul_xx<X>(A, P, Pn);
+#pragma unroll
+          for (int i = 0; i < X * X; ++i) P[i] = Pn[i];
+#pragma unroll
+          for (int a = 0; a < X; ++a) x[a] = xn[a];
+        }
+      }
+    };
+    if (have) fetch(s0, vb[0]);
+    for (int base = s0; base < s1; base += 2 * CH) {  // (two windows per trip: the buffers are indexed statically)
+      fetch(base + CH, vb[1]);
+      run(base, vb[0]);
+      fetch(base + 2 * CH, vb[0]);
+      run(base + CH, vb[1]);
+    }
+    double ec[X], Pc[X * X], Unext[X];
+#pragma unroll
+    for (int a = 0; a < X; ++a) Unext[a] = __shfl_down(Ul[a], 1, 64);
+    const bool junction = have && s1 < L;
+#pragma unroll
+    for (int a = 0; a < X; ++a) ec[a] = junction ? x[a] - Unext[a] : 0.0;
+#pragma unroll
+    for (int i = 0; i < X * X; ++i) Pc[i] = junction ? P[i] : ((i / X == i % X) ? 1.0 : 0.0);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      double Pp[X * X], ep[X], Pn[X * X];
+#pragma unroll
+      for (int i = 0; i < X * X; ++i) Pp[i] = __shfl_up(Pc[i], o, 64);
+#pragma unroll
+      for (int a = 0; a < X; ++a) ep[a] = __shfl_up(ec[a], o, 64);
+      if (lane >= o) {
+#pragma unroll
+        for (int a = 0; a < X; ++a) {
+          double tt = ec[a];
+#pragma unroll
+          for (int d = 0; d < X; ++d) tt += Pc[a * X + d] * ep[d];
+          ec[a] = tt;
+        }
+        matmul_xx<X>(Pc, Pp, Pn);
+#pragma unroll
+        for (int i = 0; i < X * X; ++i) Pc[i] = Pn[i];
+      }
+    }
+    double dl[X], Un[X];
+#pragma unroll
+    for (int a = 0; a < X; ++a) {
+      const double up = __shfl_up(ec[a], 1, 64);
+      dl[a] = lane == 0 ? 0.0 : up;
+    }
+    bool still = true;
+#pragma unroll
+    for (int a = 0; a < X; ++a) still = still && dl[a] == 0.0;
+#pragma unroll
+    for (int a = 0; a < X; ++a) {
+      double tt = 0.0;
+#pragma unroll
+      for (int d = 0; d < X; ++d) tt += P[a * X + d] * dl[d];
+      Un[a] = still ? x[a] : x[a] + tt;
+    }
+    int unsettled = 0;
+#pragma unroll
+    for (int a = 0; a < X; ++a) {
+      const double nu = __shfl_up(Un[a], 1, 64);
+      if (lane > 0 && have) {
+        const double old = Ul[a];
+        const bool same = nu == old || (nu != nu && old != old);
+        const bool close = fabs(nu - old) <= 1e-13 * (fabs(nu) > 1.0 ? fabs(nu) : 1.0);
+        unsettled |= !(same || close);
+        Ul[a] = nu;
+      }
+    }
+    converged = __ballot(unsettled) == 0ULL;
+    nsweep = sweep + 1;
+  }
+  if (sweeps && lane == 0) sweeps[c] = converged ? nsweep : 0;
+  if (lane == 0) {
+#pragma unroll
+    for (int a = 0; a < X; ++a) out[a] = x0[a];
+  }
+  if (!converged) {  // sequential recursion on lane 0
+    if (lane == 0) {
+      double x[X], xn[X];
+#pragma unroll
+      for (int a = 0; a < X; ++a) x[a] = x0[a];
+      double* o = out;
+      int left = stride;
+      for (int s = 0; s < L; ++s) {
+        M::step(cc.k, x, vbase + (size_t)s * V, xn);
+#pragma unroll
+        for (int a = 0; a < X; ++a) x[a] = xn[a];
+        if (--left == 0) {
+          o += X;
+#pragma unroll
+          for (int a = 0; a < X; ++a) o[a] = x[a];
+          left = stride;
+        }
+      }
+    }
+    return;
+  }
+  // ---- phase 2: the plain pass from the settled start states, emitting through the ring
+  // gi: index of the lane's next double, counted from the 128-byte line boundary at or below `out` (off0 doubles below it);
+  // the lane's first point is the first p with p * stride > s0
+  const int off0 = (int)(((unsigned long long)out >> 3) & 15);
+  int gi = off0 + (s0 / stride + 1) * X;
+  bool started = kPathRing && (gi & 15) == 0;  // the lane has reached a line boundary: its doubles go through the ring from there
+  int gf = gi;                    // first double not yet written out (a line boundary once started)
+  double* row = ring + lane * RS;
+  double x[X];
+#pragma unroll
+  for (int a = 0; a < X; ++a) x[a] = Ul[a];
+  int left = stride - s0 % stride;  // steps until the next emitted state
+  double vb[2][CH * V];
+  auto run = [&](int base, const double* src) {
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      const int s = base + j;
+      if (s < s1) {
+        double vv[V], xn[X];
+#pragma unroll
+        for (int a = 0; a < V; ++a) vv[a] = src[j * V + a];
+        M::step(cc.k, x, vv, xn);
+#pragma unroll
+        for (int a = 0; a < X; ++a) x[a] = xn[a];
+        if (--left == 0) {
+          left = stride;
+#pragma unroll
+          for (int a = 0; a < X; ++a) {
+            if (started)
+              row[gi & (RING - 1)] = x[a];
+            else
+              out[gi - off0] = x[a];
+            ++gi;
+            if (kPathRing && !started && (gi & 15) == 0) started = true, gf = gi;
+          }
+        }
+      }
+    }
+  };
+  auto flush = [&]() {  // (uniform: every lane calls it after every window)
+    const int nl = started ? (gi >> 4) - (gf >> 4) : 0;
+    if (__ballot(nl > 0) == 0ULL) return;
+    __syncthreads();
+    const int sub = lane >> 3, k = lane & 7;
+#pragma unroll
+    for (int grp = 0; grp < 8; ++grp) {
+      const int r = grp * 8 + sub;
+      const int gf_r = __shfl(gf, r, 64), nl_r = __shfl(nl, r, 64);
+      const double* rr = ring + r * RS;
+#pragma unroll
+      for (int j = 0; j < MAXL; ++j) {
+        if (j < nl_r) {
+          const int idx = gf_r + 16 * j + 2 * k;
+          d2_t v;
+          v.x = rr[idx & (RING - 1)];
+          v.y = rr[(idx + 1) & (RING - 1)];
+          *(d2_t*)(out + (idx - off0)) = v;
+        }
+      }
+    }
+    gf += 16 * nl;
+    __syncthreads();
+  };
+  const int nwin = (m + CH - 1) / CH;
+  fetch(s0, vb[0]);
+  for (int w = 0; w < nwin; w += 2) {
+    const int base = s0 + w * CH;
+    fetch(base + CH, vb[1]);
+    run(base, vb[0]);
+    flush();
+    fetch(base + 2 * CH, vb[0]);
+    run(base + CH, vb[1]);
+    flush();
+  }
+  if (started) {  // the doubles behind the lane's last complete line
+    for (int g = gf; g < gi; ++g) out[g - off0] = row[g & (RING - 1)];
+  }
+}
+
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Is chain c part of this scan launch?  use_nw 0: chains with work.ok; 1: chains of the Newton loop (work.nw == 1).

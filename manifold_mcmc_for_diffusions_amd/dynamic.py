@@ -150,7 +150,8 @@ class DynamicTransition:
 
 
 def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0, total_chains=None, n_head=6,
-                        trace_dir=None, trace_func=None, callback=None, per_chain_step_size=True, **kw):
+                        trace_dir=None, trace_func=None, callback=None, per_chain_step_size=True, path_posterior=None,
+                        **kw):
     """Momentum refresh -> dynamic transition -> partition switch, `n_iter` times for all chains of `ctx`, with
     dual-averaging step-size adaptation on the tree's accept statistic during warm-up: the reference's sampling loop
     (scripts/utils.py:292-306, 338-365), batched.  As in Mici every chain adapts its own step size during warm-up (the
@@ -158,7 +159,9 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     taken over the chains of all ranks.  per_chain_step_size=False: ONE step size adapted on the accept statistic
     averaged over all chains (round 2's scheme): the batched trees of a doubling then all have the same number of leaves to
     offer, which keeps the lock-step batch full during warm-up (the FitzHugh-Nagumo example: 30 k against 24 k leapfrog
-    steps/s end to end), but a chain that starts where that step size is far too long never moves."""
+    steps/s end to end), but a chain that starts where that step size is far too long never moves.
+    path_posterior: a `paths.PathPosterior` of `ctx`; the latent path of every post-warm-up state (after the partition
+    switch) is folded into its running moments, and out["path_posterior"] is its `pooled()` result."""
     import time
     from .sampling import DualAveragingStepSize, PerChainDualAveragingStepSize, _mean_over_all_chains
     tr = DynamicTransition(ctx, step_size, seed, chain_offset=chain_offset, total_chains=total_chains, **kw)
@@ -181,6 +184,8 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
         ctx.sample_momentum(seed, it + 1, chain_offset)
         st = tr.sample(it)
         ctx.switch_partition()
+        if path_posterior is not None and it >= n_adapt:
+            path_posterior.update()
         heads[it] = ctx.get_head(n_head)
         if trace_dir is not None:
             from .traces import TraceWriter
@@ -217,6 +222,8 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     out = dict(heads=heads, accept_stat=acc_hist, step_size=eps_hist, n_step=nstep_hist, integrator_error=err_hist,
                final_step_size=float(np.mean(tr.step_size)), adapted_step_sizes=adapted, chain_outcomes_dynamic=outcome,
                per_chain={k: v / n_main for k, v in per_chain.items()})
+    if path_posterior is not None:
+        out["path_posterior"] = path_posterior.pooled()
     if writer is not None:
         from .traces import save_summary
         writer.flush()

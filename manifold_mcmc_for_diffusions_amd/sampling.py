@@ -81,7 +81,8 @@ def _mean_over_all_chains(local_sum, local_count):
 
 def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_adapt=0, solver=None, rng=None,
                        n_head=6, callback=None, trace_dir=None, trace_func=None, total_chains=None,
-                       jitter_length=False, metric_adapter=None, metric_window=0.75, metric_skip=0.25):
+                       jitter_length=False, metric_adapter=None, metric_window=0.75, metric_skip=0.25,
+                       path_posterior=None):
     """Runs n_iter transitions on all chains of `ctx`; returns traces of the first `n_head` position components
     ([n_iter, B, n_head]), accept statistics and the step size used.  Directions are sampled per chain and
     transition (forward / backward in time), failed trajectories are rejected.
@@ -100,7 +101,9 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     splitting only).  It sees the warm-up draws between the fractions `metric_skip` (the initial transient is left
     out, like the first window of a staged warm-up) and `metric_window` of the warm-up; the block metric it produces
     (per-chain statistics combined over all chains and ranks) is installed with `ctx.set_metric` there, and the
-    remaining warm-up transitions re-tune the step size for the new metric."""
+    remaining warm-up transitions re-tune the step size for the new metric.
+    path_posterior: a `paths.PathPosterior` of `ctx`; the latent path of every post-warm-up state (after the partition
+    switch) is folded into its running moments, and out["path_posterior"] is its `pooled()` result."""
     solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
                   reverse_check_tol=2e-8) if solver is None else solver
     rng = np.random.default_rng(seed) if rng is None else rng
@@ -159,6 +162,8 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
             outcome[np.arange(B), col] += 1
         ctx.restore((~accept).astype(np.int32))
         ctx.switch_partition()
+        if path_posterior is not None and it >= n_adapt:
+            path_posterior.update()
         heads[it] = ctx.get_head(n_head)
         if trace_dir is not None:
             vals = {k: np.asarray(v) for k, v in trace_func(heads[it], ctx.hamiltonian()[:, 0]).items()}
@@ -183,6 +188,8 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
             callback(it, heads[it], prob.mean(), step_size)
     out = dict(heads=heads, accept_stat=acc_hist, step_size=eps_hist, fail_rate=fail_hist, final_step_size=step_size,
                chain_outcomes=outcome)
+    if path_posterior is not None:
+        out["path_posterior"] = path_posterior.pooled()
     if n_metric:
         out["metric_M_0"] = None if ctx.M_0 is None else ctx.M_0.copy()
     if writer is not None:

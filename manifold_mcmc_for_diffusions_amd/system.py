@@ -495,3 +495,27 @@ def conditioned_diffusion_neg_log_dens_and_grad(obs_interval, num_steps_per_obs,
         return g, val
 
     return neg_log_dens, grad_neg_log_dens
+
+
+def generate_from_model(system, q, stride=1):
+    """generate_from_model(q, δ, ...) -> x_seq, y_seq, z, x_0 of the reference's notebook (FitzHugh-Nagumo_example.ipynb:316-335)
+    for one position q [Q] or a batch [n, Q]: the latent path by the library's path scan (x_seq[..., p, :] is the state after
+    step p * stride, point 0 being x_0), y_seq = obs_func of the path at the observation times (noise-free), z and x_0 from the
+    model's host functions."""
+    c, md = system.ctx, system.model_dict
+    q = np.asarray(q, dtype=np.float64)
+    qq = np.atleast_2d(q)
+    if qq.ndim != 2 or qq.shape[1] != c.Q:
+        raise ValueError(f"q must have shape ({c.Q},) or (n, {c.Q})")
+    n_p, _ = c.path_points(stride)
+    x_seq = np.empty((qq.shape[0], n_p, c.X))
+    for i in range(0, qq.shape[0], c.B):  # the context's batch at a time, the last one padded with its last row
+        part = qq[i:i + c.B]
+        rows = np.concatenate([part, np.repeat(part[-1:], c.B - len(part), 0)]) if len(part) < c.B else part
+        x_seq[i:i + len(part)] = c.generate_x_seq(stride, q=rows)[:len(part)]
+    per_obs = c.S // int(stride)
+    z = md["generate_z"](qq[:, :md["dim_u"]])
+    x_0 = md["generate_x_0"](z, qq[:, md["dim_u"]:md["dim_u"] + md["dim_v_0"]])
+    y_seq = md["obs_func"](x_seq[:, per_obs::per_obs])
+    out = (x_seq, y_seq, z, x_0)
+    return tuple(a[0] for a in out) if q.ndim == 1 else out
