@@ -720,6 +720,27 @@ struct KXobs {
   }
 };
 
+// The plain recursion of a whole chain from x0 over its noise increments v [L][V]: emit(p, x) receives the state after step
+// p * stride, p = 1 .. L / stride.  KPath and the lane-0 fallbacks of the two time-parallel scans (k_xobs_par: stride S, point
+// p stored as entry p - 1; k_path_par).  Forced inline: the kernels pass register arrays, a real call would put them in scratch.
+template <class M, class Emit>
+CHMC_HD CHMC_FI inline void plain_recursion(const double* k, const double* x0, const double* v, int L, int stride, Emit emit) {
+  constexpr int X = M::X, V = M::V;
+  double x[X], xn[X];
+  CHMC_UNROLL
+  for (int a = 0; a < X; ++a) x[a] = x0[a];
+  int left = stride, p = 0;
+  for (int s = 0; s < L; ++s) {
+    M::step(k, x, v + (size_t)s * V, xn);
+    CHMC_UNROLL
+    for (int a = 0; a < X; ++a) x[a] = xn[a];
+    if (--left == 0) {
+      emit(++p, x);
+      left = stride;
+    }
+  }
+}
+
 // generate_from_model's x_seq (FitzHugh-Nagumo_example.ipynb:316-335): the latent path of every chain, one work item per
 // chain, the plain recursion from x_0.  Point 0 is x_0, point p the state after step p * stride; out [B][T S / stride + 1][X].
 // qext: caller's positions [B][Q], or null for the chains' current states.
@@ -731,26 +752,18 @@ struct KPath {
   int stride;
   double* out;
   CHMC_HD void operator()(int c) const {
-    constexpr int X = M::X, V = M::V;
+    constexpr int X = M::X;
     const double* q = (qext ? qext : pick(sl.q, sl.cur[c])) + (size_t)c * sy.Q;
     ChainConsts<M> cc;
     cc.init(q, sy.dl);
-    double x[X], xn[X];
+    double x[X];
     M::gx0(cc.z, q + sy.U, x);
-    const double* v = q + sy.U + sy.V0;
     const int L = sy.T * sy.S;
     double* o = out + (size_t)c * (L / stride + 1) * X;
     for (int a = 0; a < X; ++a) o[a] = x[a];
-    int left = stride;
-    for (int s = 0; s < L; ++s) {
-      M::step(cc.k, x, v + (size_t)s * V, xn);
-      for (int a = 0; a < X; ++a) x[a] = xn[a];
-      if (--left == 0) {
-        o += X;
-        for (int a = 0; a < X; ++a) o[a] = x[a];
-        left = stride;
-      }
-    }
+    plain_recursion<M>(cc.k, x, q + sy.U + sy.V0, L, stride, [&](int p, const double* xp) {
+      for (int a = 0; a < X; ++a) o[(size_t)p * X + a] = xp[a];
+    });
   }
 };
 

@@ -4637,13 +4637,113 @@ __device__ __forceinline__ void vm_store16_nt(double* p, const d2_t& v) {
   // for the interval sums that read it next: those get 1 % faster, the scan 2 % slower, the step 0.3 % slower)
   asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(p), "v"(v) : "memory");
 }
-// generate_x_obs_seq (:384-397) of every chain's CURRENT state by multiple shooting over the whole chain (one wavefront
-// per chain, 64 segments), seeded with the state's stored trajectory: the states at the observation times for the
-// partition switch.  The stored trajectory is exact inside every block of the CURRENT partition and its block junctions
-// close to the constraint tolerance, so the junction corrections of the first sweep are ~1e-9 and the second sweep only
-// confirms them (settled = every junction moved by rounding at most, as in k_fwd_par); the sequential recursion, 40 000
-// dependent steps on one lane (KXobs: 2 ms per switch at configs[1]), is the fallback.  sy.blk / sy.obs2blk must still
-// describe the partition the trajectory was computed in.
+
+// ---------------------------------------------------------------------------------------------------------------
+// Multiple shooting over a whole chain by ONE wavefront (k_xobs_par, k_path_par): the chain's L steps are cut into 64 segments
+// of m = ceil(L / 64) steps, lane l integrates segment l from its start state Ul, seeded with the state's stored trajectory,
+// and accumulates the segment's transition matrix; the junction defects are corrected by an affine prefix scan over the
+// lanes (the Newton step on the 63 matching conditions, as in fwd_par_sweeps).  The stored trajectory is exact inside every
+// block of the CURRENT partition and its block junctions close to the constraint tolerance, so the junction corrections of
+// the first sweep are ~1e-9 and the second sweep only confirms them.
+// (Not fwd_par_sweeps: that one works per block on W wavefronts with the DPP scan, treats the absorbing fronts of SIR, and
+// settles to CHMC_PAR_JTOL = 1e-11 before a final pass; only the settled predicate is common to the two.)
+
+// A junction value has settled: the new one equals the old one (bitwise, or both NaN: beyond a point where the true recursion
+// overflows everything is NaN and stays NaN) or differs from it by at most tol relative to max(|new|, 1).
+__device__ __forceinline__ bool junction_settled(double nu, double old, double tol) {
+  const bool same = nu == old || (nu != nu && old != old);
+  const bool close = fabs(nu - old) <= tol * (fabs(nu) > 1.0 ? fabs(nu) : 1.0);
+  return same || close;
+}
+
+// Lane `lane`'s segment [s0, s1) of the L steps (have: it is not empty) and its first start state Ul: x0 for lane 0, else
+// the stored trajectory's state before step s0.  sy.blk / sy.obs2blk must still describe the partition the trajectory was
+// computed in.
+struct ShootSeg {
+  int m, s0, s1;
+  bool have;
+};
+template <class M>
+__device__ __forceinline__ ShootSeg shoot_setup(const Sys& sy, int lane, int L, const double* trj, const double (&x0)[M::X],
+                                                double (&Ul)[M::X]) {
+  constexpr int X = M::X;
+  ShootSeg sg;
+  sg.m = (L + 63) >> 6;
+  sg.s0 = lane * sg.m, sg.s1 = (sg.s0 + sg.m < L ? sg.s0 + sg.m : L);
+  sg.have = sg.s0 < L;
+  const int b0 = sg.have ? sy.obs2blk[sg.s0 / sy.S] : 0;  // step s of block b sits at trajectory entry s + CHMC_TPAD b
+#pragma unroll
+  for (int a = 0; a < X; ++a) Ul[a] = lane == 0 ? x0[a] : (sg.have ? trj[(size_t)(sg.s0 + CHMC_TPAD * b0) * X + a] : 0.0);
+  return sg;
+}
+
+// The junction half of a sweep, after every lane has integrated its segment from Ul to x with the transition matrix P: the
+// junction defects, their affine prefix scan over the lanes, the new start states (a lane whose start state did not move
+// at all hands on its end state as it is: the exact prefix) and the settled criterion at 1e-13.  Ul becomes the new start
+// state; returns whether every junction has settled (the same value in every lane).
+// (The integration half stays in the two kernels: shared behind a per-step hook it compiled to the same fp64 instructions
+// and still moved the last bit of some settled start states on long chains, profiles/shoot_shared_full_form_rejected.txt.)
+template <int X>
+__device__ __forceinline__ bool shoot_junctions(const double (&x)[X], const double (&P)[X * X], double (&Ul)[X], int lane,
+                                                bool have, bool junction) {
+  double ec[X], Pc[X * X], Unext[X];
+#pragma unroll
+  for (int a = 0; a < X; ++a) Unext[a] = __shfl_down(Ul[a], 1, 64);
+#pragma unroll
+  for (int a = 0; a < X; ++a) ec[a] = junction ? x[a] - Unext[a] : 0.0;
+#pragma unroll
+  for (int i = 0; i < X * X; ++i) Pc[i] = junction ? P[i] : ((i / X == i % X) ? 1.0 : 0.0);
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    double Pp[X * X], ep[X], Pn[X * X];
+#pragma unroll
+    for (int i = 0; i < X * X; ++i) Pp[i] = __shfl_up(Pc[i], o, 64);
+#pragma unroll
+    for (int a = 0; a < X; ++a) ep[a] = __shfl_up(ec[a], o, 64);
+    if (lane >= o) {
+#pragma unroll
+      for (int a = 0; a < X; ++a) {
+        double tt = ec[a];
+#pragma unroll
+        for (int d = 0; d < X; ++d) tt += Pc[a * X + d] * ep[d];
+        ec[a] = tt;
+      }
+      matmul_xx<X>(Pc, Pp, Pn);
+#pragma unroll
+      for (int i = 0; i < X * X; ++i) Pc[i] = Pn[i];
+    }
+  }
+  double dl[X], Un[X];
+#pragma unroll
+  for (int a = 0; a < X; ++a) {
+    const double up = __shfl_up(ec[a], 1, 64);
+    dl[a] = lane == 0 ? 0.0 : up;
+  }
+  bool still = true;
+#pragma unroll
+  for (int a = 0; a < X; ++a) still = still && dl[a] == 0.0;
+#pragma unroll
+  for (int a = 0; a < X; ++a) {
+    double tt = 0.0;
+#pragma unroll
+    for (int d = 0; d < X; ++d) tt += P[a * X + d] * dl[d];
+    Un[a] = still ? x[a] : x[a] + tt;
+  }
+  int unsettled = 0;
+#pragma unroll
+  for (int a = 0; a < X; ++a) {
+    const double nu = __shfl_up(Un[a], 1, 64);
+    if (lane > 0 && have) {
+      unsettled |= !junction_settled(nu, Ul[a], 1e-13);
+      Ul[a] = nu;
+    }
+  }
+  return __ballot(unsettled) == 0ULL;
+}
+
+// generate_x_obs_seq (:384-397) of every chain's CURRENT state by the multiple shooting above: the states at the observation
+// times for the partition switch, stored by the sweeps themselves.  The sequential recursion, 40 000 dependent steps on one
+// lane (KXobs: 2 ms per switch at configs[1]), is the fallback.
 template <class M>
 __global__ void __launch_bounds__(64) k_xobs_par(Sys sy, Slots sl, double* xobs_out) {
   constexpr int X = M::X, V = M::V, MAXS = 8;
@@ -4653,22 +4753,15 @@ __global__ void __launch_bounds__(64) k_xobs_par(Sys sy, Slots sl, double* xobs_
   const int s_ = sl.cur[c];
   const int S = sy.S, L = sy.T * sy.S;
   const double* q = pick(sl.q, s_) + (size_t)c * sy.Q;
-  const double* trj = pick(sl.traj, s_) + (size_t)c * sy.TRJ;
   const double* vbase = q + sy.U + sy.V0;
   double* out = xobs_out + (size_t)c * sy.T * X;
   ChainConsts<M> cc;
   cc.init(q, sy.dl);
-  double x0[X];
+  double x0[X], Ul[X];
   M::gx0(cc.z, q + sy.U, x0);
-  const int m = (L + 63) >> 6;
-  const int s0 = lane * m, s1 = (s0 + m < L ? s0 + m : L);
-  const bool have = s0 < L;
-  double Ul[X];
-  {
-    const int b0 = have ? sy.obs2blk[s0 / S] : 0;  // step s of block b sits at trajectory entry s + CHMC_TPAD b
-#pragma unroll
-    for (int a = 0; a < X; ++a) Ul[a] = lane == 0 ? x0[a] : (have ? trj[(size_t)(s0 + CHMC_TPAD * b0) * X + a] : 0.0);
-  }
+  const ShootSeg sg = shoot_setup<M>(sy, lane, L, pick(sl.traj, s_) + (size_t)c * sy.TRJ, x0, Ul);
+  const int s0 = sg.s0, s1 = sg.s1;
+  const bool have = sg.have;
   bool converged = false;
   for (int sweep = 0; sweep < MAXS && !converged; ++sweep) {
     double x[X], P[X * X];
@@ -4721,87 +4814,23 @@ __global__ void __launch_bounds__(64) k_xobs_par(Sys sy, Slots sl, double* xobs_
       fetch(base + 2 * CH, vb[0]);
       run(base + CH, vb[1]);
     }
-    double ec[X], Pc[X * X], Unext[X];
-#pragma unroll
-    for (int a = 0; a < X; ++a) Unext[a] = __shfl_down(Ul[a], 1, 64);
-    const bool junction = have && s1 < L;
-#pragma unroll
-    for (int a = 0; a < X; ++a) ec[a] = junction ? x[a] - Unext[a] : 0.0;
-#pragma unroll
-    for (int i = 0; i < X * X; ++i) Pc[i] = junction ? P[i] : ((i / X == i % X) ? 1.0 : 0.0);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      double Pp[X * X], ep[X], Pn[X * X];
-#pragma unroll
-      for (int i = 0; i < X * X; ++i) Pp[i] = __shfl_up(Pc[i], o, 64);
-#pragma unroll
-      for (int a = 0; a < X; ++a) ep[a] = __shfl_up(ec[a], o, 64);
-      if (lane >= o) {
-#pragma unroll
-        for (int a = 0; a < X; ++a) {
-          double tt = ec[a];
-#pragma unroll
-          for (int d = 0; d < X; ++d) tt += Pc[a * X + d] * ep[d];
-          ec[a] = tt;
-        }
-        matmul_xx<X>(Pc, Pp, Pn);
-#pragma unroll
-        for (int i = 0; i < X * X; ++i) Pc[i] = Pn[i];
-      }
-    }
-    double dl[X], Un[X];
-#pragma unroll
-    for (int a = 0; a < X; ++a) {
-      const double up = __shfl_up(ec[a], 1, 64);
-      dl[a] = lane == 0 ? 0.0 : up;
-    }
-    bool still = true;
-#pragma unroll
-    for (int a = 0; a < X; ++a) still = still && dl[a] == 0.0;
-#pragma unroll
-    for (int a = 0; a < X; ++a) {
-      double tt = 0.0;
-#pragma unroll
-      for (int d = 0; d < X; ++d) tt += P[a * X + d] * dl[d];
-      Un[a] = still ? x[a] : x[a] + tt;
-    }
-    int unsettled = 0;
-#pragma unroll
-    for (int a = 0; a < X; ++a) {
-      const double nu = __shfl_up(Un[a], 1, 64);
-      if (lane > 0 && have) {
-        const double old = Ul[a];
-        const bool same = nu == old || (nu != nu && old != old);
-        const bool close = fabs(nu - old) <= 1e-13 * (fabs(nu) > 1.0 ? fabs(nu) : 1.0);
-        unsettled |= !(same || close);
-        Ul[a] = nu;
-      }
-    }
-    converged = __ballot(unsettled) == 0ULL;
+    converged = shoot_junctions<X>(x, P, Ul, lane, have, have && s1 < L);
   }
-  if (!converged && lane == 0) {  // sequential recursion
-    double x[X], xn[X];
+  if (!converged && lane == 0) {  // sequential recursion: the states after every S-th step, no point 0
+    plain_recursion<M>(cc.k, x0, vbase, L, S, [&](int p, const double* xs) {
 #pragma unroll
-    for (int a = 0; a < X; ++a) x[a] = x0[a];
-    for (int s = 0; s < L; ++s) {
-      M::step(cc.k, x, vbase + (size_t)s * V, xn);
-#pragma unroll
-      for (int a = 0; a < X; ++a) x[a] = xn[a];
-      if ((s + 1) % S == 0) {
-        const int t = (s + 1) / S - 1;
-#pragma unroll
-        for (int a = 0; a < X; ++a) out[t * X + a] = x[a];
-      }
-    }
+      for (int a = 0; a < X; ++a) out[(size_t)(p - 1) * X + a] = xs[a];
+    });
   }
 }
 
 // generate_from_model's x_seq (FitzHugh-Nagumo_example.ipynb:316-335) of every chain's CURRENT state: point 0 is x_0, point p
 // the state after step p * stride of the whole chain's recursion; out [B][NP = T S / stride + 1][X].  One wavefront per chain.
-// Phase 1 settles the 64 segment start states by multiple shooting from the stored trajectory -- k_xobs_par's sweeps, its
-// settled criterion and its sequential fallback, written out again here so that kernel's code stays what it is.  Phase 2 is
-// a plain pass: every lane integrates its segment once more from its settled start state (within 1e-13 relative of the
-// sequential recursion's state there) and emits the states whose step index is a multiple of `stride`.
+// Phase 1 settles the 64 segment start states by the multiple shooting above, as k_xobs_par does but storing nothing (the
+// set-up, the junction half of a sweep and the settled criterion are that kernel's; the integration loop is written out in
+// both, see shoot_junctions), and falls back to the plain recursion on lane 0.  Phase 2 is a plain pass: every lane
+// integrates its segment once more from its settled start state (within 1e-13 relative of the sequential recursion's state
+// there) and emits the states whose step index is a multiple of `stride`.
 // Emit: a lane's points are contiguous in `out`, but the 64 lanes write 64 regions, and a lane-per-region store instruction
 // touches 64 lines for 16 or 24 bytes each.  A lane therefore parks its doubles in its row of an LDS ring, indexed by the
 // global double index modulo the ring, and after every 8-step window the wavefront writes out the 128-byte lines that are
@@ -4831,22 +4860,15 @@ __global__ void __launch_bounds__(64) k_path_par(Sys sy, Slots sl, int stride, d
   const int S = sy.S, L = sy.T * sy.S;
   const int NP = L / stride + 1;
   const double* q = pick(sl.q, s_) + (size_t)c * sy.Q;
-  const double* trj = pick(sl.traj, s_) + (size_t)c * sy.TRJ;
   const double* vbase = q + sy.U + sy.V0;
   double* out = x_seq + (size_t)c * NP * X;
   ChainConsts<M> cc;
   cc.init(q, sy.dl);
-  double x0[X];
+  double x0[X], Ul[X];
   M::gx0(cc.z, q + sy.U, x0);
-  const int m = (L + 63) >> 6;
-  const int s0 = lane * m, s1 = (s0 + m < L ? s0 + m : L);
-  const bool have = s0 < L;
-  double Ul[X];
-  {
-    const int b0 = have ? sy.obs2blk[s0 / S] : 0;  // step s of block b sits at trajectory entry s + CHMC_TPAD b
-#pragma unroll
-    for (int a = 0; a < X; ++a) Ul[a] = lane == 0 ? x0[a] : (have ? trj[(size_t)(s0 + CHMC_TPAD * b0) * X + a] : 0.0);
-  }
+  const ShootSeg sg = shoot_setup<M>(sy, lane, L, pick(sl.traj, s_) + (size_t)c * sy.TRJ, x0, Ul);
+  const int m = sg.m, s0 = sg.s0, s1 = sg.s1;
+  const bool have = sg.have;
   // noise increments of eight steps, requested one window ahead (addresses past the chain are clamped to its last step)
   auto fetch = [&](int base, double* dst) {
 #pragma unroll
@@ -4892,63 +4914,7 @@ __global__ void __launch_bounds__(64) k_path_par(Sys sy, Slots sl, int stride, d
       fetch(base + 2 * CH, vb[0]);
       run(base + CH, vb[1]);
     }
-    double ec[X], Pc[X * X], Unext[X];
-#pragma unroll
-    for (int a = 0; a < X; ++a) Unext[a] = __shfl_down(Ul[a], 1, 64);
-    const bool junction = have && s1 < L;
-#pragma unroll
-    for (int a = 0; a < X; ++a) ec[a] = junction ? x[a] - Unext[a] : 0.0;
-#pragma unroll
-    for (int i = 0; i < X * X; ++i) Pc[i] = junction ? P[i] : ((i / X == i % X) ? 1.0 : 0.0);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      double Pp[X * X], ep[X], Pn[X * X];
-#pragma unroll
-      for (int i = 0; i < X * X; ++i) Pp[i] = __shfl_up(Pc[i], o, 64);
-#pragma unroll
-      for (int a = 0; a < X; ++a) ep[a] = __shfl_up(ec[a], o, 64);
-      if (lane >= o) {
-#pragma unroll
-        for (int a = 0; a < X; ++a) {
-          double tt = ec[a];
-#pragma unroll
-          for (int d = 0; d < X; ++d) tt += Pc[a * X + d] * ep[d];
-          ec[a] = tt;
-        }
-        matmul_xx<X>(Pc, Pp, Pn);
-#pragma unroll
-        for (int i = 0; i < X * X; ++i) Pc[i] = Pn[i];
-      }
-    }
-    double dl[X], Un[X];
-#pragma unroll
-    for (int a = 0; a < X; ++a) {
-      const double up = __shfl_up(ec[a], 1, 64);
-      dl[a] = lane == 0 ? 0.0 : up;
-    }
-    bool still = true;
-#pragma unroll
-    for (int a = 0; a < X; ++a) still = still && dl[a] == 0.0;
-#pragma unroll
-    for (int a = 0; a < X; ++a) {
-      double tt = 0.0;
-#pragma unroll
-      for (int d = 0; d < X; ++d) tt += P[a * X + d] * dl[d];
-      Un[a] = still ? x[a] : x[a] + tt;
-    }
-    int unsettled = 0;
-#pragma unroll
-    for (int a = 0; a < X; ++a) {
-      const double nu = __shfl_up(Un[a], 1, 64);
-      if (lane > 0 && have) {
-        const double old = Ul[a];
-        const bool same = nu == old || (nu != nu && old != old);
-        const bool close = fabs(nu - old) <= 1e-13 * (fabs(nu) > 1.0 ? fabs(nu) : 1.0);
-        unsettled |= !(same || close);
-        Ul[a] = nu;
-      }
-    }
-    converged = __ballot(unsettled) == 0ULL;
+    converged = shoot_junctions<X>(x, P, Ul, lane, have, have && s1 < L);
     nsweep = sweep + 1;
   }
   if (sweeps && lane == 0) sweeps[c] = converged ? nsweep : 0;
@@ -4958,22 +4924,10 @@ __global__ void __launch_bounds__(64) k_path_par(Sys sy, Slots sl, int stride, d
   }
   if (!converged) {  // sequential recursion on lane 0
     if (lane == 0) {
-      double x[X], xn[X];
+      plain_recursion<M>(cc.k, x0, vbase, L, stride, [&](int p, const double* xs) {
 #pragma unroll
-      for (int a = 0; a < X; ++a) x[a] = x0[a];
-      double* o = out;
-      int left = stride;
-      for (int s = 0; s < L; ++s) {
-        M::step(cc.k, x, vbase + (size_t)s * V, xn);
-#pragma unroll
-        for (int a = 0; a < X; ++a) x[a] = xn[a];
-        if (--left == 0) {
-          o += X;
-#pragma unroll
-          for (int a = 0; a < X; ++a) o[a] = x[a];
-          left = stride;
-        }
-      }
+        for (int a = 0; a < X; ++a) out[(size_t)p * X + a] = xs[a];
+      });
     }
     return;
   }
@@ -5576,12 +5530,7 @@ __device__ __forceinline__ bool fwd_par_sweeps(const Sys& sy, const Work& w, con
       int u = 0;
       if (junction) {
 #pragma unroll
-        for (int a = 0; a < X; ++a) {
-          const double nu = Un[a], old = Unext[a];
-          const bool same = nu == old || (nu != nu && old != old);
-          const bool close = fabs(nu - old) <= CHMC_PAR_JTOL * (fabs(nu) > 1.0 ? fabs(nu) : 1.0);
-          u |= !(same || close);
-        }
+        for (int a = 0; a < X; ++a) u |= !junction_settled(Un[a], Unext[a], CHMC_PAR_JTOL);
       }
       return u;
     };

@@ -90,9 +90,11 @@ def references(ctx, case, q):
     return full, at_obs
 
 
-def check_state(ctx, case, strides, label, on_device, par, settled):
-    """The checks of one state: both forms against both references for every stride; the launch counters and sweeps."""
-    q = ctx.get_state(want_p=False, want_x_obs=False)[0]
+def check_state(ctx, case, strides, label, on_device, par, settled, switched=False):
+    """The checks of one state: both forms against both references for every stride; the launch counters and sweeps.
+    switched: the state comes right out of a partition switch, so the context's x_obs is fresh (k_xobs_par; KXobs on the
+    emulation build) and is held against the C oracle and against the path at stride S."""
+    q, _, x_obs, _ = ctx.get_state(want_p=False, want_x_obs=switched)
     full, at_obs = references(ctx, case, q)
     worst = 0.0
     for stride in strides:
@@ -110,6 +112,11 @@ def check_state(ctx, case, strides, label, on_device, par, settled):
             worst = max(worst, e_a, e_b)
             print(f"  {label} stride {stride} {name}: vs models {e_b:.2e}, vs C oracle at the observations {e_a:.2e}")
             assert e_b <= TOL and e_a <= TOL, (label, stride, name, e_a, e_b)
+        if switched and stride == ctx.S:
+            e_o, e_p = rel(x_obs, at_obs), rel(x_obs, cur[:, per_obs::per_obs])
+            worst = max(worst, e_o, e_p)
+            print(f"  {label}: x_obs of the switch vs C oracle {e_o:.2e}, vs the path at stride {stride} {e_p:.2e}")
+            assert e_o <= TOL and e_p <= 1e-12, (label, e_o, e_p)
         assert d2["path_seq_launches"] == d1["path_seq_launches"] + 1 and d2["path_par_launches"] == d1["path_par_launches"]
         if on_device:
             agree = rel(cur, given)
@@ -148,9 +155,9 @@ def path_body(name, on_device=True, par=True):
     worst = check_state(ctx, case, strides, "after two steps", on_device, par, True)
     # 2, 3: right after a partition switch, and after the second one
     ctx.switch_partition()
-    worst = max(worst, check_state(ctx, case, strides, "after a switch", on_device, par, True))
+    worst = max(worst, check_state(ctx, case, strides, "after a switch", on_device, par, True, switched=True))
     ctx.switch_partition()
-    worst = max(worst, check_state(ctx, case, strides, "after two switches", on_device, par, True))
+    worst = max(worst, check_state(ctx, case, strides, "after two switches", on_device, par, True, switched=True))
     # 4: off the manifold: large junction defects in the stored trajectory
     ctx.set_state(q_on + 0.01 * rng.standard_normal(q_on.shape), None, xo, 0)
     worst = max(worst, check_state(ctx, case, strides, "off the manifold", on_device, par, False))
