@@ -56,7 +56,7 @@ typedef struct chmc_config {
   int device;                 /* HIP device ordinal */
   double obs_interval;
   double sigma;               /* fixed observation-noise std (generate_sigma given as a Number, :354-358); noisy == 1 only */
-  const double* y_seq;        /* [T] */
+  const double* y_seq;        /* [T]: shared by every chain (a data set and a fixed sigma per chain: chmc_set_observations) */
 } chmc_config;
 
 int chmc_create(const chmc_config* cfg, chmc_ctx** out);
@@ -76,6 +76,34 @@ int chmc_get_blocks(const chmc_ctx* ctx, int partition, int* out);
  * :1151-1184). */
 int chmc_set_state(chmc_ctx* ctx, const double* q, const double* p, const double* x_obs_seq, int partition);
 int chmc_get_state(chmc_ctx* ctx, double* q, double* p, double* x_obs_seq, int* partition);
+/* Per-chain observations: many data sets of one shape (model, T, S, R) in one context.  chmc_create gives every chain the
+ * same y_seq [T] and the same sigma; chmc_set_observations gives chain c the row y_seq[c] of y_seq [B][T] and, with
+ * sigma != NULL, the fixed observation-noise std sigma[c] (sigma [B], every entry > 0).
+ *   sigma is accepted in a context with noisy == 1 only.  NULL keeps the noise level(s) the context has.  With noisy == 0
+ *   (no observation noise) or noisy == 2 (sigma = exp(u[dim_z]) stays a function of the chain's own u) only y_seq is per
+ *   chain, and a non-NULL sigma is an error.
+ *   The call INVALIDATES the chain state: the constraint function changed, so the caller sets or initialises a state
+ *   afterwards (chmc_set_state, chmc_init_linear_interpolation, a finder), as after chmc_create.
+ *   Calling it again replaces the data.  Every entry point then works with the chain's own data -- the constraint and all
+ *   operators, the steps, trajectories and trees, the path scans, and row c of chmc_neg_log_dens_and_grad* /
+ *   chmc_adam_objective_device (row c is judged against chain c's data).  A chain's results are bitwise those of a
+ *   context that holds its (y, sigma) as shared data.
+ * chmc_get_observations returns what the kernels use: y_seq [B][T] and sigma [B] (either may be NULL); in a context that
+ * never had per-chain data the shared values, once per chain (sigma = 0 where noisy != 1). */
+int chmc_set_observations(chmc_ctx* ctx, const double* y_seq, const double* sigma);
+int chmc_get_observations(chmc_ctx* ctx, double* y_seq, double* sigma);
+/* Data simulated from a prior draw, per chain, on the device.  For every chain c:
+ *   pos = [u | v_0 | v_seq | n] ~ N(0, I): the keyed normals of chmc_fill_normal* for (seed, stream = chain_offset + c,
+ *   draw = CHMC_SIMULATE_DRAW), so the data of a chain do not depend on how the chains are sharded;
+ *   x_obs_seq = the path of that position at the observation times;
+ *   y_c[t] = obs_func(x(t_obs)) + sigma_c n_t   (without the noise term for noisy == 0; sigma_c = exp(u[dim_z]) for
+ *   noisy == 2, else the chain's fixed noise level: the context's, or the one chmc_set_observations gave it);
+ *   mom = 0, the given partition, and the state caches evaluated, like chmc_set_state.
+ * The data become the chain's observations as with chmc_set_observations (chmc_get_observations returns them).  Afterwards
+ * the constraint is zero by construction: every chain sits on the manifold of its own data, at an exact draw from its own
+ * posterior (simulation-based calibration needs no initial-state finder and no burn-in). */
+#define CHMC_SIMULATE_DRAW (1ULL << 62) /* (momentum refresh: the transition number; the finders: 2^63 | ...) */
+int chmc_simulate_observations_device(chmc_ctx* ctx, unsigned long long seed, int chain_offset, int partition);
 /* find_initial_state_by_linear_interpolation (sde/mici_extensions.py:1479-1547) for all chains at once, on the
  * device: given u [B][U], v_0 [B][V0] and full states at the observation times x_obs_seq_init [B][T][X]
  * (generate_x_obs_seq_init of the scripts), solves per time step for the noise increments that make the discretised

@@ -36,6 +36,9 @@ SYMBOLS = [
     ("chmc_get_blocks", C.c_int, [C.c_void_p, C.c_int, ip]),
     ("chmc_set_state", C.c_int, [C.c_void_p, dp, dp, dp, C.c_int]),
     ("chmc_get_state", C.c_int, [C.c_void_p, dp, dp, dp, ip]),
+    ("chmc_set_observations", C.c_int, [C.c_void_p, dp, dp]),
+    ("chmc_get_observations", C.c_int, [C.c_void_p, dp, dp]),
+    ("chmc_simulate_observations_device", C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]),
     ("chmc_init_linear_interpolation", C.c_int, [C.c_void_p, dp, dp, dp, C.c_int]),
     ("chmc_set_metric", C.c_int, [C.c_void_p, dp]),
     ("chmc_tree_leaf", C.c_int, [C.c_void_p, ip, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

@@ -17,7 +17,22 @@ class ChmcContext:
                  use_gaussian_splitting=False, num_chains=1, device=0):
         L = _lib.lib()
         self.L = L
-        y = as_c(np.asarray(y_seq).reshape(-1))
+        # y_seq [T] (or [T, 1]): one data set for every chain; [B, T] (or [B, T, 1]): a row per chain.  sigma likewise: a
+        # number for every chain, or an array [B] (set_observations)
+        y_all = np.asarray(y_seq, dtype=np.float64)
+        if y_all.ndim == 3 and y_all.shape[2] == 1:
+            y_all = y_all[:, :, 0]
+        per_chain_y = y_all.ndim == 2 and y_all.shape[1] != 1
+        if per_chain_y and y_all.shape[0] != int(num_chains):
+            raise ValueError(f"y_seq must have shape (T,) or ({int(num_chains)}, T), got {y_all.shape}")
+        sigma_all = None
+        if sigma is not None and not isinstance(sigma, str) and np.ndim(sigma) > 0:
+            sigma_all = as_c(np.asarray(sigma, dtype=np.float64))
+            if sigma_all.shape != (int(num_chains),):
+                raise ValueError(f"sigma must be a number, \"variable\", None or an array of shape ({int(num_chains)},), "
+                                 f"got {sigma_all.shape}")
+            sigma = float(sigma_all[0])
+        y = as_c((y_all[0] if per_chain_y else y_all).reshape(-1))
         self._y = y
         cfg = ChmcConfig(
             model=MODEL_IDS[model] if isinstance(model, str) else int(model), num_obs=len(y),
@@ -40,6 +55,7 @@ class ChmcContext:
         self.K = [int(d[12]), int(d[13])][: self.num_partition]
         self.V, self.V0 = int(d[14]), int(d[15])
         self.noisy = sigma is not None
+        self.per_chain_observations = False  # set_observations / simulate_observations: the chains have data of their own
         self.variable_sigma = isinstance(sigma, str)
         self.sigma = sigma
         self.device = int(device)
@@ -51,6 +67,42 @@ class ChmcContext:
             raw = np.zeros(self.K[p] * 12, dtype=np.int32)
             check(L.chmc_get_blocks(h, p, iptr(raw)), "chmc_get_blocks")
             self.blocks.append([dict(zip(keys, map(int, raw[12 * b:12 * b + 12]))) for b in range(self.K[p])])
+        if per_chain_y or sigma_all is not None:
+            self.set_observations(y_all if per_chain_y else np.broadcast_to(y, (self.B, self.T)), sigma_all)
+
+    # ---- per-chain observations (chmc_set_observations, include/chmc.h)
+    def set_observations(self, y, sigma=None):
+        """Chain c gets the data y[c] (y [B, T] or [B, T, 1]) and, with `sigma` [B] (fixed-noise contexts only), its own
+        noise level.  Invalidates the chain state: set or initialise a state afterwards, as after construction."""
+        y = as_c(y)
+        if y.ndim == 3 and y.shape[2] == 1:
+            y = as_c(y[:, :, 0])
+        if y.shape != (self.B, self.T):
+            raise ValueError(f"y must have shape ({self.B}, {self.T}), got {y.shape}")
+        if sigma is not None:
+            sigma = as_c(sigma)
+            if sigma.shape != (self.B,):
+                raise ValueError(f"sigma must have shape ({self.B},), got {sigma.shape}")
+        check(self.L.chmc_set_observations(self.h, ptr(y), ptr(sigma)), "chmc_set_observations")
+        self.per_chain_observations = True
+        if sigma is not None:
+            self.sigma = sigma.copy()
+
+    def simulate_observations(self, seed, chain_offset=0, partition=0):
+        """Every chain draws its position from the prior N(0, I) (keyed by (seed, chain_offset + chain): any sharding gives
+        the same data), simulates its own data from it and becomes a state on the manifold of those data, momentum 0
+        (chmc_simulate_observations_device, include/chmc.h).  observations() returns the data."""
+        check(self.L.chmc_simulate_observations_device(self.h, int(seed), int(chain_offset), int(partition)),
+              "chmc_simulate_observations_device")
+        self.per_chain_observations = True
+        self.partition = int(partition)
+
+    def observations(self):
+        """(y [B, T], sigma [B]) as the kernels use them; the shared values once per chain in a context without per-chain
+        data (sigma 0 where the noise level is not a fixed number)."""
+        y, sg = np.empty((self.B, self.T)), np.empty(self.B)
+        check(self.L.chmc_get_observations(self.h, ptr(y), ptr(sg)), "chmc_get_observations")
+        return y, sg
 
     def close(self):
         if getattr(self, "h", None):

@@ -178,6 +178,8 @@ static void set_half(chmc_ctx* c, const ViewSave& f, int h) {
   alias_step_outputs(v, c->d_out, f.sy.B, c0);
   v.sy.B = c->hB[h];
   v.sy.xobs = v.d_xobs;
+  if (v.d_yc) v.sy.y = v.d_yc;  // (shared data: stride 0, every view reads d_y)
+  v.sy.sigc = v.d_sigc;
   v.sy.order = c->d_order_half[c->part][h];
   v.w.n_active = f.w.n_active + 4 * (1 + h);
   use_stream(h);
@@ -864,6 +866,50 @@ extern "C" int chmc_get_state(chmc_ctx* ctx, double* q, double* p, double* x_obs
   if (partition) *partition = ctx->part;
   CHMC_LEAVE("chmc_get_state")
 }
+// Per-chain observations: d_yc [B][T] and d_sigc [B] are entries of the per-chain list (chmc_layout.h) that no context has
+// until this call; afterwards Sys::y strides by T and sigma_at reads the chain's own value.
+extern "C" int chmc_set_observations(chmc_ctx* ctx, const double* y_seq, const double* sigma) {
+  CHMC_ENTER("chmc_set_observations")
+  if (!y_seq) return fail("chmc_set_observations: y_seq is null");
+  Sys& sy = ctx->sy;
+  if (sigma) {
+    if (ctx->cfg.noisy != 1)
+      return fail("chmc_set_observations: a per-chain sigma needs a context with a fixed noise level (noisy == 1)");
+    for (int c = 0; c < sy.B; ++c)
+      if (!(sigma[c] > 0.0)) return fail("chmc_set_observations: every sigma must be > 0");
+  }
+  ensure_array(ctx, ctx->d_yc);
+  h2d(ctx->d_yc, y_seq, sizeof(double) * (size_t)sy.B * sy.T);
+  sy.y = ctx->d_yc, sy.ystride = sy.T;
+  if (sigma) {
+    ensure_array(ctx, ctx->d_sigc);
+    h2d(ctx->d_sigc, sigma, sizeof(double) * (size_t)sy.B);
+    sy.sigc = ctx->d_sigc;
+  }
+  // the constraint changed: nothing cached on the chain states holds any more
+  ctx->have_state = ctx->have_tree = ctx->pair_ready = ctx->rows_fresh = false;
+  ctx->mom_tangent = ctx->snap_tangent = false;
+  CHMC_LEAVE("chmc_set_observations")
+}
+extern "C" int chmc_get_observations(chmc_ctx* ctx, double* y_seq, double* sigma) {
+  CHMC_ENTER("chmc_get_observations")
+  const Sys& sy = ctx->sy;
+  const size_t B = sy.B, T = sy.T;
+  if (y_seq) {
+    if (ctx->d_yc) {
+      d2h(y_seq, ctx->d_yc, sizeof(double) * B * T);
+    } else {  // the shared sequence, once per chain
+      d2h(y_seq, ctx->d_y, sizeof(double) * T);
+      for (size_t c = 1; c < B; ++c) memcpy(y_seq + c * T, y_seq, sizeof(double) * T);
+    }
+  }
+  if (sigma) {
+    if (ctx->d_sigc) d2h(sigma, ctx->d_sigc, sizeof(double) * B);
+    else std::fill(sigma, sigma + B, sy.sigma);  // (0 without a fixed noise level: noiseless, or exp(u[Z]))
+  }
+  CHMC_LEAVE("chmc_get_observations")
+}
+
 extern "C" int chmc_get_state_device(chmc_ctx* ctx, void* q_dev, void* p_dev) {
   CHMC_ENTER("chmc_get_state_device")
   const Sys& sy = ctx->sy;
@@ -1458,6 +1504,38 @@ extern "C" int chmc_fill_normal(chmc_ctx* ctx, unsigned long long seed, int n_ro
   if (rc) return -1;
   for (int r = 0; r < n_rows; ++r) memcpy(dst + (size_t)rows[r] * (size_t)ld, h.data() + (size_t)r * n_cols, sizeof(double) * (size_t)n_cols);
   return 0;
+}
+// A prior draw per chain and the data it generates (include/chmc.h): q = keyed N(0, I), x_obs_seq = its path at the observation
+// times, y = KSimObs of the two -- the chain then sits on the manifold of its own data, at an exact draw from its posterior.
+extern "C" int chmc_simulate_observations_device(chmc_ctx* ctx, unsigned long long seed, int chain_offset, int partition) {
+  CHMC_ENTER("chmc_simulate_observations_device")
+  if (partition < 0 || partition >= ctx->num_partition)
+    return fail("chmc_simulate_observations_device: partition out of range");
+  if (chain_offset < 0) return fail("chmc_simulate_observations_device: negative chain_offset");
+  Sys& sy = ctx->sy;
+  const int B = sy.B;
+  if ((long long)B * sy.T > 0x7fffffffLL) return fail("chmc_simulate_observations_device: too many observations for one call");
+  std::vector<int> rows(B), stream(B);
+  std::vector<unsigned long long> draw(B, CHMC_SIMULATE_DRAW);
+  for (int c = 0; c < B; ++c) rows[c] = c, stream[c] = chain_offset + c;
+  const int* rows_dev = nullptr;
+  if (upload_row_keys(ctx, "chmc_simulate_observations_device", B, rows.data(), stream.data(), draw.data(), &rows_dev)) return -1;
+  dev_zero(ctx->sl.cur, sizeof(int) * B);
+  if (fill_rows(ctx, "chmc_simulate_observations_device", seed, B, rows_dev, sy.Q, ctx->sl.q[0], sy.Q)) return -1;
+  dev_zero(ctx->sl.p[0], sizeof(double) * (size_t)B * sy.Q);
+  update_x_obs(ctx);  // x_obs_seq of the draws
+  ensure_array(ctx, ctx->d_yc);
+  dispatch(ctx, [&](auto inst) {
+    launch(KSimObs<typename decltype(inst)::M>{sy, ctx->sl, ctx->d_xobs, ctx->d_yc}, (long)B * sy.T, 8);
+  });
+  sy.y = ctx->d_yc, sy.ystride = sy.T;
+  ctx->have_tree = ctx->pair_ready = ctx->snap_tangent = false;
+  select_partition(ctx, partition);
+  begin_all(ctx, nullptr, nullptr);
+  state_eval(ctx, 0);
+  ctx->have_state = true;
+  ctx->mom_tangent = true;  // zero momentum
+  CHMC_LEAVE("chmc_simulate_observations_device")
 }
 // "Deal a try into a row" for the device-resident finder (init.py): keyed start points, zero moments and gradient, and the
 // row's carried scan guess back to the cold guess of a new context, so that every evaluation of a try depends on that try's

@@ -62,7 +62,9 @@ struct Sys {
   int Q, NV, K, C, Kmax, RM, TRJ, NCOL;  // NCOL = NV + (noisy ? T : 0)
   int NOBS;  // most observations in one block, over both partitions (interval frames LF)
   double dl, sigma;
-  const double* y;
+  const double* y;     // [T] shared by every chain (ystride 0), or [B][T] one row per chain (ystride T): y_of
+  int ystride;
+  const double* sigc;  // [B] fixed observation-noise std per chain (chmc_set_observations), or null: `sigma` for every chain
   const double* xobs;  // [B][T][X]
   const BlockDesc* blk;
   const int* obs2blk;
@@ -79,8 +81,13 @@ CHMC_HD inline double metric_inv_u(const Sys& sy, const double* vu, int a) {
   for (int b = 0; b < sy.U; ++b) t += W[b] * vu[b];
   return t;
 }
-// generate_sigma(u) of a chain with position q: a number (:354-358) or exp(u[dim_z]) with variable observation noise
-CHMC_HD inline double sigma_at(const Sys& sy, const double* q) { return sy.varsig ? exp(q[sy.Z]) : sy.sigma; }
+// generate_sigma(u) of chain c with position q: a number (:354-358; the context's, or the chain's own after
+// chmc_set_observations) or exp(u[dim_z]) with variable observation noise
+CHMC_HD inline double sigma_at(const Sys& sy, const double* q, int c) {
+  return sy.varsig ? exp(q[sy.Z]) : sy.sigc ? sy.sigc[c] : sy.sigma;
+}
+// the observation sequence of chain c: one code path, the stride is 0 while every chain shares the context's data
+CHMC_HD inline const double* y_of(const Sys& sy, int c) { return sy.y + (size_t)c * sy.ystride; }
 CHMC_HD inline double metric_mul_u(const Sys& sy, const double* vu, int a) {
   if (!sy.m0) return vu[a];
   const double* Mr = sy.m0 + a * sy.U;
@@ -358,7 +365,7 @@ struct ChainConsts {
 // is integrated and (ii) no per-step branches when S is a multiple of 8 (bounds, trajectory store and the
 // observation test are hoisted to tile level).
 template <class M, int RM, bool STORE>
-CHMC_HD inline void fwd_block_impl(const Sys& sy, const BlockDesc& bd, const ChainConsts<M>& cc, const double* q,
+CHMC_HD inline void fwd_block_impl(const Sys& sy, const BlockDesc& bd, const ChainConsts<M>& cc, int c, const double* q,
                                    const double* xobs, double* traj, double* cp) {
   constexpr int X = M::X, V = M::V, PF = 8;
   double x[X], xn[X];
@@ -370,9 +377,10 @@ CHMC_HD inline void fwd_block_impl(const Sys& sy, const BlockDesc& bd, const Cha
   }
   const double* v = vb + sy.V0 + (size_t)bd.step0 * V;
   const double* n = q + sy.U + sy.NV;
+  const double* y = y_of(sy, c) + bd.obs0;
   for (int i = 0; i < RM; ++i) cp[i] = 0.0;
   const int L = bd.nsteps, S = sy.S;
-  const double sig = sy.noisy ? sigma_at(sy, q) : 0.0;
+  const double sig = sy.noisy ? sigma_at(sy, q, c) : 0.0;
   // loads run up to PF steps past the block's end (never consumed): every q-like buffer is allocated with
   // CHMC_Q_PAD doubles of slack so that the scan needs no per-element bounds branches
   double cur[PF * V], nxt[PF * V];
@@ -402,7 +410,7 @@ CHMC_HD inline void fwd_block_impl(const Sys& sy, const BlockDesc& bd, const Cha
         if (j < bd.ny) {
           double yv = M::obs(x);
           if (sy.noisy) yv += sig * n[bd.obs0 + j];
-          cp[j] = yv - sy.y[bd.obs0 + j];
+          cp[j] = yv - y[j];
         }
         ++j;
         left = S;
@@ -428,7 +436,7 @@ CHMC_HD inline void fwd_block_impl(const Sys& sy, const BlockDesc& bd, const Cha
             if (j < bd.ny) {
               double yv = M::obs(x);
               if (sy.noisy) yv += sig * n[bd.obs0 + j];
-              cp[j] = yv - sy.y[bd.obs0 + j];
+              cp[j] = yv - y[j];
             }
             ++j;
             cnt = S;
@@ -445,12 +453,12 @@ CHMC_HD inline void fwd_block_impl(const Sys& sy, const BlockDesc& bd, const Cha
     for (int a = 0; a < X; ++a) cp[bd.ny + a] = x[a] - xobs[(bd.obs0 + bd.nobs - 1) * X + a];
 }
 template <class M, int RM>
-CHMC_HD inline void fwd_block(const Sys& sy, const BlockDesc& bd, const ChainConsts<M>& cc, const double* q,
+CHMC_HD inline void fwd_block(const Sys& sy, const BlockDesc& bd, const ChainConsts<M>& cc, int c, const double* q,
                               const double* xobs, double* traj, double* cp) {
   if (traj)
-    fwd_block_impl<M, RM, true>(sy, bd, cc, q, xobs, traj, cp);
+    fwd_block_impl<M, RM, true>(sy, bd, cc, c, q, xobs, traj, cp);
   else
-    fwd_block_impl<M, RM, false>(sy, bd, cc, q, xobs, traj, cp);
+    fwd_block_impl<M, RM, false>(sy, bd, cc, c, q, xobs, traj, cp);
 }
 
 // Reverse (adjoint) sweep over a block carrying all RM constraint rows (jacob_constr_blocks :521-624).
@@ -460,7 +468,7 @@ CHMC_HD inline void fwd_block(const Sys& sy, const BlockDesc& bd, const ChainCon
 template <class M, int RM, int MODE>
 CHMC_HD inline void rev_block(const Sys& sy, const BlockDesc& bd, const ChainConsts<M>& cc, const double* u,
                               const double* q, const double* traj, double* Jv_out, const double* Jr, double* JuL,
-                              double* D, double sig_prev) {  // sig_prev: sigma at the previous point (MODE 1)
+                              double* D, double sig_prev, int c) {  // sig_prev: sigma at the previous point (MODE 1); c: the chain
   constexpr int X = M::X, V = M::V, Z = M::Z, U = M::U;
   const int S = sy.S, L = bd.nsteps, NV = sy.NV;
   double Lam[RM * X], zbar[RM * Z];
@@ -593,7 +601,7 @@ CHMC_HD inline void rev_block(const Sys& sy, const BlockDesc& bd, const ChainCon
     for (int i = 0; i < RM; ++i)
       for (int j = 0; j < i; ++j) D[j * RM + i] = D[i * RM + j];
   }
-  const double sig = sy.noisy ? sigma_at(sy, q) : 0.0;
+  const double sig = sy.noisy ? sigma_at(sy, q, c) : 0.0;
   const double s2 = sig * (MODE == 0 ? sig : sig_prev);  // dc_dn_l * dc_dn_r (:772-791)
   for (int i = 0; i < RM; ++i) {
     if (sy.noisy && i < bd.ny) D[i * RM + i] += s2;  // dc/dn dc/dn^T (:772-791)
@@ -638,7 +646,7 @@ struct KFwd {
     double* traj = store_traj ? (store_traj == 2 ? w.trajw : pick(sl.traj, s)) + (size_t)c * sy.TRJ + (size_t)(bd.step0 + CHMC_TPAD * b) * M::X
                               : nullptr;
     double cp[RM];
-    fwd_block<M, RM>(sy, bd, cc, q, sy.xobs + (size_t)c * sy.T * M::X, traj, cp);
+    fwd_block<M, RM>(sy, bd, cc, c, q, sy.xobs + (size_t)c * sy.T * M::X, traj, cp);
     double* out = w.cpad + ((size_t)c * sy.Kmax + b) * RM;
     for (int i = 0; i < RM; ++i) out[i] = cp[i];
   }
@@ -717,6 +725,24 @@ struct KXobs {
       CHMC_UNROLL
       for (int i = 0; i < PF * V; ++i) cur[i] = nxt[i];
     }
+  }
+};
+
+// Data simulated from the chains' own positions (chmc_simulate_observations_device): a work item per (chain, observation),
+//   y_c[t] = obs_func(x_c(t_obs)) + sigma_c n_c[t]      (no noise term without observation noise; sigma_c = sigma_at),
+// the expression the forward scans form before they subtract y, from x_obs_seq [B][T][X] of those positions (KXobs).
+template <class M>
+struct KSimObs {
+  Sys sy;
+  Slots sl;
+  const double* xobs;
+  double* yout;  // [B][T]
+  CHMC_HD void operator()(int tid) const {
+    const int c = tid / sy.T, t = tid - c * sy.T;
+    const double* q = pick(sl.q, sl.cur[c]) + (size_t)c * sy.Q;
+    double yv = M::obs(xobs + ((size_t)c * sy.T + t) * M::X);
+    if (sy.noisy) yv += sigma_at(sy, q, c) * q[sy.U + sy.NV + t];
+    yout[(size_t)c * sy.T + t] = yv;
   }
 };
 
@@ -847,11 +873,11 @@ struct KStateBlk {
     cc.init(q, sy.dl);
     double* traj = pick(sl.traj, s) + (size_t)c * sy.TRJ + (size_t)(bd.step0 + CHMC_TPAD * b) * M::X;
     double cp[RM];
-    fwd_block<M, RM>(sy, bd, cc, q, sy.xobs + (size_t)c * sy.T * M::X, traj, cp);
+    fwd_block<M, RM>(sy, bd, cc, c, q, sy.xobs + (size_t)c * sy.T * M::X, traj, cp);
     double* cout_ = w.cpad + ((size_t)c * sy.Kmax + b) * RM;
     for (int i = 0; i < RM; ++i) cout_[i] = cp[i];
     double D[RM * RM], Ju[RM * U];
-    rev_block<M, RM, 0>(sy, bd, cc, q, q, traj, pick(sl.Jv, s) + (size_t)c * RM * sy.NV, nullptr, Ju, D, 0.0);
+    rev_block<M, RM, 0>(sy, bd, cc, q, q, traj, pick(sl.Jv, s) + (size_t)c * RM * sy.NV, nullptr, Ju, D, 0.0, c);
     const size_t cb = (size_t)c * sy.Kmax + b;
     double ld = chol_lower<RM>(D);
     double* fd = pick(sl.facD, s) + cb * RM * RM;
@@ -918,7 +944,7 @@ struct KStateChain {
 template <int RM>
 CHMC_HD inline double var_sigma_grad_terms(const Sys& sy, const BlockDesc& bd, const double* q, const double* Wu, int U,
                                            const double* Mb, double* g) {
-  const double sg = sigma_at(sy, q);
+  const double sg = exp(q[sy.Z]);  // (variable noise only: sigma_at of any chain)
   const double* n = q + sy.U + sy.NV + bd.obs0;
   double* gn = g + sy.U + sy.NV + bd.obs0;
   double acc = 0.0;
@@ -1291,13 +1317,13 @@ struct KNewtonBlk {
     cc.init(q, sy.dl);
     double* traj = w.trajw + (size_t)c * sy.TRJ + (size_t)(bd.step0 + CHMC_TPAD * b) * M::X;
     double cp[RM];
-    fwd_block<M, RM>(sy, bd, cc, q, sy.xobs + (size_t)c * sy.T * M::X, traj, cp);
+    fwd_block<M, RM>(sy, bd, cc, c, q, sy.xobs + (size_t)c * sy.T * M::X, traj, cp);
     const size_t cb = (size_t)c * sy.Kmax + b;
     double* cout_ = w.cpad + cb * RM;
     for (int i = 0; i < RM; ++i) cout_[i] = cp[i];
     double D[RM * RM], JuL[RM * U];
     rev_block<M, RM, 1>(sy, bd, cc, q, q, traj, nullptr, pick(sl.Jv, sp) + (size_t)c * RM * sy.NV, JuL, D,
-                        sy.noisy ? sigma_at(sy, pick(sl.q, sp) + (size_t)c * sy.Q) : 0.0);
+                        sy.noisy ? sigma_at(sy, pick(sl.q, sp) + (size_t)c * sy.Q, c) : 0.0, c);
     int piv[RM];
     lu_factor<RM>(D, piv);
     lu_solve<RM, 1>(D, piv, cp);
@@ -1551,14 +1577,14 @@ struct KUpdate {
     const int t = col - sy.NV;
     const int b = sy.obs2blk[t];
     const int j = t - sy.blk[b].obs0;
-    return j < sy.blk[b].ny ? sigma_at(sy, pick(sl.q, sl.cur[c] ^ which) + (size_t)c * sy.Q) * w.lampad2[((size_t)c * sy.Kmax + b) * RM + j] : 0.0;
+    return j < sy.blk[b].ny ? sigma_at(sy, pick(sl.q, sl.cur[c] ^ which) + (size_t)c * sy.Q, c) * w.lampad2[((size_t)c * sy.Kmax + b) * RM + j] : 0.0;
   }
   CHMC_HD unsigned long long* red(int c) const { return TGT == 0 ? &w.ndq[c] : nullptr; }
   CHMC_HD double ncol_part(int c, int col, int which) const {  // observation-noise columns: dc/dn = sigma on y rows (:601-608)
     const int t = col - sy.NV;
     const int b = sy.obs2blk[t];
     const int j = t - sy.blk[b].obs0;
-    return j < sy.blk[b].ny ? sigma_at(sy, pick(sl.q, sl.cur[c] ^ which) + (size_t)c * sy.Q) * w.lampad[((size_t)c * sy.Kmax + b) * RM + j] : 0.0;
+    return j < sy.blk[b].ny ? sigma_at(sy, pick(sl.q, sl.cur[c] ^ which) + (size_t)c * sy.Q, c) * w.lampad[((size_t)c * sy.Kmax + b) * RM + j] : 0.0;
   }
   CHMC_HD unsigned long long operator()(int c, int idx) const {
     int which = this->which, qsel = this->qsel;
@@ -1871,7 +1897,7 @@ struct KUpdatePB {  // one step per work item
         const int b = sy.obs2blk[t];
         const int j = t - sy.blk[b].obs0;
         if (j < sy.blk[b].ny) {
-          const double sg = sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q);
+          const double sg = sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c);
           d = sg * w.lampad[((size_t)c * sy.Kmax + b) * RM + j];
           if (TGT == 3) d2 = sg * w.lampad2[((size_t)c * sy.Kmax + b) * RM + j];
         }
@@ -1994,7 +2020,7 @@ struct KUpdatePBPair {
           const int b = sy.obs2blk[t];
           const int j = t - sy.blk[b].obs0;
           if (j < sy.blk[b].ny) {
-            const double sg = sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q);
+            const double sg = sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c);
             d = sg * lampad[((size_t)c * sy.Kmax + b) * RM + j];
           }
         }
@@ -2240,7 +2266,7 @@ struct KJw {
       double a2 = 0.0;
       for (int k = 0; k < bd.ncols; ++k) a2 += Jv[k] * wv[k];
       acc += a2;
-      if (sy.noisy && i < bd.ny) acc += sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q) * vct[sy.U + sy.NV + bd.obs0 + i];
+      if (sy.noisy && i < bd.ny) acc += sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) * vct[sy.U + sy.NV + bd.obs0 + i];
     }
     w.cpad[cb * RM + i] = acc;
   }

@@ -10,7 +10,8 @@
 // NOT in the list, because they are not per chain (a view shares them):
 //   work.zeros [256], work.nfallback [128], work.ticket (null);
 //   work.n_active [12] = [batch | half 0 | half 1] x 4 round slots: the view of half h counts in slots 4 (1 + h) ..;
-//   d_y [T], d_m0 [3][U][U], the block tables d_blk / d_obs2blk / d_blk_full and the work orders d_order / d_order_half /
+//   d_y [T] (the observations every chain shares until chmc_set_observations: the per-chain d_yc IS in the list),
+//   d_m0 [3][U][U], the block tables d_blk / d_obs2blk / d_blk_full and the work orders d_order / d_order_half /
 //   d_order_ident (a view takes its half's order);
 //   d_ham [B][4] ([B][3] Hamiltonian terms, or [B] values + [B][3] statistics: not chain-major) and the arrays of the
 //   trajectory trees (TreeState, d_tree_*) and the scratch of chmc_gd_objective_device (d_gd), which only whole-batch launches use.
@@ -35,6 +36,9 @@ struct ChainView {
   int* d_ncommit;          // [B] inner steps a chain has completed in the current step
   double *d_qbak, *d_pbak; // [B][Q] chmc_snapshot
   int *d_nsteps, *d_ndone; // [B] per-chain trajectory lengths / steps done (k_traj_chain)
+  // allocated by chmc_set_observations only (null, and kAbsent in the list, until then):
+  double* d_yc = nullptr;    // [B][T] per-chain observations: Sys::y with Sys::ystride = T
+  double* d_sigc = nullptr;  // [B] per-chain fixed observation-noise std: Sys::sigc
 };
 
 enum ChainArrayKind {
@@ -95,6 +99,9 @@ void for_each_chain_array(ChainView& v, const KernelPlan& plan, size_t npart, F&
   arr(v.d_q0, Q, kLazy), arr(v.d_p0, Q, kLazy), arr(v.d_ncommit, 1, kLazy);
   arr(v.d_qbak, Q, kLazy), arr(v.d_pbak, Q, kLazy);
   arr(v.d_nsteps, 1, kLazy), arr(v.d_ndone, 1, kLazy);
+  // per-chain data: no context has them at chmc_create; chmc_set_observations allocates them, and from then on a view
+  // advances them like every other array of the list
+  arr(v.d_yc, sy.T, only(v.d_yc != nullptr)), arr(v.d_sigc, 1, only(v.d_sigc != nullptr));
 }
 
 // The per-step outputs of chmc_leapfrog_step live in ONE allocation (chmc_ctx::d_out) so that they cross PCIe in a single

@@ -253,8 +253,8 @@ __device__ __forceinline__ void newton_comb_wg(const Sys& sy, const Slots& sl, c
       }
     }
     if (i == jj) {  // noise term on the observation rows (dc_dn_l * dc_dn_r, :772-791), identity padding
-      const double sg_ = sy.noisy ? sigma_at(sy, q) : 0.0;
-      if (sy.noisy && i < bd.ny) tt += sg_ * sigma_at(sy, pick(sl.q, sp) + (size_t)c * sy.Q);
+      const double sg_ = sy.noisy ? sigma_at(sy, q, c) : 0.0;
+      if (sy.noisy && i < bd.ny) tt += sg_ * sigma_at(sy, pick(sl.q, sp) + (size_t)c * sy.Q, c);
       if (i >= bd.nrows) tt = 1.0;
     }
     Dl[t] = tt;
@@ -296,7 +296,7 @@ __device__ __forceinline__ void newton_comb_wg(const Sys& sy, const Slots& sl, c
         tt += zl[i * Z + mz] * gs;
       }
     } else {
-      tt = i < bd.ny ? sigma_at(sy, q) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
+      tt = i < bd.ny ? sigma_at(sy, q, c) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
     }
     JuS[tid] = tt;
     if constexpr (STATE) pick(sl.JuP, sp)[cb * RM * U + tid] = tt;
@@ -379,7 +379,7 @@ __device__ __forceinline__ void jw_pb_wg(const Sys& sy, const Slots& sl, const W
       }
       const double* ju = pick(sl.JuP, s) + (cb * RM + i) * sy.U;
       for (int d = 0; d < sy.U; ++d) a += ju[d] * (minv ? metric_inv_u(sy, vct, d) : vct[d]);
-      const double sg = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q) : 0.0;
+      const double sg = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) : 0.0;
       if (sy.noisy && i < bd.ny) a += sg * vct[sy.U + sy.NV + bd.obs0 + i];
       for (int d = 0; d < sy.U; ++d) a2 += ju[d] * (minv ? metric_inv_u(sy, vct2, d) : vct2[d]);
       if (sy.noisy && i < bd.ny) a2 += sg * vct2[sy.U + sy.NV + bd.obs0 + i];
@@ -600,7 +600,7 @@ __device__ __forceinline__ void retract_chain_body(const Sys& sy, const Slots& s
       double Ul[X];
       int s0;
       bool have;
-      (void)fwd_par_sweeps<M, RM, CHMC_CHAIN_SCAN_WAVES, 0, NW>(sy, w, bd, q, sy.xobs + (size_t)ca * sy.T * X, traj, guess, out,
+      (void)fwd_par_sweeps<M, RM, CHMC_CHAIN_SCAN_WAVES, 0, NW>(sy, w, bd, ca, q, sy.xobs + (size_t)ca * sy.T * X, traj, guess, out,
                                                                 64 * CHMC_CHAIN_SCAN_WAVES + 2,
                                          it == 0 ? 2 : 1, Ul, s0, have);
       if (tid == 0)
@@ -784,7 +784,7 @@ __global__ void __launch_bounds__(64 * NW, 2)
       double Ul[X];
       int s0;
       bool have;
-      (void)fwd_par_sweeps<M, RM, CHMC_CHAIN_SCAN_WAVES, 0, NW>(sy, w, bd, q1, sy.xobs + (size_t)c2 * sy.T * X, traj1, w.trajw + toff, out,
+      (void)fwd_par_sweeps<M, RM, CHMC_CHAIN_SCAN_WAVES, 0, NW>(sy, w, bd, c2, q1, sy.xobs + (size_t)c2 * sy.T * X, traj1, w.trajw + toff, out,
                                          64 * CHMC_CHAIN_SCAN_WAVES + 2, 3, Ul, s0, have);
       if (tid == 0)
         for (int i = bd.nrows; i < RM; ++i) out[i] = 0.0;

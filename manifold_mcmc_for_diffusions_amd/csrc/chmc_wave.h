@@ -643,8 +643,8 @@ __global__ void __launch_bounds__(256) k_rev_wave(Sys sy, Slots sl, Work w, int 
           for (int jj = 0; jj < i; ++jj) Dacc[jj * RM + i] = Dacc[i * RM + jj];
       }
       // dc_dn_l * dc_dn_r (:772-791): sigma at the iterate times sigma at the point whose rows are stored
-      const double sg_ = sy.noisy ? sigma_at(sy, q) : 0.0;
-      const double s2 = sg_ * (MODE == 0 || !sy.noisy ? sg_ : sigma_at(sy, pick(sl.q, sl_) + (size_t)c * sy.Q));
+      const double sg_ = sy.noisy ? sigma_at(sy, q, c) : 0.0;
+      const double s2 = sg_ * (MODE == 0 || !sy.noisy ? sg_ : sigma_at(sy, pick(sl.q, sl_) + (size_t)c * sy.Q, c));
 #pragma unroll URM
       for (int i = 0; i < RM; ++i) {
         if (sy.noisy && i < bd.ny) Dacc[i * RM + i] += s2;  // dc/dn dc/dn^T (:772-791)
@@ -669,7 +669,7 @@ __global__ void __launch_bounds__(256) k_rev_wave(Sys sy, Slots sl, Work w, int 
         ju[i * U + d] = tt;
       }
       // d(sigma(u) n_i) / du_sigma = sigma n_i on the observation rows (g_y_bar :559-569)
-      if (M::VS) ju[i * U + Z] = i < bd.ny ? sigma_at(sy, q) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
+      if (M::VS) ju[i * U + Z] = i < bd.ny ? sigma_at(sy, q, c) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
     }
   }
 }
@@ -948,8 +948,8 @@ __global__ void __launch_bounds__(64, (M::X * M::V <= 4) ? CHMC_LEAN_WAVES_PB : 
     const int i = lane / RM, jj = lane - i * RM;
     double v = Dl[lane];
     if (i == jj) {
-      const double sg_ = sy.noisy ? sigma_at(sy, q) : 0.0;
-      if (sy.noisy && i < bd.ny) v += sg_ * sigma_at(sy, pick(sl.q, sl_) + (size_t)c * sy.Q);  // dc_dn dc_dn^T (:772-791)
+      const double sg_ = sy.noisy ? sigma_at(sy, q, c) : 0.0;
+      if (sy.noisy && i < bd.ny) v += sg_ * sigma_at(sy, pick(sl.q, sl_) + (size_t)c * sy.Q, c);  // dc_dn dc_dn^T (:772-791)
       if (i >= bd.nrows) v = 1.0;
     }
     w.Dw[cb * RM * RM + lane] = v;
@@ -967,7 +967,7 @@ __global__ void __launch_bounds__(64, (M::X * M::V <= 4) ? CHMC_LEAN_WAVES_PB : 
         tt += zl[i * Z + mz] * gs;
       }
     } else {
-      tt = i < bd.ny ? sigma_at(sy, q) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
+      tt = i < bd.ny ? sigma_at(sy, q, c) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
     }
     pick(sl.JuP, sl_)[cb * RM * U + e] = tt;
   }
@@ -1481,8 +1481,8 @@ __device__ __forceinline__ void newton_comb_body(const Sys& sy, const Slots& sl,
     const int i = e / RM, jj = e - i * RM;
     double v = Dl[e];
     if (i == jj) {
-      const double sg_ = sy.noisy ? sigma_at(sy, q) : 0.0;
-      if (sy.noisy && i < bd.ny) v += sg_ * sigma_at(sy, pick(sl.q, sl_) + (size_t)c * sy.Q);  // dc_dn_l * dc_dn_r (:772-791)
+      const double sg_ = sy.noisy ? sigma_at(sy, q, c) : 0.0;
+      if (sy.noisy && i < bd.ny) v += sg_ * sigma_at(sy, pick(sl.q, sl_) + (size_t)c * sy.Q, c);  // dc_dn_l * dc_dn_r (:772-791)
       if (i >= bd.nrows) v = 1.0;
     }
     if constexpr (FACTOR) Dl[e] = v;
@@ -1501,7 +1501,7 @@ __device__ __forceinline__ void newton_comb_body(const Sys& sy, const Slots& sl,
         tt += zl[i * Z + mz] * gs;
       }
     } else {
-      tt = i < bd.ny ? sigma_at(sy, q) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
+      tt = i < bd.ny ? sigma_at(sy, q, c) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
     }
     if constexpr (FACTOR) JuS[e] = tt;
     else (STATE ? pick(sl.JuP, sl_) : w.JuL)[cb * RM * U + e] = tt;
@@ -1744,7 +1744,7 @@ __global__ void __launch_bounds__(64) k_rev_wave_ldsrows(Sys sy, Slots sl, Work 
     if (d < Z) {
       for (int mz = 0; mz < Z; ++mz) tt += zaccS[(i * Z + mz) * 64] * G[mz * Z + d];
     } else {
-      tt = i < bd.ny ? sigma_at(sy, q) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
+      tt = i < bd.ny ? sigma_at(sy, q, c) * q[sy.U + sy.NV + bd.obs0 + i] : 0.0;
     }
     ju[e] = tt;
   }
@@ -1792,8 +1792,8 @@ __global__ void __launch_bounds__(256) k_gram_rows(Sys sy, Slots sl, Work w, int
   }
   if (lane == 0) {
     // dc_dn_l * dc_dn_r: sigma at the point of the rows Ja (the Newton iterate, or the slot itself) times sigma of the slot
-    const double sgb = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q) : 0.0;
-    const double s2 = sgb * (newton && sy.noisy ? sigma_at(sy, (qsel ? w.qb : pick(sl.q, s ^ 1)) + (size_t)c * sy.Q) : sgb);
+    const double sgb = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) : 0.0;
+    const double s2 = sgb * (newton && sy.noisy ? sigma_at(sy, (qsel ? w.qb : pick(sl.q, s ^ 1)) + (size_t)c * sy.Q, c) : sgb);
     double* Do = w.Dw + cb * RM * RM + (size_t)g * NRG * RM;
 #pragma unroll
     for (int i = 0; i < NRG; ++i) {
@@ -1887,8 +1887,8 @@ __global__ void __launch_bounds__(64) k_gram_rows_mfma(Sys sy, Slots sl, Work w,
     }
     // D[g + 4 m][r] (m = 0, 1; r < 8) = quadrant (0, 0), here, + quadrant (1, 1): registers 2, 3 of lane r + 8
     const double d0 = acc[0] + __shfl_down(acc[2], 8, 64), d1 = acc[1] + __shfl_down(acc[3], 8, 64);
-    const double sgb = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q) : 0.0;
-    const double s2 = sgb * (newton && sy.noisy ? sigma_at(sy, (qsel ? w.qb : pick(sl.q, s ^ 1)) + (size_t)c * sy.Q) : sgb);
+    const double sgb = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) : 0.0;
+    const double s2 = sgb * (newton && sy.noisy ? sigma_at(sy, (qsel ? w.qb : pick(sl.q, s ^ 1)) + (size_t)c * sy.Q, c) : sgb);
     double* Do = w.Dw + cb * RM * RM;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -1925,8 +1925,8 @@ __global__ void __launch_bounds__(64) k_gram_rows_mfma(Sys sy, Slots sl, Work w,
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
   }
-  const double sgb = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q) : 0.0;
-  const double s2 = sgb * (newton && sy.noisy ? sigma_at(sy, (qsel ? w.qb : pick(sl.q, s ^ 1)) + (size_t)c * sy.Q) : sgb);
+  const double sgb = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) : 0.0;
+  const double s2 = sgb * (newton && sy.noisy ? sigma_at(sy, (qsel ? w.qb : pick(sl.q, s ^ 1)) + (size_t)c * sy.Q, c) : sgb);
   double* Do = w.Dw + cb * RM * RM;
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
@@ -1960,7 +1960,7 @@ __global__ void __launch_bounds__(256) k_nld_grad_wave(Sys sy, const double* qin
   ChainConsts<M> cc;
   cc.init(q, sy.dl);
   const int S = sy.S, ntile = (S + 63) >> 6;
-  const double sg = sigma_at(sy, q);  // a number, or exp(u[Z])
+  const double sg = sigma_at(sy, q, c);  // a number, or exp(u[Z])
   const double is2 = 1.0 / (sg * sg);
   double Lam[X], zacc[Z], vsq = 0.0, rsq = 0.0;
 #pragma unroll
@@ -1972,7 +1972,7 @@ __global__ void __launch_bounds__(256) k_nld_grad_wave(Sys sy, const double* qin
       double og[X];
       const double* xo = traj + (size_t)(j + 1) * S * X;  // state at observation time j (wave-uniform)
       M::obs_grad(xo, og);
-      const double rj = sy.y[j] - M::obs(xo);
+      const double rj = y_of(sy, c)[j] - M::obs(xo);
       rsq += rj * rj;
       const double wj = -rj * is2;
 #pragma unroll
@@ -2296,7 +2296,7 @@ __global__ void __launch_bounds__(256) k_jw_wave(Sys sy, Slots sl, Work w, int w
     if (i < bd.nrows) {
       const double* ju = pick(sl.JuP, s) + (cb * RM + i) * sy.U;
       for (int d = 0; d < sy.U; ++d) a += ju[d] * (minv ? metric_inv_u(sy, vct, d) : vct[d]);
-      const double sg = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q) : 0.0;
+      const double sg = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) : 0.0;
       if (sy.noisy && i < bd.ny) a += sg * vct[sy.U + sy.NV + bd.obs0 + i];
       if (TWO) {
         for (int d = 0; d < sy.U; ++d) a2 += ju[d] * (minv ? metric_inv_u(sy, vct2, d) : vct2[d]);
@@ -2441,7 +2441,7 @@ __device__ __forceinline__ void jw_pb_body(const Sys& sy, const Slots& sl, const
       }
       const double* ju = pick(sl.JuP, s) + (cb * RM + i) * sy.U;
       for (int d = 0; d < sy.U; ++d) a += ju[d] * (minv ? metric_inv_u(sy, vct, d) : vct[d]);
-      const double sg = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q) : 0.0;
+      const double sg = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) : 0.0;
       if (sy.noisy && i < bd.ny) a += sg * vct[sy.U + sy.NV + bd.obs0 + i];
       if (TWO) {
         for (int d = 0; d < sy.U; ++d) a2 += ju[d] * (minv ? metric_inv_u(sy, vct2, d) : vct2[d]);
@@ -5140,7 +5140,7 @@ __global__ void __launch_bounds__(STORE ? 64 * (1 + CHMC_SCAN_HELPERS) : 64)
   const double* xobs = sy.xobs + (size_t)c * sy.T * X;
   ChainConsts<M> cc;
   cc.init(q, sy.dl);
-  const double sig = sy.noisy ? sigma_at(sy, q) : 0.0;
+  const double sig = sy.noisy ? sigma_at(sy, q, c) : 0.0;
   double x[X], xn[X];
   const double* vb = q + sy.U;
   if (bd.first) {
@@ -5154,7 +5154,7 @@ __global__ void __launch_bounds__(STORE ? 64 * (1 + CHMC_SCAN_HELPERS) : 64)
   {
     const double* nn = q + sy.U + sy.NV;
     for (int j = 0; j < bd.ny; ++j) {
-      ov[2 * j] = sy.y[bd.obs0 + j];
+      ov[2 * j] = y_of(sy, c)[bd.obs0 + j];
       ov[2 * j + 1] = sy.noisy ? nn[bd.obs0 + j] : 0.0;
     }
   }
@@ -5303,7 +5303,7 @@ __global__ void __launch_bounds__(STORE ? 64 * (1 + CHMC_SCAN_HELPERS) : 64)
 // WG > W: the calling workgroup has WG wavefronts of which the first W integrate (the per-chain kernels: 8 wavefronts, 256
 // segments on 4 of them); the others only keep the workgroup barriers and the loop control in step.
 template <class M, int RM, int W, int PRE = 0, int WG = W>
-__device__ __forceinline__ bool fwd_par_sweeps(const Sys& sy, const Work& w, const BlockDesc& bd, const double* q,
+__device__ __forceinline__ bool fwd_par_sweeps(const Sys& sy, const Work& w, const BlockDesc& bd, int c, const double* q,
                                                const double* xobs, double* traj, const double* guess, double* out, int MAXS,
                                                int gsel, double (&Ul)[M::X], int& s0r, bool& haver) {
   constexpr int X = M::X, V = M::V;
@@ -5344,7 +5344,7 @@ __device__ __forceinline__ bool fwd_par_sweeps(const Sys& sy, const Work& w, con
   const double* nn = q + sy.U + sy.NV;
   ChainConsts<M> cc;
   cc.init(q, sy.dl);
-  const double sig = sy.noisy ? sigma_at(sy, q) : 0.0;
+  const double sig = sy.noisy ? sigma_at(sy, q, c) : 0.0;
   double x0[X];
   if (bd.first) {
     M::gx0(cc.z, q + sy.U, x0);
@@ -5639,7 +5639,7 @@ __device__ __forceinline__ bool fwd_par_sweeps(const Sys& sy, const Work& w, con
       for (int a = 0; a < X; ++a) x[a] = xn[a];
       if ((s + 1) % S == 0) {  // s + 1 is the time of local observation j
         const int j = (s + 1) / S - 1;
-        if (j < bd.ny) out[j] = (M::obs(x) + (sy.noisy ? sig * nn[bd.obs0 + j] : 0.0)) - sy.y[bd.obs0 + j];
+        if (j < bd.ny) out[j] = (M::obs(x) + (sy.noisy ? sig * nn[bd.obs0 + j] : 0.0)) - y_of(sy, c)[bd.obs0 + j];
       }
     };
     if (PRE > 0 && pre) {
@@ -5720,7 +5720,7 @@ __global__ void __launch_bounds__(64 * W) k_fwd_par(Sys sy, Slots sl, Work w, in
   // (one 16-row block per chain: the layouts of the per-chain kernels, chmc_retract.h, whose arithmetic this launch repeats
   // bit for bit -- no sequential fallback outside a loop, the sweeps go on until settled, as there)
   const bool chain16 = RM > 8 && sy.Kmax == 1;
-  const bool converged = fwd_par_sweeps<M, RM, W>(sy, w, bd, q, xobs, traj, guess, out,
+  const bool converged = fwd_par_sweeps<M, RM, W>(sy, w, bd, c, q, xobs, traj, guess, out,
                                                   (chain16 && !apend) ? 64 * W + 2 : MAXS, gsel, Ul, s0, have);
   if (apend) {
     if (!converged) {
@@ -5742,7 +5742,7 @@ __global__ void __launch_bounds__(64 * W) k_fwd_par(Sys sy, Slots sl, Work w, in
     const double* nn = q + sy.U + sy.NV;
     ChainConsts<M> cc;
     cc.init(q, sy.dl);
-    const double sig = sy.noisy ? sigma_at(sy, q) : 0.0;
+    const double sig = sy.noisy ? sigma_at(sy, q, c) : 0.0;
     double x[X], xn[X];
     if (bd.first) {
       M::gx0(cc.z, q + sy.U, x);
@@ -5758,7 +5758,7 @@ __global__ void __launch_bounds__(64 * W) k_fwd_par(Sys sy, Slots sl, Work w, in
       for (int a = 0; a < X; ++a) x[a] = xn[a];
       if ((s + 1) % S == 0) {
         const int j = (s + 1) / S - 1;
-        if (j < bd.ny) out[j] = (M::obs(x) + (sy.noisy ? sig * nn[bd.obs0 + j] : 0.0)) - sy.y[bd.obs0 + j];
+        if (j < bd.ny) out[j] = (M::obs(x) + (sy.noisy ? sig * nn[bd.obs0 + j] : 0.0)) - y_of(sy, c)[bd.obs0 + j];
       }
     }
 #pragma unroll

@@ -151,7 +151,7 @@ class DynamicTransition:
 
 def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0, total_chains=None, n_head=6,
                         trace_dir=None, trace_func=None, callback=None, per_chain_step_size=True, path_posterior=None,
-                        **kw):
+                        groups=None, n_groups=None, **kw):
     """Momentum refresh -> dynamic transition -> partition switch, `n_iter` times for all chains of `ctx`, with
     dual-averaging step-size adaptation on the tree's accept statistic during warm-up: the reference's sampling loop
     (scripts/utils.py:292-306, 338-365), batched.  As in Mici every chain adapts its own step size during warm-up (the
@@ -161,9 +161,19 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     offer, which keeps the lock-step batch full during warm-up (the FitzHugh-Nagumo example: 30 k against 24 k leapfrog
     steps/s end to end), but a chain that starts where that step size is far too long never moves.
     path_posterior: a `paths.PathPosterior` of `ctx`; the latent path of every post-warm-up state (after the partition
-    switch) is folded into its running moments, and out["path_posterior"] is its `pooled()` result."""
+    switch) is folded into its running moments, and out["path_posterior"] is its `pooled()` result.
+    groups [B], n_groups: chains that sample different posteriors in one context (per-chain observations): groups[c] is the
+    global id of chain c's data set.  Warm-up is per chain as before; the main phase of a chain runs with the mean of the
+    adapted step sizes of ITS group over all ranks instead of the all-chain mean (out["group_step_sizes"] [G]; one group
+    gives the numbers of the call without `groups`).  Needs per_chain_step_size."""
     import time
-    from .sampling import DualAveragingStepSize, PerChainDualAveragingStepSize, _mean_over_all_chains
+    from .sampling import (DualAveragingStepSize, PerChainDualAveragingStepSize, _mean_over_all_chains,
+                           _group_sums_over_all_chains, check_groups)
+    group_eps = None
+    if groups is not None:
+        groups, G = check_groups(groups, n_groups, ctx.B)
+        if not per_chain_step_size:
+            raise ValueError("groups need per_chain_step_size=True (one shared step size cannot serve several posteriors)")
     tr = DynamicTransition(ctx, step_size, seed, chain_offset=chain_offset, total_chains=total_chains, **kw)
     B = ctx.B
     adapter, adapted = None, None
@@ -211,7 +221,12 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
                 tr.step_size = adapter.update(st["accept_stat"])  # [B]: every chain its own step size during warm-up
                 if it == n_adapt - 1:
                     adapted = np.asarray(adapter.final(), dtype=np.float64).copy()  # per chain, before averaging
-                    tr.step_size = _mean_over_all_chains(adapted.sum(), B)
+                    if groups is None:
+                        tr.step_size = _mean_over_all_chains(adapted.sum(), B)
+                    else:  # every chain: the mean over its group's chains
+                        sums, counts = _group_sums_over_all_chains(adapted, groups, G)
+                        group_eps = sums / np.maximum(counts, 1.0)
+                        tr.step_size = group_eps[groups] if G > 1 else float(group_eps[0])
             else:
                 tr.step_size = adapter.update(acc)
                 if it == n_adapt - 1:
@@ -222,6 +237,8 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     out = dict(heads=heads, accept_stat=acc_hist, step_size=eps_hist, n_step=nstep_hist, integrator_error=err_hist,
                final_step_size=float(np.mean(tr.step_size)), adapted_step_sizes=adapted, chain_outcomes_dynamic=outcome,
                per_chain={k: v / n_main for k, v in per_chain.items()})
+    if groups is not None:
+        out["group_step_sizes"] = group_eps
     if path_posterior is not None:
         out["path_posterior"] = path_posterior.pooled()
     if writer is not None:
@@ -230,7 +247,7 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
         c1 = ctx.counters()
         main = {k: np.asarray(v)[:, n_adapt:] for k, v in writer.arrays().items()}
         out["summary"] = save_summary(trace_dir, main, None, time.perf_counter() - t0, float(np.mean(tr.step_size)),
-                                      {k: c1[k] - c0[k] for k in c1 if k != "_"})
+                                      {k: c1[k] - c0[k] for k in c1 if k != "_"}, groups=groups)
         import os
         out["trace_files"] = {k: os.path.join(trace_dir, f"trace_{k}.npy") for k in writer.arrays()}
     return out

@@ -47,27 +47,35 @@ def find_initial_state_by_linear_interpolation(model, obs_interval, num_steps_pe
 def fhn_initial_draws(model, y_seq, num_chains, seed=20200710, chain_offset=0, total_chains=None):
     """The random inputs of the FitzHugh-Nagumo initial states (scripts/fhn_model_noisy_obs_chmc_experiment.py:105-117),
     one independent generator per chain (SeedSequence(seed).spawn(total)[chain]) so that any sharding of the chains
-    over ranks gives the same draws: u [B, Z], v_0 [B, V0], x_obs_seq_init [B, T, X] = [y, 0.5 N(0, 1)], generators."""
-    y_seq = np.asarray(y_seq, dtype=np.float64).reshape((-1, 1))
+    over ranks gives the same draws: u [B, Z], v_0 [B, V0], x_obs_seq_init [B, T, X] = [y, 0.5 N(0, 1)], generators.
+    y_seq [T] / [T, 1]: one data set for every chain; [B, T, 1]: the data of THIS call's chains, a row per chain (per-chain
+    observations, ChmcContext.set_observations) -- every chain's x_obs_seq_init is built from its own row."""
+    y_seq = np.asarray(y_seq, dtype=np.float64)
+    if y_seq.ndim == 3:
+        if y_seq.shape[0] != num_chains or y_seq.shape[2] != 1:
+            raise ValueError(f"per-chain y_seq must have shape ({num_chains}, T, 1), got {y_seq.shape}")
+        y_rows = y_seq
+    else:
+        y_rows = np.broadcast_to(y_seq.reshape((-1, 1)), (num_chains, y_seq.size, 1))
     total = num_chains + chain_offset if total_chains is None else total_chains
     seqs = np.random.SeedSequence(seed).spawn(total)[chain_offset:chain_offset + num_chains]
     rngs = [np.random.default_rng(s) for s in seqs]
     us, v0s, xos = [], [], []
-    for rng in rngs:
+    for rng, y_c in zip(rngs, y_rows):
         us.append(rng.standard_normal(model.dim_z))
         v0s.append(rng.standard_normal(model.dim_v))  # sic: the script draws dim_v, equal to dim_v_0 for this model (:112)
-        xos.append(np.concatenate((y_seq, rng.standard_normal(y_seq.shape) * 0.5), -1))  # :105-106
+        xos.append(np.concatenate((y_c, rng.standard_normal(y_c.shape) * 0.5), -1))  # :105-106
     return np.stack(us), np.stack(v0s), np.stack(xos), rngs
 
 
 def fhn_initial_states(model, obs_interval, num_steps_per_obs, y_seq, num_chains, noisy, seed=20200710,
                        chain_offset=0, total_chains=None):
-    """Initial states for `num_chains` FitzHugh-Nagumo chains on the host (NumPy).
-    Returns q [B, Q], x_obs_seq [B, T, X], and the per-chain generators (next draw: the momentum)."""
+    """Initial states for `num_chains` FitzHugh-Nagumo chains on the host (NumPy); y_seq [T, 1], or [B, T, 1] with a data
+    set per chain.  Returns q [B, Q], x_obs_seq [B, T, X], and the per-chain generators (next draw: the momentum)."""
     us, v0s, xos, rngs = fhn_initial_draws(model, y_seq, num_chains, seed, chain_offset, total_chains)
     qs = []
     for u, v_0, xo in zip(us, v0s, xos):
-        q, _ = find_initial_state_by_linear_interpolation(model, obs_interval, num_steps_per_obs, y_seq, None,
+        q, _ = find_initial_state_by_linear_interpolation(model, obs_interval, num_steps_per_obs, xo[:, 0], None,
                                                           lambda rng, xo=xo: xo, noisy, u=u, v_0=v_0)
         qs.append(q)
     return np.stack(qs), xos, rngs
@@ -75,7 +83,8 @@ def fhn_initial_states(model, obs_interval, num_steps_per_obs, y_seq, num_chains
 
 def fhn_initial_states_device(ctx, model, y_seq, seed=20200710, chain_offset=0, total_chains=None, partition=0):
     """The same initial states solved on the device for all chains at once (`chmc_init_linear_interpolation`); the
-    state stays resident, nothing but the O(B T) draws crosses PCIe.  Returns the per-chain generators."""
+    state stays resident, nothing but the O(B T) draws crosses PCIe.  y_seq [T, 1], or [B, T, 1] with a data set per chain
+    (the context's per-chain observations).  Returns the per-chain generators."""
     us, v0s, xos, rngs = fhn_initial_draws(model, y_seq, ctx.B, seed, chain_offset, total_chains)
     ctx.init_by_linear_interpolation(us, v0s, xos, partition)
     return rngs
@@ -121,8 +130,13 @@ def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, thresho
     draw = 2^63 | k) and is dealt into its row by ONE library call (chmc_adam_begin_tries_device: start point, zero moments
     and gradient, the row's carried scan guess back to the cold guess) instead of rng.standard_normal + an upload + index
     assignments.  A try then depends on its own (chain, try number) only -- not on the row it runs in, on what ran there
-    before, or on when it was started -- so the winners do not depend on the slot schedule (see the public function)."""
+    before, or on when it was started -- so the winners do not depend on the slot schedule (see the public function).
+
+    Per-chain observations (ChmcContext.set_observations): row c of the library's objective is judged against chain c's data,
+    so rows do not change hands -- a chain runs its tries one after the other in its own row.  In keyed mode its answer is the
+    one it finds in a context that holds only its own data set."""
     import torch
+    own_rows = getattr(ctx, "per_chain_observations", False)
     if _calls is None:                                     # the two library calls of an iteration, on device pointers
         dev = _torch_device(ctx)
         sync = lambda: torch.cuda.synchronize(dev)         # (the library enqueues on its own stream)
@@ -195,7 +209,7 @@ def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, thresho
             sync()
             log_sigma = ls_host.numpy()
         else:
-            log_sigma = np.log(float(ctx.sigma))
+            log_sigma = np.log(np.asarray(ctx.sigma, dtype=np.float64))  # a number, or per chain = per row (own_rows)
         with np.errstate(invalid="ignore", over="ignore"):
             msq = 2.0 * (val - T * log_sigma - 0.5 * sq) / T   # mean squared residual
             running = slot_state == 0
@@ -226,6 +240,16 @@ def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, thresho
         if touched:
             free = np.flatnonzero(slot_state == 2)
             searching = np.flatnonzero(winner < 0)
+            if own_rows:  # a free row goes back to its own chain, for that chain's next try
+                take = free[(winner[free] < 0) & (n_running[free] == 0) & (next_try[free] < limit)]
+                free = free[:0]
+                if take.size:
+                    tryno[take], slot_state[take] = next_try[take], 0
+                    for c in take.tolist():
+                        status[c][int(next_try[c])] = c
+                    next_try[take] += 1
+                    n_running[take] += 1
+                    fresh.extend(take.tolist())
             while free.size:
                 cand = searching[(n_running[searching] < max_parallel_tries) & (next_try[searching] < limit)]
                 if cand.size == 0:
@@ -283,7 +307,7 @@ def _adam_on_device(ctx, rng, adam_step_size, max_iters, max_init_tries, thresho
     q = np.concatenate([u_v.cpu().numpy(), np.zeros((B, T))], 1)
     xo0 = np.zeros((B, T, ctx.X))
     ctx.set_state(q, None, xo0, 0)
-    sigma = np.exp(q[:, isig:isig + 1]) if var_sigma else float(ctx.sigma)
+    sigma = np.exp(q[:, isig:isig + 1]) if var_sigma else np.asarray(ctx.sigma, dtype=np.float64).reshape(-1, 1)
     res = -ctx.constr() / sigma
     assert (np.mean(res ** 2, 1) < threshold * (1 + 1e-9)).all()
     q[:, nuv:] = res
@@ -355,7 +379,7 @@ def find_initial_states_by_gradient_descent_noisy_system(ctx, rng=None, adam_ste
         q = np.concatenate([u_v, np.zeros((B, T))], 1)
         ctx.set_state(q, None, xo0, 0)
         c = ctx.constr()                                   # obs_func(x_t) - y_t  (n = 0: independent of sigma)
-        sigma = np.exp(u_v[:, iσ:iσ + 1]) if var_sigma else float(ctx.sigma)
+        sigma = np.exp(u_v[:, iσ:iσ + 1]) if var_sigma else np.asarray(ctx.sigma, dtype=np.float64).reshape(-1, 1)
         g = ctx.rmult_by_jacob_constr(c / sigma ** 2)[:, :nuv] + u_v
         if var_sigma:                                      # d/du_sigma [1/2 sum c^2 / sigma^2 + T log sigma]
             g[:, iσ] += T - np.sum((c / sigma) ** 2, 1)
@@ -425,12 +449,16 @@ GD_OUTCOMES = ("projected", "diverged", "projection failed", "budget")
 def fhn_x_obs_seq_init(y_seq, seed):
     """generate_x_obs_seq_init of the FitzHugh-Nagumo scripts ([y, 0.5 N(0, 1)], scripts/fhn_model_*_chmc_experiment.py:105-106)
     as a pure function of (global chain, try): `gen(chains, tries) -> [n, T, X]` with the hidden component of (chain c, try k)
-    drawn from np.random.default_rng([seed, c, k])."""
-    y = np.asarray(y_seq, dtype=np.float64).reshape((-1, 1))
+    drawn from np.random.default_rng([seed, c, k]).  y_seq [T] / [T, 1]: one data set; [N, T] / [N, T, 1] with N the chains
+    of the WHOLE job: per-chain data, row c the data of global chain c (the finder hands out global chain numbers)."""
+    y = np.asarray(y_seq, dtype=np.float64)
+    per_chain = y.ndim == 3 or (y.ndim == 2 and y.shape[1] != 1)
+    y = y.reshape((y.shape[0], -1, 1)) if per_chain else y.reshape((-1, 1))
 
     def gen(chains, tries):
-        return np.stack([np.concatenate((y, 0.5 * np.random.default_rng([int(seed), int(c), int(k)]).standard_normal(y.shape)), -1)
-                         for c, k in zip(chains, tries)])
+        rows = [y[int(c)] if per_chain else y for c in chains]
+        return np.stack([np.concatenate((yc, 0.5 * np.random.default_rng([int(seed), int(c), int(k)]).standard_normal(yc.shape)), -1)
+                         for yc, c, k in zip(rows, chains, tries)])
     return gen
 
 
@@ -504,7 +532,9 @@ def find_initial_states_by_gradient_descent(ctx, generate_x_obs_seq_init, seed, 
     Keyed draws only: try k of global chain c = chain_offset + row starts from the keyed normals (seed, stream c, draw
     2^63 | 2^62 | k) (chmc_fill_normal_device, filled on the device over all Q columns) and from
     generate_x_obs_seq_init(chains, tries) -> [n, T, X], which gets GLOBAL chain indices and try numbers and must be a pure
-    function of them (fhn_x_obs_seq_init).  A try then depends on (seed, chain, try) and nothing else: any sharding of
+    function of them (fhn_x_obs_seq_init).  Because it receives global chain numbers it may return per-chain data: in a
+    context with per-chain observations (ChmcContext.set_observations) chain c's x_obs_seq_init is built from chain c's own
+    y, and the projection works against that chain's constraint.  A try then depends on (seed, chain, try) and nothing else: any sharding of
     `total_chains` chains over contexts gives the same states bit for bit, within one backend.
     Per Adam iteration: chmc_gd_objective_device and chmc_adam_update_cols_device on device buffers and one [B, 3] read-back;
     x_obs_seq_init rows go up when a try starts; nothing of size [B, Q] crosses PCIe inside the loop.

@@ -79,10 +79,39 @@ def _mean_over_all_chains(local_sum, local_count):
     return float(local_sum) / float(local_count)
 
 
+def _group_sums_over_all_chains(values, groups, n_groups):
+    """(sums [G], counts [G]) of a per-chain statistic by group, over the chains of every rank: ONE all-reduce of a vector of
+    2 G numbers (distributed.sum_over_ranks), so that every rank adapts every group's step size on the same numbers."""
+    values = np.asarray(values, dtype=np.float64)
+    local = np.zeros(2 * n_groups)
+    for g in np.unique(groups):
+        sel = groups == g
+        local[g], local[n_groups + g] = values[sel].sum(), sel.sum()
+    try:
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            from . import distributed as D
+            local = np.asarray(D.sum_over_ranks(local), dtype=np.float64)
+    except ImportError:
+        pass
+    return local[:n_groups], local[n_groups:]
+
+
+def check_groups(groups, n_groups, num_chains):
+    """groups [B] (global group id of every chain of this rank) and the number of groups of the whole job."""
+    groups = np.asarray(groups)
+    if groups.shape != (num_chains,) or not np.issubdtype(groups.dtype, np.integer):
+        raise ValueError(f"groups must be an integer array of shape ({num_chains},), got {groups.dtype} {groups.shape}")
+    G = int(groups.max()) + 1 if n_groups is None else int(n_groups)
+    if groups.min() < 0 or groups.max() >= G:
+        raise ValueError(f"groups must lie in [0, {G})")
+    return groups.astype(np.int64), G
+
+
 def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_adapt=0, solver=None, rng=None,
                        n_head=6, callback=None, trace_dir=None, trace_func=None, total_chains=None,
                        jitter_length=False, metric_adapter=None, metric_window=0.75, metric_skip=0.25,
-                       path_posterior=None):
+                       path_posterior=None, groups=None, n_groups=None):
     """Runs n_iter transitions on all chains of `ctx`; returns traces of the first `n_head` position components
     ([n_iter, B, n_head]), accept statistics and the step size used.  Directions are sampled per chain and
     transition (forward / backward in time), failed trajectories are rejected.
@@ -103,12 +132,26 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     (per-chain statistics combined over all chains and ranks) is installed with `ctx.set_metric` there, and the
     remaining warm-up transitions re-tune the step size for the new metric.
     path_posterior: a `paths.PathPosterior` of `ctx`; the latent path of every post-warm-up state (after the partition
-    switch) is folded into its running moments, and out["path_posterior"] is its `pooled()` result."""
+    switch) is folded into its running moments, and out["path_posterior"] is its `pooled()` result.
+    groups [B], n_groups: chains that sample different posteriors in one context (per-chain observations,
+    ChmcContext.set_observations): groups[c] is the GLOBAL id of the data set chain c belongs to, n_groups their number over
+    the whole job (default: max + 1 of this rank's).  Every group then has its own dual-averaging state, driven by the mean
+    accept statistic of ITS chains over all ranks (one all-reduce of 2 G numbers per transition), and its own step size:
+    out["step_size"] is [n_iter, G], out["group_accept_stat"] likewise, out["final_step_size"] [G].  One group gives the
+    numbers of the call without `groups`.  The block metric is one M_0 per context: `metric_adapter` with more than one group
+    raises ValueError."""
+    if groups is not None:
+        groups, G = check_groups(groups, n_groups, ctx.B)
+        if metric_adapter is not None and G > 1:
+            raise ValueError("the block metric is one M_0 per context: no metric_adapter with more than one group")
     solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
                   reverse_check_tol=2e-8) if solver is None else solver
     rng = np.random.default_rng(seed) if rng is None else rng
     adapter = DualAveragingStepSize(step_size) if n_adapt > 0 else None
     B = ctx.B
+    if groups is not None:  # one adapter state and one step size per group
+        adapter = [DualAveragingStepSize(step_size) for _ in range(G)] if n_adapt > 0 else None
+        step_size = np.full(G, float(step_size))
 
     def draw():  # uniforms of this rank's chains
         if total_chains is None:
@@ -128,6 +171,8 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     outcome = np.zeros((B, 5), dtype=np.int64)
     heads = np.empty((n_iter, B, n_head))
     acc_hist, eps_hist, fail_hist = np.empty(n_iter), np.empty(n_iter), np.empty(n_iter)
+    if groups is not None:
+        eps_hist, group_acc_hist = np.empty((n_iter, G)), np.empty((n_iter, G))
     if trace_func is None:
         def trace_func(head, ham):
             return {"pos_head": head, "hamiltonian": ham}
@@ -143,7 +188,8 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
         # warm-up only: a chain whose trajectories keep failing (a start far from the typical set, where the shared
         # step size is too long for the retraction) backs its own step size off until it moves again
         scale = 0.5 ** np.minimum(stuck, 8) if it < n_adapt else 1.0
-        dt = np.where(draw() < 0.5, step_size, -step_size) * scale
+        eps = step_size if groups is None else step_size[groups]  # (per chain)
+        dt = np.where(draw() < 0.5, eps, -eps) * scale
         act = np.ones(B, dtype=np.int32)
         # the trajectory as ONE library call (the loop an integration transition runs around integrator.step,
         # scripts/utils.py:284-301: a chain stops at its first failed step): single-block layouts walk it in one launch per
@@ -177,17 +223,31 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
             if it == n_metric - 1:
                 metric = metric_adapter.finalize(metric_state)
                 ctx.set_metric(metric.blocks[0].array)
-                adapter = DualAveragingStepSize(step_size)  # the step size is re-tuned under the new metric
-        acc_all = _mean_over_all_chains(prob.sum(), B)
+                # the step size is re-tuned under the new metric
+                adapter = DualAveragingStepSize(step_size) if groups is None else [DualAveragingStepSize(float(step_size[0]))]
+        if groups is None:
+            acc_all = _mean_over_all_chains(prob.sum(), B)
+        else:
+            sums, counts = _group_sums_over_all_chains(prob, groups, G)
+            acc_all = float(sums.sum()) / float(counts.sum())
+            acc_group = sums / np.maximum(counts, 1.0)
+            group_acc_hist[it] = acc_group
         acc_hist[it], eps_hist[it], fail_hist[it] = acc_all, step_size, 1.0 - act.mean()
         if adapter is not None and it < n_adapt:
-            step_size = adapter.update(acc_all)
-            if it == n_adapt - 1:
-                step_size = adapter.final()
+            if groups is None:
+                step_size = adapter.update(acc_all)
+                if it == n_adapt - 1:
+                    step_size = adapter.final()
+            else:
+                step_size = np.array([a.update(acc_group[g]) for g, a in enumerate(adapter)])
+                if it == n_adapt - 1:
+                    step_size = np.array([a.final() for a in adapter])
         if callback is not None:
             callback(it, heads[it], prob.mean(), step_size)
     out = dict(heads=heads, accept_stat=acc_hist, step_size=eps_hist, fail_rate=fail_hist, final_step_size=step_size,
                chain_outcomes=outcome)
+    if groups is not None:
+        out["group_accept_stat"] = group_acc_hist
     if path_posterior is not None:
         out["path_posterior"] = path_posterior.pooled()
     if n_metric:
@@ -199,6 +259,6 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
         c_end = ctx.counters()
         main = {k: np.asarray(v)[:, n_adapt:] for k, v in writer.arrays().items()}  # summary over the post-warm-up draws
         out["summary"] = save_summary(trace_dir, main, None, time.perf_counter() - t_start, step_size,
-                                      {k: c_end[k] - c_start[k] for k in c_end if k != "_"})
+                                      {k: c_end[k] - c_start[k] for k in c_end if k != "_"}, groups=groups)
         out["trace_files"] = {k: os.path.join(trace_dir, f"trace_{k}.npy") for k in writer.arrays()}
     return out

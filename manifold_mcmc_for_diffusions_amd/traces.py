@@ -69,8 +69,14 @@ def split_rhat_and_ess(x):
     return rhat, float(min(ess, m * n * np.log10(max(m * n, 10))))
 
 
-def summarize(traces, var_names=None):
-    """{name or name[i]: {mean, sd, r_hat, ess_bulk}} over [chain, draw, ...] arrays (ArviZ's summary columns)."""
+def summarize(traces, var_names=None, groups=None):
+    """{name or name[i]: {mean, sd, r_hat, ess_bulk}} over [chain, draw, ...] arrays (ArviZ's summary columns).
+    groups [chain]: chains that sampled different posteriors (per-chain observations); returns {group id: that table over
+    the group's chains} instead -- a statistic across groups would mix posteriors."""
+    if groups is not None:
+        groups = np.asarray(groups)
+        return {int(g): summarize({k: np.asarray(traces[k])[groups == g] for k in (var_names or list(traces))}, var_names)
+                for g in np.unique(groups)}
     out = {"mean": {}, "sd": {}, "r_hat": {}, "ess_bulk": {}}
     for k in (var_names or list(traces)):
         a = np.asarray(traces[k])
@@ -84,11 +90,15 @@ def summarize(traces, var_names=None):
     return out
 
 
-def save_summary(directory, traces, var_names, sampling_time, step_size, call_counts=None):
-    """summary.json as scripts/utils.py:368-381 writes it."""
-    s = summarize(traces, var_names)
+def save_summary(directory, traces, var_names, sampling_time, step_size, call_counts=None, groups=None):
+    """summary.json as scripts/utils.py:368-381 writes it.  groups [chain]: one table per group under "groups" (keys: the
+    group ids), the run totals beside them; step_size may then be one number per group."""
+    if groups is None:
+        s = summarize(traces, var_names)
+    else:
+        s = {"groups": {str(g): t for g, t in summarize(traces, var_names, groups).items()}}
     s["total_sampling_time"] = float(sampling_time)
-    s["final_integrator_step_size"] = float(step_size)
+    s["final_integrator_step_size"] = float(step_size) if groups is None else [float(v) for v in np.atleast_1d(step_size)]
     for k, v in (call_counts or {}).items():
         s[f"total_{k}_calls"] = int(v)
     with open(os.path.join(directory, "summary.json"), "w") as f:

@@ -116,3 +116,72 @@ class SirWorkload(FhnWorkload):
         self.solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
                            reverse_check_tol=2e-8)
         self._torch_gen = None
+
+
+class GridWorkload:
+    """G data sets x n chains each of ONE shape (model, T, S, R) in one context: the cells of a sweep over noise levels and
+    data seeds, a replication study or a calibration check, which on their own (the reference runs 4 chains per cell) leave
+    the GPU nearly empty.  Chain c of the whole job belongs to cell c // n; a rank holds the contiguous shard
+    [chain_offset, chain_offset + num_chains) of the G n chains -- shards may cut through a cell -- with each chain's own
+    (y, sigma) installed by ChmcContext.set_observations.
+
+    cells: a list of (y_seq [T] or [T, 1], sigma) pairs; sigma a number for every cell (fixed noise), or None / "variable"
+    for every cell.  `groups` [B] is the global cell id of this rank's chains (the `groups` argument of the samplers and of
+    traces.summarize), `total_chains` = G n, `n_groups` = G.  init: "linear_interpolation" (FitzHugh-Nagumo: the scripts'
+    initial states, every chain from its own cell's data, keyed by the global chain number: any sharding gives the same
+    states), or None (the caller sets or finds the states)."""
+
+    def __init__(self, cells, chains_per_cell, model="fhn", num_steps_per_obs=400, num_obs_per_subseq=5, obs_interval=0.2,
+                 device=0, chain_offset=0, num_chains=None, use_gaussian_splitting=False, seed=SEED,
+                 init="linear_interpolation"):
+        if not cells:
+            raise ValueError("cells must hold at least one (y_seq, sigma) pair")
+        ys = [np.asarray(y, dtype=np.float64).reshape(-1) for y, _ in cells]
+        sigmas = [s for _, s in cells]
+        if len({len(y) for y in ys}) != 1:
+            raise ValueError("every cell must have the same number of observations")
+        kinds = {"variable" if isinstance(s, str) else "none" if s is None else "fixed" for s in sigmas}
+        if len(kinds) != 1:
+            raise ValueError("sigma must be a number for every cell, or None / \"variable\" for every cell")
+        fixed = kinds == {"fixed"}
+        self.n_groups, self.chains_per_cell = len(cells), int(chains_per_cell)
+        self.total_chains = self.n_groups * self.chains_per_cell
+        self.chain_offset = int(chain_offset)
+        self.B = self.total_chains - self.chain_offset if num_chains is None else int(num_chains)
+        if self.chains_per_cell < 1 or self.chain_offset < 0 or self.B < 1 or self.chain_offset + self.B > self.total_chains:
+            raise ValueError(f"the shard [{self.chain_offset}, {self.chain_offset + self.B}) does not lie in the "
+                             f"{self.total_chains} chains of {self.n_groups} cells x {self.chains_per_cell}")
+        self.groups = (np.arange(self.chain_offset, self.chain_offset + self.B) // self.chains_per_cell).astype(np.int64)
+        self.cell_y, self.cell_sigma = np.stack(ys), sigmas
+        self.y = self.cell_y[self.groups]                                              # [B, T]
+        self.sigma = np.asarray(sigmas, dtype=np.float64)[self.groups] if fixed else sigmas[0]
+        self.model, self.S, self.T, self.R = model, num_steps_per_obs, self.y.shape[1], num_obs_per_subseq
+        self.obs_interval, self.seed = obs_interval, seed
+        self.ctx = ChmcContext(model, obs_interval, num_steps_per_obs, num_obs_per_subseq, self.y, sigma=self.sigma,
+                               use_gaussian_splitting=use_gaussian_splitting, num_chains=self.B, device=device)
+        if init not in (None, "linear_interpolation"):
+            raise ValueError("init must be None or 'linear_interpolation'")
+        if init == "linear_interpolation":
+            if model != "fhn":
+                raise ValueError("linear-interpolation initial states are the FitzHugh-Nagumo scripts'")
+            self.rngs = fhn_initial_states_device(self.ctx, em.fhn, self.y[:, :, None], seed=seed, chain_offset=self.chain_offset,
+                                                  total_chains=self.total_chains)
+        self.solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
+                           reverse_check_tol=2e-8)  # scripts/utils.py:131-166
+
+    @classmethod
+    def fhn_noise_grid(cls, sigmas, data_seeds, chains_per_cell, num_obs=100, obs_interval=0.2, num_steps_per_obs_data=10000,
+                       **kw):
+        """The cells of scripts/run_fhn_model_noisy_obs_experiments.sh: every noise level x every data seed, each cell's
+        data simulated the way the experiment script does for that (sigma, seed) (example_models.simulate_fhn_observations).
+        Cell order: sigma-major, `cell_labels` holds (sigma, seed) per cell."""
+        labels = [(float(s), int(d)) for s in sigmas for d in data_seeds]
+        cells = [(em.simulate_fhn_observations(num_obs, obs_interval, num_steps_per_obs_data, seed=d, sigma=s)[:, 0], s)
+                 for s, d in labels]
+        w = cls(cells, chains_per_cell, model="fhn", obs_interval=obs_interval, **kw)
+        w.cell_labels = labels
+        return w
+
+    def cell_chains(self, g):
+        """Local indices of this rank's chains that belong to cell g."""
+        return np.flatnonzero(self.groups == g)
