@@ -4,7 +4,11 @@
 noise level of its own grid cell (ChmcContext.set_observations through workload.GridWorkload), every cell adapts its own step
 size, and one summary.json per cell is written.
 
-usage: fhn_noise_grid_chmc.py [seeds] [S] [iters] [warm-up] [output dir] [chains per cell] [T] [data steps per obs]
+usage: fhn_noise_grid_chmc.py [seeds] [S] [iters] [warm-up] [output dir] [chains per cell] [T] [data steps per obs] [metric]
+
+With the trailing word `metric` every cell also adapts its own block metric M_0 over the dim_u global parameters during the
+warm-up (OnlineBlockDiagonalMetricAdapter.finalize_groups, ChmcContext.set_metric(M, groups=...)): the posterior scale of u
+differs widely between sigma_y = 0.01 and 0.316.  The adapted diagonal of every cell is printed.
 
 Prints leapfrog steps/s of the batch and, measured in the same process on the same build, of ONE cell run alone (4 chains: how
 a sweep runs without per-chain observations, one cell after the other), and their ratio."""
@@ -17,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 from manifold_mcmc_for_diffusions_amd.workload import GridWorkload  # noqa: E402
 from manifold_mcmc_for_diffusions_amd.sampling import sample_static_chmc  # noqa: E402
+from manifold_mcmc_for_diffusions_amd.adapters import OnlineBlockDiagonalMetricAdapter  # noqa: E402
 from manifold_mcmc_for_diffusions_amd import example_models as em  # noqa: E402
 
 SIGMAS = (0.01, 0.0316, 0.1, 0.316)
@@ -28,6 +33,7 @@ out_dir = sys.argv[5] if len(sys.argv) > 5 and sys.argv[5] != "-" else None
 n_chain = int(sys.argv[6]) if len(sys.argv) > 6 else 4
 T = int(sys.argv[7]) if len(sys.argv) > 7 else 100
 data_steps = int(sys.argv[8]) if len(sys.argv) > 8 else 1000
+with_metric = len(sys.argv) > 9 and sys.argv[9] == "metric"
 N_STEP = 16
 seeds = [20200710 + i for i in range(n_seed)]
 
@@ -40,8 +46,9 @@ def trace_func(head, ham):  # scripts/fhn_model_noisy_obs_chmc_experiment.py:82-
 
 def run(w, trace_dir):
     t0 = time.time()
+    extra = dict(metric_adapter=OnlineBlockDiagonalMetricAdapter(w.ctx.U), metric_per_group=True) if with_metric else {}
     res = sample_static_chmc(w.ctx, n_iter, N_STEP, 0.05, seed=w.seed, n_adapt=n_warm, trace_dir=trace_dir, trace_func=trace_func,
-                             groups=w.groups, n_groups=w.n_groups, total_chains=w.total_chains)
+                             groups=w.groups, n_groups=w.n_groups, total_chains=w.total_chains, **extra)
     el = time.time() - t0
     return res, n_iter * N_STEP * w.B / el, el
 
@@ -58,6 +65,8 @@ for g, (sigma, seed) in enumerate(grid.cell_labels):
     print(f"  sigma_y {sigma:<7g} data seed {seed}: step size {res['final_step_size'][g]:.4f}  accept "
           f"{res['group_accept_stat'][n_warm:, g].mean():.2f}  posterior means (sigma, eps, gamma, beta) "
           f"{z.reshape(-1, 4).mean(0).round(3)}")
+    if with_metric:
+        print(f"    adapted M_0 diagonal {np.diag(res['metric_M_0'][g]).round(2)}")
     if out_dir:
         cell_dir = os.path.join(out_dir, f"sigma_{sigma:g}_seed_{seed}")
         os.makedirs(cell_dir, exist_ok=True)

@@ -120,6 +120,18 @@ int chmc_init_linear_interpolation(chmc_ctx* ctx, const double* u, const double*
  * is (project it again if it has to be tangent with respect to the new metric).  Errors: Gaussian splitting (the
  * reference raises ValueError :293-300), M_0 not symmetric positive definite. */
 int chmc_set_metric(chmc_ctx* ctx, const double* M_0);
+/* One M_0 per chain: M_0 [B][U][U], chain c's metric is blockdiag(M_0[c], identity) -- many posteriors in one context
+ * (chmc_set_observations) whose global parameters u have different scales, each with the metric the reference's
+ * OnlineBlockDiagonalMetricAdapter (scripts/utils.py, sde/mici_extensions.py:279-315) would give a system of its own.  The
+ * interface knows nothing of groups: a caller with one matrix per group passes M[groups].  Every matrix is validated as
+ * chmc_set_metric validates its one (symmetric positive definite, dim_u <= 8, no Gaussian splitting :293-300); the error
+ * names the first offending chain and the context keeps the metric it had.  Like chmc_set_metric the call refreshes the
+ * cached factors of the current state and keeps the momentum.  A chain's results are bitwise those of a context that holds
+ * its matrix as the shared metric.  A later chmc_set_metric(ctx, M_0) returns every chain to one shared matrix, and
+ * chmc_set_metric(ctx, NULL) to the identity.
+ * chmc_get_metric writes the matrix each chain uses, M_0 [B][U][U]: the shared one once per chain, or the identity. */
+int chmc_set_metrics(chmc_ctx* ctx, const double* M_0);
+int chmc_get_metric(chmc_ctx* ctx, double* M_0);
 /* One leaf of a batched dynamic-integration (no-U-turn) tree (the caller of integrator.step in the reference:
  * mici.transitions.MultinomialDynamicIntegrationTransition, scripts/utils.py:292-301), fused into one pass over the state
  * the last chmc_leapfrog_step produced.  The tree vectors stay with the caller as device buffers (plain pointers:

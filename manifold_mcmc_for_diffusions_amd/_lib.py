@@ -41,6 +41,8 @@ SYMBOLS = [
     ("chmc_simulate_observations_device", C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]),
     ("chmc_init_linear_interpolation", C.c_int, [C.c_void_p, dp, dp, dp, C.c_int]),
     ("chmc_set_metric", C.c_int, [C.c_void_p, dp]),
+    ("chmc_set_metrics", C.c_int, [C.c_void_p, dp]),
+    ("chmc_get_metric", C.c_int, [C.c_void_p, dp]),
     ("chmc_tree_leaf", C.c_int, [C.c_void_p, ip, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_int, C.c_int, dp]),
     ("chmc_tree_begin", C.c_int, [C.c_void_p, dp]),

@@ -78,3 +78,34 @@ class OnlineBlockDiagonalMetricAdapter:
         if system is not None:
             system.metric = metric
         return metric
+
+    def finalize_groups(self, adapt_state, groups, n_groups):
+        """One M_0 per group of chains (per-chain observations: every group samples its own posterior): [G, U, U], each the
+        matrix `finalize` gives the per-chain statistics of that group's chains alone, combined in global chain order.
+        groups [B] holds the GLOBAL group id of this rank's chains, n_groups their number over the whole job.  Under
+        torch.distributed ONE all_gather_object of (groups, iters, means, sums): a group cut by a rank boundary gives every
+        rank the same matrix."""
+        groups = np.asarray(groups)
+        iters, means, sums = adapt_state["iter"], adapt_state["mean"], adapt_state["sum_diff_outer"]
+        try:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                parts = [None] * dist.get_world_size()
+                dist.all_gather_object(parts, (groups, iters, means, sums))  # rank order = global chain order
+                groups = np.concatenate([p[0] for p in parts])
+                iters = np.concatenate([p[1] for p in parts])
+                means = np.concatenate([p[2] for p in parts])
+                sums = np.concatenate([p[3] for p in parts])
+        except ImportError:
+            pass
+        out = np.empty((int(n_groups), self.dim_param, self.dim_param))
+        for g in range(int(n_groups)):
+            sel = np.flatnonzero(groups == g)
+            n_iter, _, covar_est = self.combine(iters[sel], means[sel], sums[sel])
+            if n_iter < 2:
+                raise AdaptationError(f"At least two chain samples required to compute a variance estimates: group {g} has "
+                                      f"{n_iter}.")
+            covar_est = covar_est / (n_iter - 1)
+            self._regularize_covar_est(covar_est, n_iter)
+            out[g] = DensePositiveDefiniteMatrix(covar_est).inv.array
+        return out

@@ -51,6 +51,7 @@ class ChmcContext:
         check(L.chmc_get_dims(h, iptr(d)), "chmc_get_dims")
         (self.B, self.Q, self.NV, self.U, self.X, self.T, self.S, self.num_partition, self.RM, self.Kmax) = map(int, d[:10])
         self.M_0 = None  # block metric (set_metric); None = identity
+        self.per_chain_metric = False  # set_metric with [B, U, U] or groups: M_0 is [B, U, U]
         self.C = [int(d[10]), int(d[11])][: self.num_partition]
         self.K = [int(d[12]), int(d[13])][: self.num_partition]
         self.V, self.V0 = int(d[14]), int(d[15])
@@ -150,18 +151,42 @@ class ChmcContext:
         check(self.L.chmc_get_state(self.h, ptr(q), ptr(p), ptr(xo), C.byref(part)), "chmc_get_state")
         return q, p, xo, part.value
 
-    def set_metric(self, M_0):
+    def set_metric(self, M_0, groups=None):
         """metric = blockdiag(M_0 [U, U] dense positive definite, identity) (sde/mici_extensions.py:279-315); None = identity.
+        M_0 [B, U, U] gives every chain a matrix of its own, M_0 [G, U, U] with `groups` [B] (group index per chain) gives
+        chain c the matrix M_0[groups[c]] (chmc_set_metrics, include/chmc.h); self.M_0 is then the [B, U, U] array.
         The cached factors of the current state are refreshed; the momentum is left as it is."""
         if M_0 is None:
+            if groups is not None:
+                raise ValueError("groups needs M_0 of shape (G, U, U)")
             check(self.L.chmc_set_metric(self.h, None), "chmc_set_metric")
             self.M_0 = None
+            self.per_chain_metric = False
             return
         m = np.ascontiguousarray(M_0, dtype=np.float64)
+        if groups is not None:
+            g = np.asarray(groups)
+            if m.ndim != 3 or m.shape[1:] != (self.U, self.U):
+                raise ValueError(f"with groups, M_0 must have shape (G, {self.U}, {self.U}), got {m.shape}")
+            if g.shape != (self.B,) or not np.issubdtype(g.dtype, np.integer) or g.min() < 0 or g.max() >= m.shape[0]:
+                raise ValueError(f"groups must be {self.B} integers in [0, {m.shape[0]})")
+            m = np.ascontiguousarray(m[g])
+        if m.shape == (self.B, self.U, self.U):
+            check(self.L.chmc_set_metrics(self.h, ptr(m)), "chmc_set_metrics")
+            self.M_0 = m.copy()
+            self.per_chain_metric = True
+            return
         if m.shape != (self.U, self.U):
-            raise ValueError(f"M_0 must have shape ({self.U}, {self.U})")
+            raise ValueError(f"M_0 must have shape ({self.U}, {self.U}) or ({self.B}, {self.U}, {self.U})")
         check(self.L.chmc_set_metric(self.h, ptr(m)), "chmc_set_metric")
         self.M_0 = m.copy()
+        self.per_chain_metric = False
+
+    def metrics(self):
+        """M_0 [B, U, U] as the kernels use it: the shared matrix once per chain, or the identity (chmc_get_metric)."""
+        m = np.empty((self.B, self.U, self.U))
+        check(self.L.chmc_get_metric(self.h, ptr(m)), "chmc_get_metric")
+        return m
 
     def tree_leaf(self, run, take, sub_prop_q_ptr, sub_sum_ptr, ck_p_ptr, ck_sum_ptr, store_slot, check_lo, n_check,
                   ck_end_ptr=None):

@@ -46,7 +46,7 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   bool mom_tangent = false;  // every chain's momentum is known to lie in the cotangent space of its current point
   bool snap_tangent = false; // ... at the time of chmc_snapshot
   bool have_state = false;   // a chain state has been set (chmc_set_metric then refreshes its cached factors)
-  double* d_m0 = nullptr;    // [3][U][U] M_0, M_0^-1, chol(M_0) of the block metric
+  double* d_m0 = nullptr;    // [3 U U + 1] M_0, M_0^-1, chol(M_0), log det(M_0) / 2 of the block metric every chain shares
   double *d_tree_part = nullptr, *d_tree_out = nullptr;  // chmc_tree_leaf: workgroup partials, per-chain results
   int* d_tree_mask = nullptr;                            // [2][B] run, take
   int* d_path_ints = nullptr;       // chmc_generate_x_seq* / chmc_path_stats_update_device: [2][B] sweeps, mask
@@ -180,6 +180,7 @@ static void set_half(chmc_ctx* c, const ViewSave& f, int h) {
   v.sy.xobs = v.d_xobs;
   if (v.d_yc) v.sy.y = v.d_yc;  // (shared data: stride 0, every view reads d_y)
   v.sy.sigc = v.d_sigc;
+  if (v.sy.m0stride) v.sy.m0 = v.d_m0c;  // (shared metric: stride 0, every view reads d_m0)
   v.sy.order = c->d_order_half[c->part][h];
   v.w.n_active = f.w.n_active + 4 * (1 + h);
   use_stream(h);
@@ -935,60 +936,110 @@ extern "C" int chmc_set_momentum_device(chmc_ctx* ctx, const void* p_dev) {
 }
 
 // metric = blockdiag(M_0, identity) (sde/mici_extensions.py:303-315); see include/chmc.h
+// One chain's table h [3 U U + 1] = M_0, M_0^-1, lower Cholesky factor, log det(M_0) / 2 from M0 [U][U]; null, or what is
+// wrong with the matrix.
+static const char* metric_table(const double* M0, int U, double* h) {
+  double* Mh = h;
+  double* W = Mh + U * U;
+  double* L = W + U * U;
+  for (int i = 0; i < U * U; ++i) Mh[i] = M0[i], L[i] = 0.0;
+  for (int i = 0; i < U; ++i)
+    for (int j = 0; j < i; ++j)
+      if (!(std::fabs(M0[i * U + j] - M0[j * U + i]) <= 1e-12 * (std::fabs(M0[i * U + i]) + std::fabs(M0[j * U + j]))))
+        return "is not symmetric";
+  double hld = 0.0;
+  for (int j = 0; j < U; ++j) {  // lower Cholesky factor
+    double d = M0[j * U + j];
+    for (int k = 0; k < j; ++k) d -= L[j * U + k] * L[j * U + k];
+    if (!(d > 0.0)) return "is not positive definite";
+    L[j * U + j] = std::sqrt(d);
+    hld += std::log(L[j * U + j]);
+    for (int i = j + 1; i < U; ++i) {
+      double t = M0[i * U + j];
+      for (int k = 0; k < j; ++k) t -= L[i * U + k] * L[j * U + k];
+      L[i * U + j] = t / L[j * U + j];
+    }
+  }
+  for (int c = 0; c < U; ++c) {  // M_0^-1, column by column
+    double y[8];
+    for (int i = 0; i < U; ++i) {
+      double t = (i == c) ? 1.0 : 0.0;
+      for (int k = 0; k < i; ++k) t -= L[i * U + k] * y[k];
+      y[i] = t / L[i * U + i];
+    }
+    for (int i = U - 1; i >= 0; --i) {
+      double t = y[i];
+      for (int k = i + 1; k < U; ++k) t -= L[k * U + i] * W[k * U + c];
+      W[i * U + c] = t / L[i * U + i];
+    }
+  }
+  h[3 * U * U] = hld;
+  return nullptr;
+}
+// the metric changed: tangency is with respect to it, and the factors, log-determinant, gradient and kick direction of the
+// current state depend on M_0
+static void metric_changed(chmc_ctx* ctx) {
+  ctx->mom_tangent = false;
+  if (ctx->have_state) {
+    begin_all(ctx, nullptr, nullptr);
+    state_eval(ctx, 0);
+  }
+}
 extern "C" int chmc_set_metric(chmc_ctx* ctx, const double* M0) {
   CHMC_ENTER("chmc_set_metric")
   Sys& sy = ctx->sy;
   const int U = sy.U;
   if (!M0) {
-    sy.m0 = nullptr, sy.hld_m0 = 0.0;
+    sy.m0 = nullptr, sy.m0stride = 0;
   } else {
     if (sy.gaussian) return fail("chmc_set_metric: only the identity metric can be used with Gaussian splitting");
     if (U > 8) return fail("chmc_set_metric: dim_u must be at most 8");
-    std::vector<double> h(3 * (size_t)U * U);
-    double* Mh = h.data();
-    double* W = Mh + U * U;
-    double* L = W + U * U;
-    for (int i = 0; i < U * U; ++i) Mh[i] = M0[i], L[i] = 0.0;
-    for (int i = 0; i < U; ++i)
-      for (int j = 0; j < i; ++j)
-        if (!(std::fabs(M0[i * U + j] - M0[j * U + i]) <= 1e-12 * (std::fabs(M0[i * U + i]) + std::fabs(M0[j * U + j]))))
-          return fail("chmc_set_metric: M_0 is not symmetric");
-    double hld = 0.0;
-    for (int j = 0; j < U; ++j) {  // lower Cholesky factor
-      double d = M0[j * U + j];
-      for (int k = 0; k < j; ++k) d -= L[j * U + k] * L[j * U + k];
-      if (!(d > 0.0)) return fail("chmc_set_metric: M_0 is not positive definite");
-      L[j * U + j] = std::sqrt(d);
-      hld += std::log(L[j * U + j]);
-      for (int i = j + 1; i < U; ++i) {
-        double t = M0[i * U + j];
-        for (int k = 0; k < j; ++k) t -= L[i * U + k] * L[j * U + k];
-        L[i * U + j] = t / L[j * U + j];
-      }
-    }
-    for (int c = 0; c < U; ++c) {  // M_0^-1, column by column
-      double y[8];
-      for (int i = 0; i < U; ++i) {
-        double t = (i == c) ? 1.0 : 0.0;
-        for (int k = 0; k < i; ++k) t -= L[i * U + k] * y[k];
-        y[i] = t / L[i * U + i];
-      }
-      for (int i = U - 1; i >= 0; --i) {
-        double t = y[i];
-        for (int k = i + 1; k < U; ++k) t -= L[k * U + i] * W[k * U + c];
-        W[i * U + c] = t / L[i * U + i];
-      }
-    }
-    if (!ctx->d_m0) ctx->d_m0 = alloc<double>(ctx, 3 * (size_t)U * U);
+    std::vector<double> h(3 * (size_t)U * U + 1);
+    if (const char* what = metric_table(M0, U, h.data())) return fail(std::string("chmc_set_metric: M_0 ") + what);
+    if (!ctx->d_m0) ctx->d_m0 = alloc<double>(ctx, h.size());
     h2d(ctx->d_m0, h.data(), sizeof(double) * h.size());
-    sy.m0 = ctx->d_m0, sy.hld_m0 = hld;
+    sy.m0 = ctx->d_m0, sy.m0stride = 0;  // (every chain reads the one table, also after chmc_set_metrics)
   }
-  ctx->mom_tangent = false;  // tangency is with respect to the metric
-  if (ctx->have_state) {     // factors, log-determinant, gradient and kick direction of the current state depend on M_0
-    begin_all(ctx, nullptr, nullptr);
-    state_eval(ctx, 0);
-  }
+  metric_changed(ctx);
   CHMC_LEAVE("chmc_set_metric")
+}
+// Per-chain block metrics: d_m0c [B][3 U U + 1] is an entry of the per-chain list (chmc_layout.h) that no context has until
+// this call; afterwards Sys::m0 strides by the table size and metric_of reads the chain's own table.
+extern "C" int chmc_set_metrics(chmc_ctx* ctx, const double* M0) {
+  CHMC_ENTER("chmc_set_metrics")
+  if (!M0) return fail("chmc_set_metrics: M0 is null");
+  Sys& sy = ctx->sy;
+  const int U = sy.U;
+  if (sy.gaussian) return fail("chmc_set_metrics: only the identity metric can be used with Gaussian splitting");
+  if (U > 8) return fail("chmc_set_metrics: dim_u must be at most 8");
+  const size_t n = 3 * (size_t)U * U + 1;
+  std::vector<double> h((size_t)sy.B * n);
+  for (int c = 0; c < sy.B; ++c)
+    if (const char* what = metric_table(M0 + (size_t)c * U * U, U, h.data() + c * n))
+      return fail("chmc_set_metrics: M_0 of chain " + std::to_string(c) + " " + what);
+  ensure_array(ctx, ctx->d_m0c);
+  h2d(ctx->d_m0c, h.data(), sizeof(double) * h.size());
+  sy.m0 = ctx->d_m0c, sy.m0stride = (int)n;
+  metric_changed(ctx);
+  CHMC_LEAVE("chmc_set_metrics")
+}
+extern "C" int chmc_get_metric(chmc_ctx* ctx, double* M0) {
+  CHMC_ENTER("chmc_get_metric")
+  if (!M0) return fail("chmc_get_metric: null output");
+  const Sys& sy = ctx->sy;
+  const size_t B = sy.B, UU = (size_t)sy.U * sy.U, n = 3 * UU + 1;
+  if (!sy.m0) {  // the identity
+    for (size_t c = 0; c < B; ++c)
+      for (size_t i = 0; i < UU; ++i) M0[c * UU + i] = (i / sy.U == i % sy.U) ? 1.0 : 0.0;
+  } else if (sy.m0stride) {
+    std::vector<double> h(B * n);
+    d2h(h.data(), ctx->d_m0c, sizeof(double) * h.size());
+    for (size_t c = 0; c < B; ++c) memcpy(M0 + c * UU, h.data() + c * n, sizeof(double) * UU);
+  } else {  // the shared matrix, once per chain
+    d2h(M0, ctx->d_m0, sizeof(double) * UU);
+    for (size_t c = 1; c < B; ++c) memcpy(M0 + c * UU, M0, sizeof(double) * UU);
+  }
+  CHMC_LEAVE("chmc_get_metric")
 }
 
 extern "C" int chmc_sample_momentum(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw,
@@ -1618,7 +1669,7 @@ struct KMuFromMove {  // mu / dt, or mu / sin(dt) with Gaussian splitting (:1060
     if (sy.m0 && col < sy.U) {  // the multiplier term is metric @ (position move) (:1033-1041, :1105-1113)
       d = 0.0;
       for (int b = 0; b < sy.U; ++b)
-        d += sy.m0[col * sy.U + b] * (q_in[(size_t)c * sy.Q + b] - sl.q[sl.cur[c] ^ 1][(size_t)c * sy.Q + b]);
+        d += metric_of(sy, c)[col * sy.U + b] * (q_in[(size_t)c * sy.Q + b] - sl.q[sl.cur[c] ^ 1][(size_t)c * sy.Q + b]);
     }
     w.mu[tid] = d / (sy.gaussian ? sin(dt) : dt);
   }

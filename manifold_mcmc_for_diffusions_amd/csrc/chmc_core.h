@@ -69,14 +69,19 @@ struct Sys {
   const BlockDesc* blk;
   const int* obs2blk;
   const int* order;  // [B * K] work item -> chain * K + block of the wave-per-block kernels (longest blocks first)
-  // metric M = diag(M_0, I) (:303-315): [3][U][U] = M_0, M_0^-1, lower Cholesky factor of M_0; nullptr = identity
+  // metric M = diag(M_0, I) (:303-315): [3 U U + 1] = M_0, M_0^-1, lower Cholesky factor of M_0, then log det(M_0) / 2
+  // (log_det_sqrt_metric_0 :305-310); nullptr = identity.  One table every chain shares (m0stride 0), or [B][3 U U + 1], one
+  // table per chain (m0stride 3 U U + 1, chmc_set_metrics): metric_of
   const double* m0;
-  double hld_m0;  // log det(M_0) / 2 (log_det_sqrt_metric_0 :305-310)
+  int m0stride;
 };
-// (M_0^-1 v_u)[a] and (M_0 v_u)[a] for the u-part of a [Q] vector (the rest of the metric is the identity)
-CHMC_HD inline double metric_inv_u(const Sys& sy, const double* vu, int a) {
+// the metric table of chain c (sy.m0 != nullptr): one code path, the stride is 0 while every chain shares the context's table
+CHMC_HD inline const double* metric_of(const Sys& sy, int c) { return sy.m0 + (size_t)c * sy.m0stride; }
+CHMC_HD inline double metric_hld(const Sys& sy, int c) { return metric_of(sy, c)[3 * sy.U * sy.U]; }
+// (M_0^-1 v_u)[a] and (M_0 v_u)[a] of chain c for the u-part of a [Q] vector (the rest of the metric is the identity)
+CHMC_HD inline double metric_inv_u(const Sys& sy, int c, const double* vu, int a) {
   if (!sy.m0) return vu[a];
-  const double* W = sy.m0 + sy.U * sy.U + a * sy.U;
+  const double* W = metric_of(sy, c) + sy.U * sy.U + a * sy.U;
   double t = 0.0;
   for (int b = 0; b < sy.U; ++b) t += W[b] * vu[b];
   return t;
@@ -88,9 +93,9 @@ CHMC_HD inline double sigma_at(const Sys& sy, const double* q, int c) {
 }
 // the observation sequence of chain c: one code path, the stride is 0 while every chain shares the context's data
 CHMC_HD inline const double* y_of(const Sys& sy, int c) { return sy.y + (size_t)c * sy.ystride; }
-CHMC_HD inline double metric_mul_u(const Sys& sy, const double* vu, int a) {
+CHMC_HD inline double metric_mul_u(const Sys& sy, int c, const double* vu, int a) {
   if (!sy.m0) return vu[a];
-  const double* Mr = sy.m0 + a * sy.U;
+  const double* Mr = metric_of(sy, c) + a * sy.U;
   double t = 0.0;
   for (int b = 0; b < sy.U; ++b) t += Mr[b] * vu[b];
   return t;
@@ -916,8 +921,8 @@ struct KStateChain {
     for (int i = 0; i < U * U; ++i) Cm[i] = 0.0;
     for (int i = 0; i < U; ++i) Cm[i * U + i] = 1.0;
     if (sy.m0)  // get_M_0_matrix (:794-798)
-      for (int i = 0; i < U * U; ++i) Cm[i] = sy.m0[i];
-    double ld = sy.m0 ? -sy.hld_m0 : 0.0;  // - log_det_sqrt_metric_0 (:809)
+      for (int i = 0; i < U * U; ++i) Cm[i] = metric_of(sy, c)[i];
+    double ld = sy.m0 ? -metric_hld(sy, c) : 0.0;  // - log_det_sqrt_metric_0 (:809)
     for (int b = 0; b < sy.K; ++b) {
       const double* Cb = w.Cb + ((size_t)c * sy.Kmax + b) * U * U;
       for (int i = 0; i < U * U; ++i) Cm[i] += Cb[i];
@@ -1479,7 +1484,7 @@ struct KSolveChain {
       for (int i = 0; i < U * U; ++i) Cm[i] = 0.0;
       for (int i = 0; i < U; ++i) Cm[i * U + i] = 1.0;
       if (sy.m0)
-        for (int i = 0; i < U * U; ++i) Cm[i] = sy.m0[i];
+        for (int i = 0; i < U * U; ++i) Cm[i] = metric_of(sy, c)[i];
       for (int b = 0; b < sy.K; ++b)
         for (int i = 0; i < U * U; ++i) Cm[i] += w.Cb[((size_t)c * sy.Kmax + b) * U * U + i];
       lu_factor<U>(Cm, piv);
@@ -1507,7 +1512,7 @@ struct KSolveChain {
       double* q = (qsel ? w.qb : pick(sl.q, s ^ 1)) + (size_t)c * sy.Q;
       unsigned long long nb = 0ULL;
       for (int a = 0; a < U; ++a) {
-        const double dq = metric_inv_u(sy, du, a);  // delta_q = metric.inv @ delta_mu (:1033-1041, :1105-1113)
+        const double dq = metric_inv_u(sy, c, du, a);  // delta_q = metric.inv @ delta_mu (:1033-1041, :1105-1113)
         q[a] -= dq;
         unsigned long long vb = absbits(dq);
         if (vb > nb) nb = vb;
@@ -2260,7 +2265,7 @@ struct KJw {
     double acc = 0.0;
     if (i < bd.nrows) {
       const double* ju = pick(sl.JuP, s) + (cb * RM + i) * sy.U;
-      for (int a = 0; a < sy.U; ++a) acc += ju[a] * (minv ? metric_inv_u(sy, vct, a) : vct[a]);
+      for (int a = 0; a < sy.U; ++a) acc += ju[a] * (minv ? metric_inv_u(sy, c, vct, a) : vct[a]);
       const double* Jv = pick(sl.Jv, s) + ((size_t)c * RM + i) * sy.NV + bd.col0;
       const double* wv = vct + sy.U + bd.col0;
       double a2 = 0.0;
@@ -2349,8 +2354,8 @@ struct KFlow {
     }
     if (sy.m0 && col < sy.U) {  // pos += dt * metric.inv @ mom (:1208, :1231) on the u-part
       const double* pu = (from_p_other ? pick(sl.p, s ^ 1) : pick(sl.p, s)) + (size_t)c * sy.Q;
-      qn.x = q0.x + dt * metric_inv_u(sy, pu, col);
-      if (col + 1 < sy.U) qn.y = q0.y + dt * metric_inv_u(sy, pu, col + 1);
+      qn.x = q0.x + dt * metric_inv_u(sy, c, pu, col);
+      if (col + 1 < sy.U) qn.y = q0.y + dt * metric_inv_u(sy, c, pu, col + 1);
     }
     if (dst == 0) {
       stv2(pick(sl.q, s ^ 1) + i, qn, wide, two);
@@ -2405,8 +2410,8 @@ struct KMomFixInitPg {
       const double* qnu = pick(sl.q, s) + cq;
       double* pu = pick(sl.p, s) + cq;
       double mv[8], pnew[8];
-      for (int a = 0; a < sy.U; ++a) mv[a] = qpu[a] + w.dt[c] * metric_inv_u(sy, pu, a) - qnu[a];
-      for (int a = 0; a < sy.U; ++a) pnew[a] = pu[a] - sc * metric_mul_u(sy, mv, a);
+      for (int a = 0; a < sy.U; ++a) mv[a] = qpu[a] + w.dt[c] * metric_inv_u(sy, c, pu, a) - qnu[a];
+      for (int a = 0; a < sy.U; ++a) pnew[a] = pu[a] - sc * metric_mul_u(sy, c, mv, a);
       for (int a = 0; a < sy.U; ++a) {
         pu[a] = pnew[a];
         pick(sl.pg, s)[cq + a] = pick(sl.grad, s)[cq + a] + qnu[a];
@@ -2455,11 +2460,12 @@ struct KKickFlowPg {
     if (sy.m0 && col < sy.U) {  // u-part of the flow with the block metric: q_u += dt * M_0^-1 (p - h pg)_u
       const double* pu = pick(sl.p, s) + (size_t)c * sy.Q;
       const double* gu = pick(sl.pg, s) + (size_t)c * sy.Q;
+      const double* W = metric_of(sy, c) + sy.U * sy.U;
       double t0 = 0.0, t1 = 0.0;
       for (int b = 0; b < sy.U; ++b) {
         const double pb = pu[b] - h * gu[b];
-        t0 += sy.m0[sy.U * sy.U + col * sy.U + b] * pb;
-        if (col + 1 < sy.U) t1 += sy.m0[sy.U * sy.U + (col + 1) * sy.U + b] * pb;
+        t0 += W[col * sy.U + b] * pb;
+        if (col + 1 < sy.U) t1 += W[(col + 1) * sy.U + b] * pb;
       }
       qn.x = q0.x + w.dt[c] * t0;
       if (col + 1 < sy.U) qn.y = q0.y + w.dt[c] * t1;
@@ -2689,11 +2695,12 @@ struct KTreeLeaf {
   double* ck_end;      // [D][B][Q] momentum at the last leaf of the left half of the pending span of a slot (or null)
   int store, lo, nchk;  // store: checkpoint slot this leaf is recorded in (-1: none); checks against slots lo .. lo + nchk - 1
   CHMC_HD bool active(int c) const { return run[c] != 0; }
-  CHMC_HD double2_ vel(const double* base, size_t cq, int col, double2_ p) const {
+  CHMC_HD double2_ vel(const double* base, int c, int col, double2_ p) const {
+    const size_t cq = (size_t)c * sy.Q;
     // metric.inv @ p: only the u-part of the block metric differs from p
     if (sy.m0 && col < sy.U) {
-      p.x = metric_inv_u(sy, base + cq, col);
-      if (col + 1 < sy.U) p.y = metric_inv_u(sy, base + cq, col + 1);
+      p.x = metric_inv_u(sy, c, base + cq, col);
+      if (col + 1 < sy.U) p.y = metric_inv_u(sy, c, base + cq, col + 1);
     }
     return p;
   }
@@ -2710,7 +2717,7 @@ struct KTreeLeaf {
       stv2(ck_p + store * BQ + i, p, wide, two);
       stv2(ck_sum + store * BQ + i, S, wide, two);
     }
-    const double2_ vp = vel(pick(sl.p, s), cq, col, p);
+    const double2_ vp = vel(pick(sl.p, s), c, col, p);
     double2_ a_r, cs_r;  // checkpoint of the right half (the next smaller span), carried from slot to slot
     a_r.x = a_r.y = cs_r.x = cs_r.y = 0.0;
     // from the smallest span (slot lo + nchk - 1) to the largest (slot lo)
@@ -2720,7 +2727,7 @@ struct KTreeLeaf {
       if (k >= 0) {
         const double* cp = ck_p + (size_t)(lo + k) * BQ;
         const double2_ a = ldv2(cp + i, wide, two), cs = ldv2(ck_sum + (size_t)(lo + k) * BQ + i, wide, two);
-        const double2_ va = vel(cp, cq, col, a);
+        const double2_ va = vel(cp, c, col, a);
         const double sx = S.x - cs.x + a.x, sy_ = two ? S.y - cs.y + a.y : 0.0;
         acc[6 * k] += va.x * sx + (two ? va.y * sy_ : 0.0);
         acc[6 * k + 1] += vp.x * sx + (two ? vp.y * sy_ : 0.0);
@@ -2728,7 +2735,7 @@ struct KTreeLeaf {
           const double* ce = ck_end + (size_t)(lo + k) * BQ;
           const double* cr = ck_p + (size_t)(lo + k + 1) * BQ;
           const double2_ pm = ldv2(ce + i, wide, two);
-          const double2_ vm = vel(ce, cq, col, pm), vr = vel(cr, cq, col, a_r);
+          const double2_ vm = vel(ce, c, col, pm), vr = vel(cr, c, col, a_r);
           const double r1x = cs_r.x - cs.x + a.x, r1y = two ? cs_r.y - cs.y + a.y : 0.0;
           const double r2x = S.x - cs_r.x + a_r.x + pm.x, r2y = two ? S.y - cs_r.y + a_r.y + pm.y : 0.0;
           acc[6 * k + 2] += va.x * r1x + (two ? va.y * r1y : 0.0);
@@ -2865,10 +2872,11 @@ struct KTreeDoubleRows {
   double *prop_q, *sum_mom, *neg_q, *neg_p, *pos_q, *pos_p;
   const double *sub_prop_q, *sub_sum;
   CHMC_HD bool active(int c) const { return t.done[c] != 0; }
-  CHMC_HD double2_ vel(const double* base, size_t cq, int col, double2_ p) const {
+  CHMC_HD double2_ vel(const double* base, int c, int col, double2_ p) const {
+    const size_t cq = (size_t)c * sy.Q;
     if (sy.m0 && col < sy.U) {
-      p.x = metric_inv_u(sy, base + cq, col);
-      if (col + 1 < sy.U) p.y = metric_inv_u(sy, base + cq, col + 1);
+      p.x = metric_inv_u(sy, c, base + cq, col);
+      if (col + 1 < sy.U) p.y = metric_inv_u(sy, c, base + cq, col + 1);
     }
     return p;
   }
@@ -2890,7 +2898,7 @@ struct KTreeDoubleRows {
     const double2_ pp = fwd ? p : ldv2(pos_p + i, wide, two);
     stv2((fwd ? pos_q : neg_q) + i, q, wide, two);
     stv2((fwd ? pos_p : neg_p) + i, p, wide, two);
-    const double2_ vn = vel(nbase, cq, col, pn), vp = vel(pbase, cq, col, pp);
+    const double2_ vn = vel(nbase, c, col, pn), vp = vel(pbase, c, col, pp);
     acc[0] += vn.x * S.x + (two ? vn.y * S.y : 0.0);
     acc[1] += vp.x * S.x + (two ? vp.y * S.y : 0.0);
   }
@@ -2986,7 +2994,7 @@ struct KMetricSqrtU {
   Slots sl;
   CHMC_HD void operator()(int c) const {
     double* pu = pick(sl.p, sl.cur[c]) + (size_t)c * sy.Q;
-    const double* L = sy.m0 + 2 * sy.U * sy.U;
+    const double* L = metric_of(sy, c) + 2 * sy.U * sy.U;
     for (int a = sy.U - 1; a >= 0; --a) {  // lower triangular: row a only needs entries <= a, so go bottom-up in place
       double t = 0.0;
       for (int b = 0; b <= a; ++b) t += L[a * sy.U + b] * pu[b];
@@ -3006,7 +3014,7 @@ struct KHamiltonian {
     const double ld = sl.logdet[sl.cur[c]][c];
     if (sy.m0) {  // h2 = mom @ metric.inv @ mom / 2 (:1202): the u-part's quadratic form replaces its plain square
       const double* pu = pick(sl.p, sl.cur[c]) + (size_t)c * sy.Q;
-      for (int a = 0; a < sy.U; ++a) pp += pu[a] * (metric_inv_u(sy, pu, a) - pu[a]);
+      for (int a = 0; a < sy.U; ++a) pp += pu[a] * (metric_inv_u(sy, c, pu, a) - pu[a]);
     }
     out[c * 3 + 1] = 0.5 * qq;
     out[c * 3 + 2] = 0.5 * pp;

@@ -11,7 +11,7 @@
 //   work.zeros [256], work.nfallback [128], work.ticket (null);
 //   work.n_active [12] = [batch | half 0 | half 1] x 4 round slots: the view of half h counts in slots 4 (1 + h) ..;
 //   d_y [T] (the observations every chain shares until chmc_set_observations: the per-chain d_yc IS in the list),
-//   d_m0 [3][U][U], the block tables d_blk / d_obs2blk / d_blk_full and the work orders d_order / d_order_half /
+//   d_m0 [3 U U + 1] (the block metric every chain shares until chmc_set_metrics: the per-chain d_m0c IS in the list), the block tables d_blk / d_obs2blk / d_blk_full and the work orders d_order / d_order_half /
 //   d_order_ident (a view takes its half's order);
 //   d_ham [B][4] ([B][3] Hamiltonian terms, or [B] values + [B][3] statistics: not chain-major) and the arrays of the
 //   trajectory trees (TreeState, d_tree_*) and the scratch of chmc_gd_objective_device (d_gd), which only whole-batch launches use.
@@ -39,6 +39,8 @@ struct ChainView {
   // allocated by chmc_set_observations only (null, and kAbsent in the list, until then):
   double* d_yc = nullptr;    // [B][T] per-chain observations: Sys::y with Sys::ystride = T
   double* d_sigc = nullptr;  // [B] per-chain fixed observation-noise std: Sys::sigc
+  // allocated by chmc_set_metrics only:
+  double* d_m0c = nullptr;   // [B][3 U U + 1] per-chain M_0, M_0^-1, chol(M_0), log det(M_0) / 2: Sys::m0 with Sys::m0stride = 3 U U + 1
 };
 
 enum ChainArrayKind {
@@ -102,6 +104,8 @@ void for_each_chain_array(ChainView& v, const KernelPlan& plan, size_t npart, F&
   // per-chain data: no context has them at chmc_create; chmc_set_observations allocates them, and from then on a view
   // advances them like every other array of the list
   arr(v.d_yc, sy.T, only(v.d_yc != nullptr)), arr(v.d_sigc, 1, only(v.d_sigc != nullptr));
+  // per-chain block metrics, likewise: chmc_set_metrics allocates the tables
+  arr(v.d_m0c, 3 * U * U + 1, only(v.d_m0c != nullptr));
 }
 
 // The per-step outputs of chmc_leapfrog_step live in ONE allocation (chmc_ctx::d_out) so that they cross PCIe in a single

@@ -378,10 +378,10 @@ __device__ __forceinline__ void jw_pb_wg(const Sys& sy, const Slots& sl, const W
         for (int d = 0; d < sy.V0; ++d) a += Jv[d] * vct[sy.U + d], a2 += Jv[d] * vct2[sy.U + d];
       }
       const double* ju = pick(sl.JuP, s) + (cb * RM + i) * sy.U;
-      for (int d = 0; d < sy.U; ++d) a += ju[d] * (minv ? metric_inv_u(sy, vct, d) : vct[d]);
+      for (int d = 0; d < sy.U; ++d) a += ju[d] * (minv ? metric_inv_u(sy, c, vct, d) : vct[d]);
       const double sg = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) : 0.0;
       if (sy.noisy && i < bd.ny) a += sg * vct[sy.U + sy.NV + bd.obs0 + i];
-      for (int d = 0; d < sy.U; ++d) a2 += ju[d] * (minv ? metric_inv_u(sy, vct2, d) : vct2[d]);
+      for (int d = 0; d < sy.U; ++d) a2 += ju[d] * (minv ? metric_inv_u(sy, c, vct2, d) : vct2[d]);
       if (sy.noisy && i < bd.ny) a2 += sg * vct2[sy.U + sy.NV + bd.obs0 + i];
     }
     w.cpad[cb * RM + i] = a;

@@ -1123,7 +1123,7 @@ __device__ __forceinline__ void newton_factor16(const Sys& sy, const Slots& sl, 
     constexpr int X = M::X;
     __shared__ double lamS[4][RM];
 #pragma unroll
-    for (int i = 0; i < U * U; ++i) Cm[i] += sy.m0 ? sy.m0[i] : ((i / U == i % U) ? 1.0 : 0.0);
+    for (int i = 0; i < U * U; ++i) Cm[i] += sy.m0 ? metric_of(sy, c)[i] : ((i / U == i % U) ? 1.0 : 0.0);
     {
       int piv[U];
       lu_factor<U>(Cm, piv);
@@ -1157,7 +1157,7 @@ __device__ __forceinline__ void newton_factor16(const Sys& sy, const Slots& sl, 
       unsigned long long nb = 0ULL;
 #pragma unroll
       for (int aa = 0; aa < U; ++aa) {
-        const double dq = metric_inv_u(sy, du, aa);  // delta_q = metric.inv @ delta_mu (:1033-1041, :1105-1113)
+        const double dq = metric_inv_u(sy, c, du, aa);  // delta_q = metric.inv @ delta_mu (:1033-1041, :1105-1113)
         q[aa] -= dq;
         const unsigned long long vb = absbits(dq);
         nb = vb > nb ? vb : nb;
@@ -2295,11 +2295,11 @@ __global__ void __launch_bounds__(256) k_jw_wave(Sys sy, Slots sl, Work w, int w
       if (k == i) a = acc[k], a2 = acc2[k];
     if (i < bd.nrows) {
       const double* ju = pick(sl.JuP, s) + (cb * RM + i) * sy.U;
-      for (int d = 0; d < sy.U; ++d) a += ju[d] * (minv ? metric_inv_u(sy, vct, d) : vct[d]);
+      for (int d = 0; d < sy.U; ++d) a += ju[d] * (minv ? metric_inv_u(sy, c, vct, d) : vct[d]);
       const double sg = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) : 0.0;
       if (sy.noisy && i < bd.ny) a += sg * vct[sy.U + sy.NV + bd.obs0 + i];
       if (TWO) {
-        for (int d = 0; d < sy.U; ++d) a2 += ju[d] * (minv ? metric_inv_u(sy, vct2, d) : vct2[d]);
+        for (int d = 0; d < sy.U; ++d) a2 += ju[d] * (minv ? metric_inv_u(sy, c, vct2, d) : vct2[d]);
         if (sy.noisy && i < bd.ny) a2 += sg * vct2[sy.U + sy.NV + bd.obs0 + i];
       }
     } else {
@@ -2440,11 +2440,11 @@ __device__ __forceinline__ void jw_pb_body(const Sys& sy, const Slots& sl, const
         }
       }
       const double* ju = pick(sl.JuP, s) + (cb * RM + i) * sy.U;
-      for (int d = 0; d < sy.U; ++d) a += ju[d] * (minv ? metric_inv_u(sy, vct, d) : vct[d]);
+      for (int d = 0; d < sy.U; ++d) a += ju[d] * (minv ? metric_inv_u(sy, c, vct, d) : vct[d]);
       const double sg = sy.noisy ? sigma_at(sy, pick(sl.q, s) + (size_t)c * sy.Q, c) : 0.0;
       if (sy.noisy && i < bd.ny) a += sg * vct[sy.U + sy.NV + bd.obs0 + i];
       if (TWO) {
-        for (int d = 0; d < sy.U; ++d) a2 += ju[d] * (minv ? metric_inv_u(sy, vct2, d) : vct2[d]);
+        for (int d = 0; d < sy.U; ++d) a2 += ju[d] * (minv ? metric_inv_u(sy, c, vct2, d) : vct2[d]);
         if (sy.noisy && i < bd.ny) a2 += sg * vct2[sy.U + sy.NV + bd.obs0 + i];
       }
     } else {
@@ -4235,7 +4235,7 @@ __device__ __forceinline__ void solve_chain_body(const Sys& sy, const Slots& sl,
       double v = Cm[i];
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-      Cm[i] = v + (sy.m0 ? sy.m0[i] : ((i / U == i % U) ? 1.0 : 0.0));  // + M_0 (:794-798)
+      Cm[i] = v + (sy.m0 ? metric_of(sy, c)[i] : ((i / U == i % U) ? 1.0 : 0.0));  // + M_0 (:794-798)
     }
     int piv[U];
     lu_factor<U>(Cm, piv);
@@ -4282,7 +4282,7 @@ __device__ __forceinline__ void solve_chain_body(const Sys& sy, const Slots& sl,
       unsigned long long nb = 0ULL;
 #pragma unroll
       for (int a = 0; a < U; ++a) {
-        const double dq = metric_inv_u(sy, du, a);  // delta_q = metric.inv @ delta_mu (:1033-1041, :1105-1113)
+        const double dq = metric_inv_u(sy, c, du, a);  // delta_q = metric.inv @ delta_mu (:1033-1041, :1105-1113)
         q[a] -= dq;
         const unsigned long long vb = absbits(dq);
         nb = vb > nb ? vb : nb;
@@ -4458,7 +4458,7 @@ __device__ __forceinline__ void newton_fsm_body(const Sys& sy, const Slots& sl, 
     double v = Cm[i];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    Cm[i] = v + (sy.m0 ? sy.m0[i] : ((i / U == i % U) ? 1.0 : 0.0));  // + M_0 (:794-798)
+    Cm[i] = v + (sy.m0 ? metric_of(sy, c)[i] : ((i / U == i % U) ? 1.0 : 0.0));  // + M_0 (:794-798)
   }
   {
     int piv[U];
@@ -4495,7 +4495,7 @@ __device__ __forceinline__ void newton_fsm_body(const Sys& sy, const Slots& sl, 
     unsigned long long nb = 0ULL;
 #pragma unroll
     for (int a = 0; a < U; ++a) {
-      const double dq = metric_inv_u(sy, du, a);  // delta_q = metric.inv @ delta_mu (:1033-1041, :1105-1113)
+      const double dq = metric_inv_u(sy, c, du, a);  // delta_q = metric.inv @ delta_mu (:1033-1041, :1105-1113)
       q[a] -= dq;
       const unsigned long long vb = absbits(dq);
       nb = vb > nb ? vb : nb;

@@ -99,9 +99,9 @@ class DynamicTransition:
         d = (edge * span).sum(1)
         M0 = getattr(self.ctx, "M_0", None)
         if M0 is not None:
-            U = M0.shape[0]
-            Wm = self.torch.from_numpy(np.linalg.inv(M0) - np.eye(U)).to(self.dev)
-            d = d + ((edge[:, :U] @ Wm) * span[:, :U]).sum(1)
+            U = M0.shape[-1]
+            Wm = self.torch.from_numpy(np.broadcast_to(np.linalg.inv(M0) - np.eye(U), (edge.shape[0], U, U)).copy()).to(self.dev)
+            d = d + (self.torch.einsum("ba,bac->bc", edge[:, :U], Wm) * span[:, :U]).sum(1)  # (M_0 [U, U] or one per chain)
         return d
 
     def sample(self, it):

@@ -111,7 +111,7 @@ def check_groups(groups, n_groups, num_chains):
 def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_adapt=0, solver=None, rng=None,
                        n_head=6, callback=None, trace_dir=None, trace_func=None, total_chains=None,
                        jitter_length=False, metric_adapter=None, metric_window=0.75, metric_skip=0.25,
-                       path_posterior=None, groups=None, n_groups=None):
+                       path_posterior=None, groups=None, n_groups=None, metric_per_group=False):
     """Runs n_iter transitions on all chains of `ctx`; returns traces of the first `n_head` position components
     ([n_iter, B, n_head]), accept statistics and the step size used.  Directions are sampled per chain and
     transition (forward / backward in time), failed trajectories are rejected.
@@ -139,10 +139,16 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     accept statistic of ITS chains over all ranks (one all-reduce of 2 G numbers per transition), and its own step size:
     out["step_size"] is [n_iter, G], out["group_accept_stat"] likewise, out["final_step_size"] [G].  One group gives the
     numbers of the call without `groups`.  The block metric is one M_0 per context: `metric_adapter` with more than one group
-    raises ValueError."""
+    raises ValueError --
+    metric_per_group: unless this is set.  The adapter then produces one M_0 per group from the statistics of that group's
+    chains over all ranks (`finalize_groups`), in the same window; they are installed with `ctx.set_metric(M, groups=...)`,
+    every group's dual averaging restarts from that group's current step size, and out["metric_M_0"] is [G, U, U]."""
+    if metric_per_group and (groups is None or metric_adapter is None):
+        raise ValueError("metric_per_group needs groups and a metric_adapter")
+    group_metrics = None
     if groups is not None:
         groups, G = check_groups(groups, n_groups, ctx.B)
-        if metric_adapter is not None and G > 1:
+        if metric_adapter is not None and G > 1 and not metric_per_group:
             raise ValueError("the block metric is one M_0 per context: no metric_adapter with more than one group")
     solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
                   reverse_check_tol=2e-8) if solver is None else solver
@@ -220,7 +226,11 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
             if metric_state is None:
                 metric_state = metric_adapter.initialize(np.zeros((B, ctx.Q)))
             metric_adapter.update(metric_state, heads[it])
-            if it == n_metric - 1:
+            if it == n_metric - 1 and metric_per_group:
+                group_metrics = metric_adapter.finalize_groups(metric_state, groups, G)
+                ctx.set_metric(group_metrics, groups=groups)
+                adapter = [DualAveragingStepSize(float(e)) for e in step_size]  # re-tuned under the new metrics, per group
+            elif it == n_metric - 1:
                 metric = metric_adapter.finalize(metric_state)
                 ctx.set_metric(metric.blocks[0].array)
                 # the step size is re-tuned under the new metric
@@ -250,7 +260,9 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
         out["group_accept_stat"] = group_acc_hist
     if path_posterior is not None:
         out["path_posterior"] = path_posterior.pooled()
-    if n_metric:
+    if n_metric and metric_per_group:
+        out["metric_M_0"] = group_metrics
+    elif n_metric:
         out["metric_M_0"] = None if ctx.M_0 is None else ctx.M_0.copy()
     if writer is not None:
         import time
