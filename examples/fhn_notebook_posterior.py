@@ -15,7 +15,11 @@ With `--init gradient-descent` the initial states come from the reference's gene
 the notebook's linear interpolation; candidates are screened in the same way.
 
 usage: fhn_notebook_posterior.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir] [static|dynamic]
-                                 [--init linear-interpolation|gradient-descent]"""
+                                 [--init linear-interpolation|gradient-descent] [--path-posterior STRIDE] [--forecast H]
+--forecast H: posterior predictive forecast of the observed component over H observation intervals beyond the last
+observation: 64 replicate futures of every post-warm-up state with fresh driving noise (paths.PredictivePosterior, simulated on
+the device); mean, sd and the 5 / 50 / 95 % points of the predictive CDF are printed per observation time and
+`predictive.npz` is written next to the traces."""
 import json
 import os
 import sys
@@ -56,8 +60,9 @@ def print_path_posterior(pp, pool, path, y, per_obs, verbose=True):
 
 
 def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=20200710, verbose=True,
-        transition="static", init="linear-interpolation", path_posterior=None):
-    """path_posterior: a stride (a divisor of the steps per observation); the posterior moments of the latent path x(t) at every
+        transition="static", init="linear-interpolation", path_posterior=None, forecast=None):
+    """forecast: a number of observation intervals beyond the last observation (see the usage text).
+    path_posterior: a stride (a divisor of the steps per observation); the posterior moments of the latent path x(t) at every
     stride-th step are accumulated over the main phase and written to `path_posterior.npz` next to the traces."""
     if init not in ("linear-interpolation", "gradient-descent"):
         raise ValueError("init must be linear-interpolation or gradient-descent")
@@ -115,11 +120,16 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
     if path_posterior:
         from manifold_mcmc_for_diffusions_amd.paths import PathPosterior
         pp = PathPosterior(ctx, int(path_posterior))
+    extra, pred = {}, None
+    if forecast:
+        from manifold_mcmc_for_diffusions_amd.paths import PredictivePosterior
+        pred = PredictivePosterior(ctx, int(forecast), n_rep=64, levels=np.linspace(-3.0, 3.0, 241))
+        extra["predictive"] = pred
     t0 = time.time()
     if transition == "dynamic":
         from manifold_mcmc_for_diffusions_amd.dynamic import sample_dynamic_chmc
         res = sample_dynamic_chmc(ctx, n_iter, 0.1, seed=seed, n_adapt=n_warm, trace_dir=tmp, trace_func=trace_func,
-                                  path_posterior=pp,
+                                  path_posterior=pp, **extra,
                                   solver=dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10,
                                               max_iters=50, reverse_check_tol=2e-8),
                                   callback=(lambda it, h, a, e, st: (it % 50 == 0) and print(
@@ -128,7 +138,7 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
         res["fail_rate"] = res["integrator_error"]
     else:
       res = sample_static_chmc(ctx, n_iter, n_step, 0.1, seed=seed, n_adapt=n_warm, trace_dir=tmp, trace_func=trace_func,
-                             jitter_length=True, path_posterior=pp,
+                             jitter_length=True, path_posterior=pp, **extra,
                              solver=dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10,
                                          max_iters=50, reverse_check_tol=2e-8),  # cell 33
                              callback=(lambda it, h, a, e: (it % 50 == 0) and print(
@@ -136,6 +146,14 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
     el = time.time() - t0
     if pp is not None:
         print_path_posterior(pp, res["path_posterior"], pp.save(tmp), d["y"], d["S"] // pp.stride, verbose)
+    if pred is not None:
+        pool, path = res["predictive"], pred.save(tmp)
+        qs = pred.quantiles([0.05, 0.5, 0.95], cdf=pool["cdf"])
+        if verbose:
+            print(f"forecast: {pool['n']} replicate futures pooled over the chains -> {path}")
+            print("     t    E[obs(x(t))] +- sd       5 %     50 %     95 %")
+            for p, t in enumerate(pred.times):
+                print(f"  {t:6.2f}   {pool['mean'][p, -1]:7.3f} +- {pool['sd'][p, -1]:.3f}   {qs[p, 0]:7.3f}  {qs[p, 1]:7.3f}  {qs[p, 2]:7.3f}")
     ctx.close()
     ref = json.load(open(TABLE))
     # A chain that (almost) never moves in the main phase is not exploring a mode, it is stuck on an unusable start that
@@ -211,5 +229,10 @@ if __name__ == "__main__":
         i = a.index("--path-posterior")
         stride = int(a[i + 1])
         del a[i:i + 2]
-    run(*(int(x) for x in a[:4]), init=init, path_posterior=stride, out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
+    forecast = None
+    if "--forecast" in a:
+        i = a.index("--forecast")
+        forecast = int(a[i + 1])
+        del a[i:i + 2]
+    run(*(int(x) for x in a[:4]), init=init, path_posterior=stride, forecast=forecast, out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
         transition=a[5] if len(a) > 5 else "static")

@@ -4,7 +4,11 @@ data, as scripts/sir_model_chmc_experiment.py of the reference sets it up (14 da
 one sub-sequence of 14 observations, sigma_y = 1): batched initial states by the Adam-based finder of the noisy system
 (sde/mici_extensions.py:1679-1801), then batched constrained HMC.
 usage: sir_boarding_school_chmc.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir]
-       [--keyed-init] [--chain-offset N] [--total-chains N] [--path-posterior STRIDE]
+       [--keyed-init] [--chain-offset N] [--total-chains N] [--path-posterior STRIDE] [--forecast DAYS]
+--forecast DAYS: posterior predictive forecast of the observed count for DAYS days after day 14: 64 replicate futures of every
+post-warm-up state with fresh driving and observation noise (paths.PredictivePosterior, simulated on the device); the band
+(mean, sd and the 5 / 50 / 95 % points of the predictive CDF over levels 0, 2, .. 800) is printed per day and `predictive.npz`
+is written next to the traces.
 --path-posterior STRIDE: accumulate the posterior moments of the latent path (S, I and the contact rate at every STRIDE-th step,
 and the observed count) over the main phase; `path_posterior.npz` is written next to the traces and the infected-curve band
 is printed beside the data.
@@ -23,14 +27,14 @@ from manifold_mcmc_for_diffusions_amd.context import ChmcContext  # noqa: E402
 from manifold_mcmc_for_diffusions_amd.sampling import sample_static_chmc  # noqa: E402
 
 a = sys.argv[1:]
-opts = {"--keyed-init": False, "--chain-offset": 0, "--total-chains": None, "--path-posterior": None}
+opts = {"--keyed-init": False, "--chain-offset": 0, "--total-chains": None, "--path-posterior": None, "--forecast": None}
 for name in list(opts):
     if name in a:
         i = a.index(name)
         opts[name] = True if name == "--keyed-init" else int(a[i + 1])
         del a[i:i + (1 if name == "--keyed-init" else 2)]
 keyed, chain_offset, total_chains = opts["--keyed-init"], opts["--chain-offset"], opts["--total-chains"]
-path_stride = opts["--path-posterior"]
+path_stride, forecast = opts["--path-posterior"], opts["--forecast"]
 B = int(a[0]) if len(a) > 0 else 256
 n_iter = int(a[1]) if len(a) > 1 else 300
 n_warm = int(a[2]) if len(a) > 2 else 100
@@ -64,8 +68,13 @@ pp = None
 if path_stride:
     from manifold_mcmc_for_diffusions_amd.paths import PathPosterior
     pp = PathPosterior(ctx, path_stride)
+pred = None
+if forecast:
+    from manifold_mcmc_for_diffusions_amd.paths import PredictivePosterior
+    pred = PredictivePosterior(ctx, forecast, n_rep=64, levels=np.arange(0.0, 801.0, 2.0))
 t0 = time.time()
 res = sample_static_chmc(ctx, n_iter, n_step, 0.05, seed=7, n_adapt=n_warm, n_head=5, jitter_length=True, path_posterior=pp,
+                         **({} if pred is None else {"predictive": pred}),
                          chain_offset=chain_offset, total_chains=total_chains if keyed else None,
                          trace_dir=out_dir or os.path.join(ROOT, "gpurun_out", "sir_run"), trace_func=trace_func,
                          callback=lambda it, h, acc, e: (it % 25 == 0) and print(
@@ -85,3 +94,11 @@ if pp is not None:
     for k, yk in enumerate(y):
         p = (k + 1) * per_obs
         print(f"  {pp.times[p]:5.1f} {yk:6.0f}   {pool['mean'][p, -1]:7.1f} +- {pool['sd'][p, -1]:.1f}")
+if pred is not None:
+    pool = res["predictive"]
+    trace_dir = os.path.dirname(next(iter(res["trace_files"].values())))
+    qs = pred.quantiles([0.05, 0.5, 0.95], cdf=pool["cdf"])
+    print(f"forecast: {pool['n']} replicate futures pooled over the chains -> {pred.save(trace_dir)}")
+    print("   day   E[count] +- sd      5 %    50 %    95 %")
+    for p, t in enumerate(pred.times):
+        print(f"  {t:5.1f}   {pool['mean'][p, -1]:7.1f} +- {pool['sd'][p, -1]:5.1f}  {qs[p, 0]:7.1f} {qs[p, 1]:7.1f} {qs[p, 2]:7.1f}")

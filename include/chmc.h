@@ -251,6 +251,47 @@ int chmc_generate_x_seq_device(chmc_ctx* ctx, int stride, void* x_seq_dev, int* 
 int chmc_path_stats_update_device(chmc_ctx* ctx, int stride, const int* mask, void* x_seq_dev, void* n_dev, void* mean_dev,
                                   void* m2_dev);
 
+/* Posterior predictive simulation on the device: forecasts beyond the last observation and replicated data sets, folded into
+ * running moments per chain.  For chain c with current position q = [u | v_0 | v_seq | n], z = generate_z(u) and
+ * dl = obs_interval / S, replicate r = 0 .. n_rep - 1 integrates horizon * S steps of the model's one-step map from
+ *   origin = 0 (forecast):    x_T, the state after step T S of the chain's path as chmc_generate_x_seq* defines it (the
+ *                             path is rebuilt from q by the path scan, never read from a possibly stale x_obs_seq, so the call is
+ *                             right after leapfrog steps with no partition switch in between); point p has time
+ *                             T obs_interval + p stride dl,
+ *   origin = 1 (replication): x_0 = generate_x_0(z, v_0); point p has time p stride dl (horizon = T, stride = S: a
+ *                             replicated data set for a posterior predictive check),
+ * driven by fresh normals w_r = [v (horizon S V) | eps (NPF)] and emits the NPF = horizon S / stride points p = 1 .. NPF
+ * (stride >= 1 divides S).  Normals 2 j, 2 j + 1 of w_r are the pair j of the keyed stream of chmc_fill_normal*:
+ *   (seed, stream = chain_offset + c, draw_key = CHMC_PREDICT_DRAW | (draw << 16) | r),   draw < 2^45, n_rep <= 65536,
+ * disjoint from the momentum refresh (small draw indices), CHMC_SIMULATE_DRAW (bit 62) and the finders (bit 63).  Without
+ * observation noise (noisy == 0) w_r has no eps part.
+ * Channels per point, XC = X + 2: the X state components, obs_func(x), and y_rep = obs_func(x) + sigma_c eps_p with
+ * sigma_c the chain's observation-noise std (the context's, the chain's own after chmc_set_observations, or exp(u[Z]) with
+ * variable noise); noisy == 0: y_rep = obs_func(x).
+ * Running moments per (chain, point, channel): n_dev [B] (long long, counts replicate paths), mean_dev, m2_dev
+ * [B][NPF][XC] are the caller's device buffers, zero before the first call.  One call merges its replicates in groups of 64
+ * consecutive replicates, in group order (the last group may be partial): for a group of R_g values v,
+ *   m_g = sum(v) / R_g,  s_g = sum((v - m_g)^2),  then Chan's merge
+ *   n' = n + R_g;  d = m_g - mean;  mean += d R_g / n';  m2 += s_g + d^2 n R_g / n'.
+ * Non-finite values are not filtered: a replicate that leaves the finite range makes that point's mean and m2 (and every
+ * later point's it reaches) non-finite from then on, and counts in no CDF level.
+ * Predictive CDF of y_rep: with n_levels > 0 and levels (host, n_levels increasing doubles),
+ *   cdf_dev [B][NPF][n_levels] (long long) += #{r : y_rep_r <= levels[l]}.
+ * Kept paths: paths_dev [B][n_keep][NPF][XC] receives the first n_keep <= n_rep replicates of this call (overwritten by
+ * every call); n_keep = 0 or a NULL pointer keeps none.
+ * mask (host [B], NULL = all): no buffer of a chain with mask[c] == 0 is touched.
+ * A chain's outputs depend on (seed, draw, chain_offset + c), its own state and data alone -- not on B, the other chains or
+ * the launch geometry: any sharding of the chains gives the same bits.
+ * Errors: no state set; horizon < 1; stride < 1 or not a divisor of num_steps_per_obs; origin not 0 or 1; n_rep outside
+ * [1, 65536]; n_keep outside [0, n_rep]; draw >= 2^45; n_levels < 0, or n_levels > 0 with NULL levels or cdf_dev; levels
+ * not increasing; a NULL n_dev, mean_dev or m2_dev.
+ * chmc_predict_points: NPF into *n_points and, where times != NULL, the NPF point times. */
+#define CHMC_PREDICT_DRAW (1ULL << 61)
+int chmc_predict_points(const chmc_ctx* ctx, int horizon, int stride, int origin, int* n_points, double* times);
+int chmc_predict_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset, int horizon,
+                        int stride, int origin, int n_rep, const int* mask, int n_levels, const double* levels, void* n_dev,
+                        void* mean_dev, void* m2_dev, void* cdf_dev, void* paths_dev, int n_keep);
+
 /* ---- per-op entry points, evaluated at the current state ------------------------------------------------
  * Internally the library keeps the dc/dv rows of a state in a compact factored form (per step a row-independent X x V
  * matrix, per observation interval the RM x X adjoint frame; DESIGN.md section 4 "Compact rows") and the stepping path
@@ -443,7 +484,9 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *   out80[74]      launches of the time-parallel path scan (k_path_par: chmc_generate_x_seq* / chmc_path_stats_update_device
  *                  on the current states with the compact rows allocated)
  *   out80[75]      launches of the sequential path scan (KPath: a caller's q, or CHMC_COMPACT_ROWS=0)
- *   out80[76 .. 79] reserved (0)
+ *   out80[76]      launches of the predictive wave kernel (k_predict: chmc_predict_device with the compact rows on)
+ *   out80[77]      launches of the predictive functor form (KPredict: CHMC_COMPACT_ROWS=0)
+ *   out80[78 .. 79] reserved (0)
  * Synchronises the context's stream. */
 int chmc_get_diagnostics(chmc_ctx* ctx, long long* out80);
 

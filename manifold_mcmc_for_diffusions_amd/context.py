@@ -338,6 +338,30 @@ class ChmcContext:
                                                    C.c_void_p(n_dev_ptr), C.c_void_p(mean_dev_ptr), C.c_void_p(m2_dev_ptr)),
               "chmc_path_stats_update_device")
 
+    # ---- posterior predictive simulation (chmc_predict_points, chmc_predict_device; paths.PredictivePosterior keeps the buffers)
+    def predict_points(self, horizon, stride, origin=0):
+        """(NPF, times): the points of a predictive over `horizon` observation intervals at `stride` and their times
+        (origin 0: after the last observation; 1: from time 0)."""
+        n = C.c_int(0)
+        check(self.L.chmc_predict_points(self.h, int(horizon), int(stride), int(origin), C.byref(n), None),
+              "chmc_predict_points")
+        times = np.empty(n.value)
+        check(self.L.chmc_predict_points(self.h, int(horizon), int(stride), int(origin), C.byref(n), ptr(times)),
+              "chmc_predict_points")
+        return n.value, times
+
+    def predict_device(self, seed, draw, chain_offset, horizon, stride, origin, n_rep, n_dev_ptr, mean_dev_ptr, m2_dev_ptr,
+                       mask=None, levels=None, cdf_dev_ptr=None, paths_dev_ptr=None, n_keep=0):
+        """n_rep replicate futures (origin 0) or replicated data sets (origin 1) of every chain's current state, merged into
+        the caller's device moments, CDF counts and kept paths (chmc_predict_device, include/chmc.h)."""
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        lv = None if levels is None else as_c(levels).reshape(-1)
+        check(self.L.chmc_predict_device(self.h, int(seed), int(draw), int(chain_offset), int(horizon), int(stride),
+                                         int(origin), int(n_rep), iptr(m), 0 if lv is None else len(lv), ptr(lv),
+                                         C.c_void_p(n_dev_ptr), C.c_void_p(mean_dev_ptr), C.c_void_p(m2_dev_ptr),
+                                         C.c_void_p(cdf_dev_ptr), C.c_void_p(paths_dev_ptr), int(n_keep)),
+              "chmc_predict_device")
+
     # ---- per-op
     @property
     def dim_c(self):
@@ -583,7 +607,8 @@ class ChmcContext:
                     retract_kernel_launches=int(v[66]), traj_kernel_launches=int(v[67]),
                     newton_fsm_launches=int(v[68]), newton_factor8_launches=int(v[69]), pair_scan_rounds=int(v[70]),
                     newton_scan_launches=int(v[71]), newton_rounds=int(v[72]), path_par_launches=int(v[74]),
-                    path_seq_launches=int(v[75]), extra=v[68:80])
+                    path_seq_launches=int(v[75]), predict_wave_launches=int(v[76]), predict_seq_launches=int(v[77]),
+                    extra=v[68:80])
 
     def counters(self):
         out = (C.c_longlong * 8)()

@@ -52,7 +52,12 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   int* d_path_ints = nullptr;       // chmc_generate_x_seq* / chmc_path_stats_update_device: [2][B] sweeps, mask
   double* d_path_out = nullptr;     // chmc_generate_x_seq: staging of the host form's output, d_path_cap doubles
   size_t d_path_cap = 0;
-  TreeState tree{};                                      // chmc_tree_begin / _subtree / _step: per-chain tree decisions
+  double* d_pred = nullptr;         // chmc_predict_device: the replicates' raw channels or group statistics, d_pred_cap doubles
+  size_t d_pred_cap = 0;
+  double* d_pred_x = nullptr;       // ... [B][T + 1][X] the chains' paths at the observation times (the forecast's start state)
+  double* d_pred_lev = nullptr;     // ... the CDF levels, d_pred_lev_cap doubles
+  size_t d_pred_lev_cap = 0;
+  TreeState tree{};                                     // chmc_tree_begin / _subtree / _step: per-chain tree decisions
   bool have_tree = false;
   bool rows_fresh = false;  // Slots::Jv holds the full rows of the current states (see ensure_rows)
   std::vector<unsigned char> h_out;
@@ -66,7 +71,8 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
                               // lock-step Newton loops, [8] rounds enqueued by them, per problem, [9] rounds of a paired loop
                               // whose passes behind the scan served two problems as well (KernelPlan::pair_passes: interval
                               // sums, combine, solve and J^T lambda update one launch each; a subset of [6]), [10] launches of
-                              // the time-parallel path scan, [11] of the sequential one (KPath)
+                              // the time-parallel path scan, [11] of the sequential one (KPath), [12] of the predictive wave
+                              // kernel, [13] of its functor form (KPredict)
   // Paired retractions (KernelPlan::pair_retractions): the second problem of run_projection_pair -- the forward retraction of
   // the NEXT step -- works in a Work of its own: every array a round's kernels, KNewtonBegin, KCheck or KNewtonEnd write
   // (pair_alloc), everything they only read shared with `w`.  Whole batch only, allocated on first use.
@@ -1226,6 +1232,74 @@ extern "C" int chmc_path_stats_update_device(chmc_ctx* ctx, int stride, const in
     launch(g, (long)sy.B * NP, 8);
   });
   CHMC_LEAVE("chmc_path_stats_update_device")
+}
+
+// posterior predictive simulation (include/chmc.h): predict_pass picks the kernel
+static int predict_check(const chmc_ctx* ctx, const char* fn, int horizon, int stride, int origin) {
+  if (horizon < 1) return fail(std::string(fn) + ": horizon must be at least 1");
+  if (stride < 1 || ctx->sy.S % stride != 0)
+    return fail(std::string(fn) + ": stride must be at least 1 and divide num_steps_per_obs");
+  if (origin != 0 && origin != 1) return fail(std::string(fn) + ": origin must be 0 (forecast) or 1 (replication)");
+  if ((long long)horizon * ctx->sy.S * (ctx->sy.V + 1) >= (1LL << 31))
+    return fail(std::string(fn) + ": horizon too long for the 32-bit counter of the normal stream");
+  return 0;
+}
+extern "C" int chmc_predict_points(const chmc_ctx* ctx, int horizon, int stride, int origin, int* n_points, double* times) {
+  if (!ctx) return fail("chmc_predict_points: null context");
+  if (!n_points) return fail("chmc_predict_points: null output");
+  if (predict_check(ctx, "chmc_predict_points", horizon, stride, origin)) return -1;
+  const Sys& sy = ctx->sy;
+  const int NPF = horizon * sy.S / stride;
+  *n_points = NPF;
+  const double t0 = origin == 0 ? sy.T * ctx->cfg.obs_interval : 0.0;
+  if (times)
+    for (int p = 1; p <= NPF; ++p) times[p - 1] = t0 + p * (stride * sy.dl);
+  return 0;
+}
+extern "C" int chmc_predict_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset,
+                                   int horizon, int stride, int origin, int n_rep, const int* mask, int n_levels,
+                                   const double* levels, void* n_dev, void* mean_dev, void* m2_dev, void* cdf_dev,
+                                   void* paths_dev, int n_keep) {
+  CHMC_ENTER("chmc_predict_device")
+  if (!n_dev || !mean_dev || !m2_dev) return fail("chmc_predict_device: null argument");
+  if (predict_check(ctx, "chmc_predict_device", horizon, stride, origin)) return -1;
+  if (!ctx->have_state) return fail("chmc_predict_device: no state has been set");
+  if (n_rep < 1 || n_rep > 65536) return fail("chmc_predict_device: n_rep must be in [1, 65536]");
+  if ((long long)ctx->sy.B * n_rep >= (1LL << 31) || (long long)ctx->sy.B * (horizon * ctx->sy.S / stride) >= (1LL << 31))
+    return fail("chmc_predict_device: chains x replicates and chains x points must stay below 2^31");
+  if (n_keep < 0 || n_keep > n_rep) return fail("chmc_predict_device: n_keep must be in [0, n_rep]");
+  if (draw >= (1ULL << 45)) return fail("chmc_predict_device: draw must be below 2^45");
+  if (n_levels < 0) return fail("chmc_predict_device: n_levels must not be negative");
+  if (n_levels > 0 && (!levels || !cdf_dev)) return fail("chmc_predict_device: n_levels > 0 needs levels and cdf_dev");
+  for (int l = 1; l < n_levels; ++l)
+    if (!(levels[l] > levels[l - 1])) return fail("chmc_predict_device: levels must be increasing");
+  const Sys& sy = ctx->sy;
+  if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)sy.B);
+  PredictArgs a{};
+  a.seed = seed, a.key0 = CHMC_PREDICT_DRAW | (draw << 16);
+  a.chain_offset = chain_offset, a.HS = horizon * sy.S, a.stride = stride, a.NPF = a.HS / stride;
+  a.n_rep = n_rep, a.n_keep = paths_dev ? n_keep : 0, a.n_levels = n_levels;
+  a.paths = a.n_keep ? (double*)paths_dev : nullptr;
+  if (origin == 0) {  // x_T: the last point of the path of the current states at the observation times
+    if (!ctx->d_pred_x) ctx->d_pred_x = alloc<double>(ctx, (size_t)sy.B * (sy.T + 1) * sy.X);
+    path_run(ctx, nullptr, sy.S, ctx->d_pred_x, nullptr);
+    a.xstart = ctx->d_pred_x + (size_t)sy.T * sy.X, a.xld = (long long)(sy.T + 1) * sy.X;
+  }
+  if (mask) {
+    int* d_mask = ctx->d_path_ints + sy.B;
+    h2d(d_mask, mask, sizeof(int) * sy.B);
+    a.mask = d_mask;
+  }
+  if (n_levels > 0) {
+    if (ctx->d_pred_lev_cap < (size_t)n_levels)
+      ctx->d_pred_lev = alloc<double>(ctx, (size_t)n_levels), ctx->d_pred_lev_cap = (size_t)n_levels;
+    h2d(ctx->d_pred_lev, levels, sizeof(double) * n_levels);
+    a.levels = ctx->d_pred_lev;
+  }
+  dispatch(ctx, [&](auto inst) {
+    predict_pass<typename decltype(inst)::M>(ctx, a, (long long*)n_dev, (double*)mean_dev, (double*)m2_dev, (long long*)cdf_dev);
+  });
+  CHMC_LEAVE("chmc_predict_device")
 }
 
 // padded [B][Kmax][RM] <-> packed [B][C] conversion of block-row vectors (host side, small)

@@ -2164,6 +2164,159 @@ struct KNormalFillRows {
     }
   }
 };
+// ------------------------------------------------------------------------------------------
+// Posterior predictive simulation (chmc_predict_device, include/chmc.h): replicate r of chain c integrates HS steps from the
+// chain's start state over fresh keyed normals w_r = [v (HS V) | eps (NPF)] and emits XC = X + 2 channels per point: the
+// state, obs(x), y_rep = obs(x) + sigma_c eps.  The replicate's arithmetic is ONE function, predict_replicate, shared by the
+// functor form below (KPredict, a work item per replicate) and by the wave kernel (k_predict, chmc_wave.h: a lane per
+// replicate), so the two differ in the reduction order of the group statistics alone.
+struct PredictArgs {
+  unsigned long long seed, key0;  // key0 = CHMC_PREDICT_DRAW | draw << 16; the replicate's draw key is key0 | r
+  int chain_offset, HS, stride, NPF, n_rep, n_keep, n_levels;
+  const int* mask;        // [B] or null
+  const double* xstart;   // origin 0: x_T of chain c at xstart + c * xld; null: origin 1, x_0 = generate_x_0(z, v_0)
+  long long xld;
+  const double* levels;   // [n_levels] on the device
+  double* paths;          // [B][n_keep][NPF][XC] or null
+};
+// Sequential reader of one keyed normal stream: at(i) is normal i; a pair is drawn once while its two normals are read in
+// order (V = 3: the pair that straddles two steps keeps its second normal for the next step).
+struct NormalCursor {
+  unsigned long long seed, key;
+  uint32_t stream, j;
+  double n0, n1;
+  CHMC_HD void open(unsigned long long seed_, unsigned long long key_, uint32_t stream_) {
+    seed = seed_, key = key_, stream = stream_, j = 0xffffffffu, n0 = n1 = 0.0;
+  }
+  CHMC_HD CHMC_FI inline double at(uint32_t i) {
+    const uint32_t jj = i >> 1;
+    if (jj != j) {
+      philox_normal_pair(seed, key, stream, jj, n0, n1);
+      j = jj;
+    }
+    return (i & 1u) ? n1 : n0;
+  }
+};
+// emit(p, ch): point p = 0 .. NPF - 1 (time index p + 1) with its XC channels.  The step noise and the observation noise are
+// read through a cursor each, so that the eps reads between the steps do not evict the step noise's open pair (one pair, at
+// the junction of the two parts, is drawn by both where HS V is odd).  Forced inline: x and the constants stay in registers.
+template <class M, class Emit>
+CHMC_HD CHMC_FI inline void predict_replicate(const Sys& sy, const PredictArgs& a, const double* q, int c, int r, Emit emit) {
+  constexpr int X = M::X, V = M::V, XC = X + 2;
+  ChainConsts<M> cc;
+  cc.init(q, sy.dl);
+  double x[X], xn[X], vv[V], ch[XC];
+  if (a.xstart) {
+    CHMC_UNROLL
+    for (int i = 0; i < X; ++i) x[i] = a.xstart[(size_t)c * a.xld + i];
+  } else {
+    M::gx0(cc.z, q + sy.U, x);
+  }
+  const double sig = sy.noisy ? sigma_at(sy, q, c) : 0.0;
+  NormalCursor cv, ce;
+  cv.open(a.seed, a.key0 | (unsigned long long)r, (uint32_t)(a.chain_offset + c));
+  ce = cv;
+  const uint32_t e0 = (uint32_t)a.HS * V;
+  int left = a.stride, p = 0;
+  for (int s = 0; s < a.HS; ++s) {
+    CHMC_UNROLL
+    for (int i = 0; i < V; ++i) vv[i] = cv.at((uint32_t)s * V + i);
+    M::step(cc.k, x, vv, xn);
+    CHMC_UNROLL
+    for (int i = 0; i < X; ++i) x[i] = xn[i];
+    if (--left == 0) {
+      CHMC_UNROLL
+      for (int i = 0; i < X; ++i) ch[i] = x[i];
+      ch[X] = M::obs(x);
+      ch[X + 1] = sy.noisy ? ch[X] + sig * ce.at(e0 + (uint32_t)p) : ch[X];
+      emit(p, ch);
+      ++p;
+      left = a.stride;
+    }
+  }
+}
+// The functor form, pass 1: one work item per (chain, replicate); the replicate's channels go to the library's scratch
+// raw [B][n_rep][NPF][XC], and to the kept paths for r < n_keep.
+template <class M>
+struct KPredict {
+  Sys sy;
+  Slots sl;
+  PredictArgs a;
+  double* raw;
+  CHMC_HD void operator()(int tid) const {
+    constexpr int XC = M::X + 2;
+    const int c = tid / a.n_rep, r = tid - c * a.n_rep;
+    if (a.mask && !a.mask[c]) return;
+    const double* q = pick(sl.q, sl.cur[c]) + (size_t)c * sy.Q;
+    double* o = raw + ((size_t)c * a.n_rep + r) * a.NPF * XC;
+    double* k = a.paths && r < a.n_keep ? a.paths + ((size_t)c * a.n_keep + r) * a.NPF * XC : nullptr;
+    predict_replicate<M>(sy, a, q, c, r, [&](int p, const double* ch) {
+      for (int i = 0; i < XC; ++i) o[(size_t)p * XC + i] = ch[i];
+      if (k)
+        for (int i = 0; i < XC; ++i) k[(size_t)p * XC + i] = ch[i];
+    });
+  }
+};
+// Chan's merge of a group (R values, mean mg, centred sum of squares sg) into running moments of nn values
+CHMC_HD CHMC_FI inline void predict_merge(double nn, double R, double mg, double sg, double& mu, double& s2) {
+  const double n1 = nn + R, d = mg - mu;
+  mu += d * R / n1;
+  s2 += sg + d * d * nn * R / n1;
+}
+// Pass 2 of both forms.  phase 0: one work item per chain counts the replicates, n[c] += n_rep; phase 1 (a launch behind
+// it): one work item per (chain, point) merges the call's groups of 64 consecutive replicates, in group order, into
+// mean / m2 [B][NPF][XC] and adds the CDF counts.  The group statistics come from src:
+//   grouped: [B][G][NPF][2 XC + n_levels] = m_g, s_g, counts, as the wave kernel left them;
+//   else:    the raw replicates of KPredict, summed here in replicate order (two passes: mean, then centred squares).
+template <class M>
+struct KPredictFold {
+  int NPF, n_rep, n_levels, phase, grouped;
+  const int* mask;
+  const double* levels;
+  const double* src;
+  long long* n;
+  double *mean, *m2;
+  long long* cdf;
+  CHMC_HD void operator()(int tid) const {
+    constexpr int XC = M::X + 2;
+    const int c = phase ? tid / NPF : tid;
+    if (mask && !mask[c]) return;
+    if (!phase) {
+      n[c] += n_rep;
+      return;
+    }
+    const int p = tid - c * NPF, G = (n_rep + 63) / 64, REC = 2 * XC + n_levels;
+    double nn = (double)(n[c] - n_rep);
+    double* mp = mean + (size_t)tid * XC;
+    double* sp = m2 + (size_t)tid * XC;
+    long long* cp = cdf ? cdf + (size_t)tid * n_levels : nullptr;
+    for (int g = 0; g < G; ++g) {
+      const int R = n_rep - 64 * g < 64 ? n_rep - 64 * g : 64;
+      if (grouped) {
+        const double* rec = src + (((size_t)c * G + g) * NPF + p) * REC;
+        for (int i = 0; i < XC; ++i) predict_merge(nn, (double)R, rec[i], rec[XC + i], mp[i], sp[i]);
+        for (int l = 0; l < n_levels; ++l) cp[l] += (long long)rec[2 * XC + l];
+      } else {
+        const double* v = src + (((size_t)c * n_rep + 64 * g) * NPF + p) * XC;  // replicate k of the group: v + k NPF XC
+        const size_t ld = (size_t)NPF * XC;
+        for (int i = 0; i < XC; ++i) {
+          double sum = 0.0, sq = 0.0;
+          for (int k = 0; k < R; ++k) sum += v[k * ld + i];
+          const double mg = sum / R;
+          for (int k = 0; k < R; ++k) sq += (v[k * ld + i] - mg) * (v[k * ld + i] - mg);
+          predict_merge(nn, (double)R, mg, sq, mp[i], sp[i]);
+        }
+        for (int l = 0; l < n_levels; ++l) {
+          int cnt = 0;
+          for (int k = 0; k < R; ++k) cnt += v[k * ld + XC - 1] <= levels[l] ? 1 : 0;
+          cp[l] += cnt;
+        }
+      }
+      nn += R;
+    }
+  }
+};
+
 // "Deal a try into a row" (chmc_adam_begin_tries_device): zero moments and gradient of the listed rows, and the row's work
 // trajectory -- the guess the time-parallel scan of the comparator target would otherwise inherit from whatever was
 // evaluated in that row before.  One work item per (listed row, element), the longer of the two spans.

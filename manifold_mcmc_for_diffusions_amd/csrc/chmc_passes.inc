@@ -50,8 +50,42 @@ static void path_seq(chmc_ctx* c, const double* q, int stride, double* out, int*
   launch(KPath<M>{c->sy, c->sl, q, stride, out}, c->sy.B, 7), c->diag[11]++;
 }
 
+// chmc_predict_device: the library's scratch for the replicates' channels or group statistics, grown on demand
+static double* predict_scratch(chmc_ctx* c, size_t n) {
+  if (c->d_pred_cap < n) c->d_pred = alloc<double>(c, n), c->d_pred_cap = n;
+  return c->d_pred;
+}
+// the moments' second pass (KPredictFold): the replicates are counted, then every (chain, point) merges the call's groups
+template <class M>
+static void predict_fold(chmc_ctx* c, const PredictArgs& a, int grouped, const double* src, long long* n, double* mean, double* m2,
+                         long long* cdf) {
+  KPredictFold<M> f{a.NPF, a.n_rep, a.n_levels, 0, grouped, a.mask, a.levels, src, n, mean, m2, cdf};
+  launch(f, c->sy.B, 8);
+  f.phase = 1;
+  launch(f, (long)c->sy.B * a.NPF, 8);
+}
+// the predictive by the generic functors: a work item per (chain, replicate) writes the raw channels, the fold sums them in
+// replicate order
+template <class M>
+static void predict_seq(chmc_ctx* c, const PredictArgs& a, long long* n, double* mean, double* m2, long long* cdf) {
+  double* raw = predict_scratch(c, (size_t)c->sy.B * a.n_rep * a.NPF * (M::X + 2));
+  launch(KPredict<M>{c->sy, c->sl, a, raw}, (long)c->sy.B * a.n_rep, 7), c->diag[13]++;
+  predict_fold<M>(c, a, 0, raw, n, mean, m2, cdf);
+}
+
 #ifdef CHMC_WAVE_KERNELS
 constexpr bool kWaveKernels = true;  // PlanInput::wave_kernels of every context of this build
+// chmc_predict_device: a wavefront per (chain, group of 64 replicates) where the library keeps the compact rows (the
+// default; path_scan's rule) leaves the groups' statistics to the fold; CHMC_COMPACT_ROWS=0 runs the functor form, the A/B
+// partner
+template <class M>
+static void predict_pass(chmc_ctx* c, const PredictArgs& a, long long* n, double* mean, double* m2, long long* cdf) {
+  if (!c->plan.pb_allocated) return predict_seq<M>(c, a, n, mean, m2, cdf);
+  const int G = (a.n_rep + 63) / 64;
+  double* grp = predict_scratch(c, (size_t)c->sy.B * G * a.NPF * (2 * (M::X + 2) + a.n_levels));
+  launch_blocks(k_predict<M>, (long)c->sy.B * G, 64, 7, c->sy, c->sl, a, grp), c->diag[12]++;
+  predict_fold<M>(c, a, 1, grp, n, mean, m2, cdf);
+}
 // chain-level Woodbury solve: one wavefront per chain up to 64 blocks
 template <class M, int RM, int SYM, int TGT>
 static void solve_chain(const Sys& sy, const Slots& sl, const Work& w, int which, int qsel, int psel) {
@@ -471,6 +505,10 @@ static void xobs_par(chmc_ctx*) { no_wave_kernels("the partition switch's time-p
 template <class M>
 static void path_scan(chmc_ctx* c, const double* q, int stride, double* out, int* sweeps) {
   path_seq<M>(c, q, stride, out, sweeps);
+}
+template <class M>
+static void predict_pass(chmc_ctx* c, const PredictArgs& a, long long* n, double* mean, double* m2, long long* cdf) {
+  predict_seq<M>(c, a, n, mean, m2, cdf);
 }
 template <class M, int RM>
 static void nld_sweeps(chmc_ctx*, const Sys&, int, int, double*) { no_wave_kernels("the comparator target"); }

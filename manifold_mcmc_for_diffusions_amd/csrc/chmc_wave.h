@@ -5773,6 +5773,70 @@ __global__ void __launch_bounds__(64 * W) k_fwd_par(Sys sy, Slots sl, Work w, in
     for (int i = bd.nrows; i < RM; ++i) out[i] = 0.0;  // padded constraint slots
 }
 
+// Posterior predictive simulation (chmc_predict_device): one wavefront per (chain, group of 64 consecutive replicates), one
+// lane per replicate.  The lane runs predict_replicate (chmc_core.h: x, the model constants and the open Philox pair stay in
+// registers, the normals are generated in the loop); at every emitted point the wavefront reduces each of the XC channels
+// over its lanes -- sum, then the centred squares about the group mean; both by wave_allsum, which leaves the same bits in
+// every lane -- and counts y_rep <= level by a ballot per level.  Lanes past n_rep (the partial last group) repeat
+// the last replicate so that every lane runs the same trip counts, and enter the sums as zeros and the ballots as false.
+// What leaves the wavefront per point is the record [m_g (XC) | s_g (XC) | counts (n_levels)] of (chain, group, point) in
+// grp [B][G][NPF][2 XC + n_levels], 64 times less than the raw replicates; KPredictFold<.., grouped> merges the groups in
+// order behind it.  The kernel only ever stores: with 256 chains x 64 replicates there is one wavefront on a quarter of
+// the SIMDs and nothing hides a load, so a merge into the caller's moments inside the loop (a read-modify-write per point,
+// measured: 8 us per emitted point, profiles/predictive_timing.txt) put the memory latency on the recursion's critical path.
+// Kept paths (r < n_keep): every lane stores its own XC doubles per point, rows NPF XC doubles apart -- a plotting output
+// of a few replicates, not worth a transpose through LDS.
+// Sum of v over the 64 lanes, the same bits in every lane.  Inside each row of 16 lanes by rotations through the DPP path
+// (row_ror:n = 0x120 + n): after adding the row rotated by 8, 4, 2 and 1 the partial sums have period 8, 4, 2 and 1 in the
+// row bit for bit, because both lanes of a pair add the same two numbers (a + b == b + a).  Across the four rows by two xor
+// shuffles.  (Six xor shuffles, the form of the Gram kernels, make three times the LDS crossbar trips; with 2 XC sums per
+// emitted point and one wavefront on a SIMD that was 0.3 of the 5.5 us a point cost, profiles/predictive_timing.txt.)
+__device__ __forceinline__ double wave_allsum(double v) {
+  v += dpp_mov<0x128, 0xf, 0xf>(v, 0.0);
+  v += dpp_mov<0x124, 0xf, 0xf>(v, 0.0);
+  v += dpp_mov<0x122, 0xf, 0xf>(v, 0.0);
+  v += dpp_mov<0x121, 0xf, 0xf>(v, 0.0);
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+template <class M>
+__global__ void __launch_bounds__(64) k_predict(Sys sy, Slots sl, PredictArgs a, double* grp) {
+  constexpr int X = M::X, XC = X + 2;
+  const int lane = threadIdx.x & 63;
+  const int G = (a.n_rep + 63) / 64;
+  const int c = blockIdx.x / G, g = blockIdx.x - c * G;
+  if (c >= sy.B) return;
+  if (a.mask && !a.mask[c]) return;
+  const int R = a.n_rep - 64 * g < 64 ? a.n_rep - 64 * g : 64;
+  const bool act = lane < R;
+  const int r = 64 * g + (act ? lane : R - 1);
+  const int REC = 2 * XC + a.n_levels;
+  const double* q = pick(sl.q, sl.cur[c]) + (size_t)c * sy.Q;
+  double* keep = a.paths && act && r < a.n_keep ? a.paths + ((size_t)c * a.n_keep + r) * a.NPF * XC : nullptr;
+  double* rec0 = grp + ((size_t)c * G + g) * a.NPF * REC;
+  predict_replicate<M>(sy, a, q, c, r, [&](int p, const double* ch) {
+    if (keep) {
+#pragma unroll
+      for (int i = 0; i < XC; ++i) keep[(size_t)p * XC + i] = ch[i];
+    }
+    double mg = 0.0, sg = 0.0;  // lane i < XC: the group statistics of channel i
+#pragma unroll
+    for (int i = 0; i < XC; ++i) {
+      const double m = wave_allsum(act ? ch[i] : 0.0) / R;
+      const double d = act ? ch[i] - m : 0.0;
+      const double s = wave_allsum(d * d);
+      if (lane == i) mg = m, sg = s;
+    }
+    double* rec = rec0 + (size_t)p * REC;
+    if (lane < XC) rec[lane] = mg, rec[XC + lane] = sg;
+    for (int l = 0; l < a.n_levels; ++l) {
+      const int cnt = __popcll(__ballot(act && ch[XC - 1] <= a.levels[l]));
+      if (lane == (l & 63)) rec[2 * XC + l] = (double)cnt;
+    }
+  });
+}
+
 // (An LDS-staged variant of the forward scan -- 8 lanes fetching one block's 128-byte tile, tiles parked in LDS with a
 // 144-byte row stride, trajectory tiles written back the same way -- was built and measured at 2x the time of the
 // plain lane-per-block scan of chmc_core.h: with one wavefront per SIMD the extra LDS round trips sit on the

@@ -151,7 +151,7 @@ class DynamicTransition:
 
 def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0, total_chains=None, n_head=6,
                         trace_dir=None, trace_func=None, callback=None, per_chain_step_size=True, path_posterior=None,
-                        groups=None, n_groups=None, **kw):
+                        groups=None, n_groups=None, predictive=None, **kw):
     """Momentum refresh -> dynamic transition -> partition switch, `n_iter` times for all chains of `ctx`, with
     dual-averaging step-size adaptation on the tree's accept statistic during warm-up: the reference's sampling loop
     (scripts/utils.py:292-306, 338-365), batched.  As in Mici every chain adapts its own step size during warm-up (the
@@ -165,7 +165,10 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     groups [B], n_groups: chains that sample different posteriors in one context (per-chain observations): groups[c] is the
     global id of chain c's data set.  Warm-up is per chain as before; the main phase of a chain runs with the mean of the
     adapted step sizes of ITS group over all ranks instead of the all-chain mean (out["group_step_sizes"] [G]; one group
-    gives the numbers of the call without `groups`).  Needs per_chain_step_size."""
+    gives the numbers of the call without `groups`).  Needs per_chain_step_size.
+    predictive: a `paths.PredictivePosterior` of `ctx`; after warm-up every state (after the partition switch) gets
+    `predictive.update(seed, it, chain_offset)`, out["predictive"] is its `pooled()` result and, with `groups`,
+    out["predictive_groups"] the list of the G groups' pooled results."""
     import time
     from .sampling import (DualAveragingStepSize, PerChainDualAveragingStepSize, _mean_over_all_chains,
                            _group_sums_over_all_chains, check_groups)
@@ -196,6 +199,8 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
         ctx.switch_partition()
         if path_posterior is not None and it >= n_adapt:
             path_posterior.update()
+        if predictive is not None and it >= n_adapt:
+            predictive.update(seed, it, chain_offset)
         heads[it] = ctx.get_head(n_head)
         if trace_dir is not None:
             from .traces import TraceWriter
@@ -241,6 +246,10 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
         out["group_step_sizes"] = group_eps
     if path_posterior is not None:
         out["path_posterior"] = path_posterior.pooled()
+    if predictive is not None:
+        out["predictive"] = predictive.pooled()
+        if groups is not None:
+            out["predictive_groups"] = [predictive.pooled(np.flatnonzero(groups == g)) for g in range(G)]
     if writer is not None:
         from .traces import save_summary
         writer.flush()

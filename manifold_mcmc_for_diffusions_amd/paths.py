@@ -22,6 +22,28 @@ def merge_moments(a, b):
     return n, ma + d * (nb / n), sa + sb + d * d * (na * nb / n)
 
 
+def merge_ranks(acc):
+    """Under torch.distributed with more than one rank: the ranks' (n, mean, m2) merged in rank order; otherwise `acc`."""
+    try:
+        import torch
+        import torch.distributed as dist
+    except ImportError:
+        return acc
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return acc
+    dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
+    flat = np.concatenate(([float(acc[0])], acc[1].ravel(), acc[2].ravel()))
+    t = torch.from_numpy(flat).to(dev)
+    parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, t)
+    shape, k = acc[1].shape, acc[1].size
+    out = (0, np.zeros(shape), np.zeros(shape))
+    for p in parts:
+        p = p.cpu().numpy()
+        out = merge_moments(out, (int(round(p[0])), p[1:1 + k].reshape(shape), p[1 + k:].reshape(shape)))
+    return out
+
+
 class PathPosterior:
     def __init__(self, ctx, stride=1):
         self.ctx, self.stride = ctx, int(stride)
@@ -70,31 +92,10 @@ class PathPosterior:
         acc = (0, np.zeros_like(mean[0]), np.zeros_like(m2[0]))
         for c in range(len(n)):
             acc = merge_moments(acc, (int(n[c]), mean[c], m2[c]))
-        acc = self._merge_ranks(acc)
+        acc = merge_ranks(acc)
         nn = acc[0]
         var = acc[2] / (nn - 1) if nn > 1 else np.full_like(acc[2], np.nan)
         return dict(n=nn, mean=acc[1], var=var, sd=np.sqrt(var), m2=acc[2])
-
-    @staticmethod
-    def _merge_ranks(acc):
-        try:
-            import torch
-            import torch.distributed as dist
-        except ImportError:
-            return acc
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-            return acc
-        dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
-        flat = np.concatenate(([float(acc[0])], acc[1].ravel(), acc[2].ravel()))
-        t = torch.from_numpy(flat).to(dev)
-        parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
-        dist.all_gather(parts, t)
-        shape, k = acc[1].shape, acc[1].size
-        out = (0, np.zeros(shape), np.zeros(shape))
-        for p in parts:
-            p = p.cpu().numpy()
-            out = merge_moments(out, (int(round(p[0])), p[1:1 + k].reshape(shape), p[1 + k:].reshape(shape)))
-        return out
 
     def save(self, directory):
         """`path_posterior.npz` in `directory`: times, per-chain n and means, pooled n, mean and sd."""
@@ -104,4 +105,149 @@ class PathPosterior:
         path = os.path.join(directory, "path_posterior.npz")
         np.savez(path, times=self.times, stride=self.stride, n=n, chain_mean=mean, pooled_n=pool["n"], mean=pool["mean"],
                  sd=pool["sd"])
+        return path
+
+
+def sum_ranks(a):
+    """Under torch.distributed with more than one rank: the ranks' integer arrays added up; otherwise `a`."""
+    try:
+        import torch
+        import torch.distributed as dist
+    except ImportError:
+        return a
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return a
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to("cuda" if dist.get_backend() == "nccl" else "cpu")
+    dist.all_reduce(t)
+    return t.cpu().numpy()
+
+
+class PredictivePosterior:
+    """Posterior predictive of the model, simulated on the device (chmc_predict_device, include/chmc.h): every `update` draws
+    `n_rep` replicate futures of each chain's current state over `horizon` observation intervals -- origin "end": beyond
+    the last observation (a forecast); "start": from x_0 (replicated data; horizon = T and stride = S give data sets for a
+    posterior predictive check) -- and folds them into running moments per (chain, point, channel) and, with `levels`, into
+    counts of y_rep <= level.  Channels: the X state components, obs_func(x), y_rep = obs_func(x) + sigma eps."""
+
+    def __init__(self, ctx, horizon, stride=None, n_rep=64, origin="end", levels=None, n_keep=0):
+        if origin not in ("end", "start"):
+            raise ValueError('origin must be "end" (forecast) or "start" (replication)')
+        self.ctx, self.horizon, self.n_rep, self.n_keep = ctx, int(horizon), int(n_rep), int(n_keep)
+        self.stride = ctx.S if stride is None else int(stride)
+        self.origin = 0 if origin == "end" else 1
+        if not 1 <= self.n_rep <= 65536 or not 0 <= self.n_keep <= self.n_rep:
+            raise ValueError("need 1 <= n_rep <= 65536 and 0 <= n_keep <= n_rep")
+        self.levels = None if levels is None else np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+        if self.levels is not None and (len(self.levels) == 0 or not (np.diff(self.levels) > 0).all()):
+            raise ValueError("levels must be a non-empty increasing sequence")
+        self.NPF, self.times = ctx.predict_points(self.horizon, self.stride, self.origin)
+        self.XC = ctx.X + 2
+        B, nl = ctx.B, 0 if self.levels is None else len(self.levels)
+        f64 = dict(mean=(B, self.NPF, self.XC), m2=(B, self.NPF, self.XC))
+        i64 = dict(n=(B,))
+        if self.n_keep:
+            f64["paths"] = (B, self.n_keep, self.NPF, self.XC)
+        if nl:
+            i64["cdf"] = (B, self.NPF, nl)
+        if ctx.L.chmc_backend() == b"hip:gfx950":  # torch-ROCm tensors; the library works on their pointers
+            import torch
+            dev = torch.device("cuda", ctx.device)
+            self._buf = {k: torch.zeros(s, dtype=torch.float64, device=dev) for k, s in f64.items()}
+            self._buf.update({k: torch.zeros(s, dtype=torch.int64, device=dev) for k, s in i64.items()})
+            torch.cuda.synchronize(dev)
+            self._ptr = lambda k: self._buf[k].data_ptr() if k in self._buf else None
+            self._host = lambda k: self._buf[k].cpu().numpy()
+        else:  # the library's "device" is host memory (the emulation build of the tests)
+            self._buf = {k: np.zeros(s) for k, s in f64.items()}
+            self._buf.update({k: np.zeros(s, dtype=np.int64) for k, s in i64.items()})
+            self._ptr = lambda k: self._buf[k].ctypes.data if k in self._buf else None
+            self._host = lambda k: self._buf[k].copy()
+
+    def update(self, seed, draw, chain_offset=0, mask=None):
+        """n_rep replicates of every chain's current state (chains with mask[c] != 0; None: all), keyed by (seed, draw,
+        chain_offset + c): a chain's replicates do not depend on how the chains are sharded."""
+        self.ctx.predict_device(seed, draw, chain_offset, self.horizon, self.stride, self.origin, self.n_rep, self._ptr("n"),
+                                self._ptr("mean"), self._ptr("m2"), mask=mask, levels=self.levels,
+                                cdf_dev_ptr=self._ptr("cdf"), paths_dev_ptr=self._ptr("paths"), n_keep=self.n_keep)
+
+    def last_paths(self):
+        """[B, n_keep, NPF, X + 2]: the first n_keep replicates of the last update."""
+        if not self.n_keep:
+            raise ValueError("no paths are kept (n_keep = 0)")
+        return self._host("paths")
+
+    def moments(self):
+        """n [B] (replicate paths), mean, m2 [B, NPF, X + 2] as they stand on the device."""
+        return self._host("n"), self._host("mean"), self._host("m2")
+
+    def counts(self):
+        """[B, NPF, n_levels]: per chain, how many y_rep were at or below each level."""
+        if self.levels is None:
+            raise ValueError("no CDF levels were given")
+        return self._host("cdf")
+
+    def per_chain(self):
+        """n [B], mean, var [B, NPF, X + 2]; var = m2 / (n - 1), NaN for chains with fewer than two replicates."""
+        n, mean, m2 = self.moments()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            var = m2 / np.where(n > 1, n - 1, np.nan)[:, None, None]
+        return n, mean, var
+
+    def _pool(self, chains):
+        n, mean, m2 = self.moments()
+        acc = (0, np.zeros_like(mean[0]), np.zeros_like(m2[0]))
+        for c in chains:
+            acc = merge_moments(acc, (int(n[c]), mean[c], m2[c]))
+        return acc
+
+    def pooled(self, chains=None, across_ranks=True):
+        """All replicates of the chains (None: all) as one sample: merged pairwise in chain order and, under
+        torch.distributed, over the ranks in rank order.  dict(n, mean, var, sd, m2) [NPF, X + 2], and with levels cdf
+        [NPF, n_levels] = pooled counts / n."""
+        chains = range(self.ctx.B) if chains is None else list(chains)
+        acc = self._pool(chains)
+        if across_ranks:
+            acc = merge_ranks(acc)
+        nn = acc[0]
+        var = acc[2] / (nn - 1) if nn > 1 else np.full_like(acc[2], np.nan)
+        out = dict(n=nn, mean=acc[1], var=var, sd=np.sqrt(var), m2=acc[2])
+        if self.levels is not None:
+            cnt = self.counts()[list(chains)].sum(0)
+            if across_ranks:
+                cnt = sum_ranks(cnt)
+            out["cdf"] = cnt / nn if nn else np.full(cnt.shape, np.nan)
+        return out
+
+    def cdf(self):
+        """[NPF, n_levels]: the pooled predictive CDF of y_rep at the levels."""
+        if self.levels is None:
+            raise ValueError("no CDF levels were given")
+        return self.pooled()["cdf"]
+
+    def quantiles(self, probs, cdf=None):
+        """[NPF, len(probs)]: the pooled CDF inverted by linear interpolation over the levels; NaN where a probability lies
+        outside the CDF's range over the levels."""
+        F = self.cdf() if cdf is None else np.asarray(cdf)
+        probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        out = np.full((F.shape[0], len(probs)), np.nan)
+        for p in range(F.shape[0]):
+            for i, pr in enumerate(probs):
+                k = int(np.searchsorted(F[p], pr, side="left"))  # first level with F >= pr
+                if k == 0:
+                    out[p, i] = self.levels[0] if F[p, 0] == pr else np.nan
+                elif k < len(self.levels):
+                    f0, f1 = F[p, k - 1], F[p, k]
+                    out[p, i] = self.levels[k - 1] + (pr - f0) / (f1 - f0) * (self.levels[k] - self.levels[k - 1])
+        return out
+
+    def save(self, directory):
+        """`predictive.npz` in `directory`: times, per-chain n and means, pooled n, mean and sd, and with levels the levels and
+        the pooled CDF."""
+        os.makedirs(directory, exist_ok=True)
+        n, mean, _ = self.per_chain()
+        pool = self.pooled()
+        extra = {} if self.levels is None else dict(levels=self.levels, cdf=pool["cdf"])
+        path = os.path.join(directory, "predictive.npz")
+        np.savez(path, times=self.times, horizon=self.horizon, stride=self.stride, origin=self.origin, n_rep=self.n_rep, n=n,
+                 chain_mean=mean, pooled_n=pool["n"], mean=pool["mean"], sd=pool["sd"], **extra)
         return path

@@ -111,7 +111,7 @@ def check_groups(groups, n_groups, num_chains):
 def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_adapt=0, solver=None, rng=None,
                        n_head=6, callback=None, trace_dir=None, trace_func=None, total_chains=None,
                        jitter_length=False, metric_adapter=None, metric_window=0.75, metric_skip=0.25,
-                       path_posterior=None, groups=None, n_groups=None, metric_per_group=False):
+                       path_posterior=None, groups=None, n_groups=None, metric_per_group=False, predictive=None):
     """Runs n_iter transitions on all chains of `ctx`; returns traces of the first `n_head` position components
     ([n_iter, B, n_head]), accept statistics and the step size used.  Directions are sampled per chain and
     transition (forward / backward in time), failed trajectories are rejected.
@@ -142,7 +142,10 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     raises ValueError --
     metric_per_group: unless this is set.  The adapter then produces one M_0 per group from the statistics of that group's
     chains over all ranks (`finalize_groups`), in the same window; they are installed with `ctx.set_metric(M, groups=...)`,
-    every group's dual averaging restarts from that group's current step size, and out["metric_M_0"] is [G, U, U]."""
+    every group's dual averaging restarts from that group's current step size, and out["metric_M_0"] is [G, U, U].
+    predictive: a `paths.PredictivePosterior` of `ctx`; after warm-up every state (after the partition switch) gets
+    `predictive.update(seed, it, chain_offset)`, out["predictive"] is its `pooled()` result and, with `groups`,
+    out["predictive_groups"] the list of the G groups' pooled results."""
     if metric_per_group and (groups is None or metric_adapter is None):
         raise ValueError("metric_per_group needs groups and a metric_adapter")
     group_metrics = None
@@ -216,6 +219,8 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
         ctx.switch_partition()
         if path_posterior is not None and it >= n_adapt:
             path_posterior.update()
+        if predictive is not None and it >= n_adapt:
+            predictive.update(seed, it, chain_offset)
         heads[it] = ctx.get_head(n_head)
         if trace_dir is not None:
             vals = {k: np.asarray(v) for k, v in trace_func(heads[it], ctx.hamiltonian()[:, 0]).items()}
@@ -260,6 +265,10 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
         out["group_accept_stat"] = group_acc_hist
     if path_posterior is not None:
         out["path_posterior"] = path_posterior.pooled()
+    if predictive is not None:
+        out["predictive"] = predictive.pooled()
+        if groups is not None:
+            out["predictive_groups"] = [predictive.pooled(np.flatnonzero(groups == g)) for g in range(G)]
     if n_metric and metric_per_group:
         out["metric_M_0"] = group_metrics
     elif n_metric:
