@@ -68,14 +68,14 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   long long diag[16] = {0};  // launches by kernel family: [0] k_gram_rows_mfma, [1] k_gram_rows, [2] k_retract_chain, [3] k_traj_chain,
                               // [4] k_newton_fsm_wave, [5] KNewtonFactor (blocks of at most 8 rows), [6] rounds whose forward scan
                               // served two problems (one k_fwd_scan<.., PAIR> launch), [7] forward-scan launches of the
-                              // lock-step Newton loops, [8] rounds enqueued by them, per problem, [9] rounds of a paired loop
-                              // whose passes behind the scan served two problems as well (KernelPlan::pair_passes: interval
+                              // lock-step Newton loop (run_lockstep), [8] rounds it enqueued, per problem, [9] rounds of a paired
+                              // call whose passes behind the scan served two problems as well (KernelPlan::pair_passes: interval
                               // sums, combine, solve and J^T lambda update one launch each; a subset of [6]), [10] launches of
                               // the time-parallel path scan, [11] of the sequential one (KPath), [12] of the predictive wave
                               // kernel, [13] of its functor form (KPredict)
-  // Paired retractions (KernelPlan::pair_retractions): the second problem of run_projection_pair -- the forward retraction of
-  // the NEXT step -- works in a Work of its own: every array a round's kernels, KNewtonBegin, KCheck or KNewtonEnd write
-  // (pair_alloc), everything they only read shared with `w`.  Whole batch only, allocated on first use.
+  // Paired retractions (KernelPlan::pair_retractions): the second problem of a paired run_lockstep call -- the forward
+  // retraction of the NEXT step -- works in a Work of its own: every array a round's kernels, KNewtonBegin, KCheck or KNewtonEnd
+  // write (pair_alloc), everything they only read shared with `w`.  Whole batch only, allocated on first use.
   Work pw{};
   int* d_itf_next = nullptr;  // [B] its iteration counts: the next step's iters_fwd
   bool have_pair = false;
@@ -89,7 +89,7 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   int comm_rank = 0, comm_world = 1;
   int last_n_inner = 1;
   int proj_rounds[2] = {0, 0}, proj_stable[2] = {0, 0};  // rounds the last forward / reverse retraction needed; how often in a row
-                                                          // (by problem, whichever loop it ran in)
+                                                          // (by a problem's direction, alone or paired; half-batches leave it alone)
   int num_cus = 256;                            // compute units of the device (per-chain kernels: up to 2 chains per CU)
   std::vector<double> last_dt;     // last uploaded step sizes
   std::vector<int> last_active;
@@ -524,13 +524,131 @@ static void iteration_after_scan_pair(chmc_ctx* c, int prev, int qsel, const Wor
   c->diag[9]++;
 }
 
-// Newton / quasi-Newton loop (:999-1135), every chain of the batch in lock step.  Leaves per-chain iters / err / ndq / nstat
-// in the work arrays.
-// views == nullptr: the loop of the active view (whole batch) on the current stream.  Otherwise the loops of the two
-// half-batches advance in lock step on the host, each on its own stream: iteration k of half 0 is enqueued, then
-// iteration k of half 1, then the read-backs are examined.
-// count_dir: -1 none, 0 / 1: add every chain's iteration count of this loop to the step's forward / reverse counter
-// (d_itf / d_itb; KAddIters)
+// The solver of a retraction as the entry points receive it (include/chmc.h)
+struct Solver {
+  int newton;  // 1: Newton, 0: quasi-Newton
+  double ctol, ptol, dtol;
+  int max_iters;
+};
+
+// One set of chains in the lock-step loop below: the whole batch, a half-batch, or one of two paired retractions.
+struct Problem {
+  const ViewSave* view = nullptr;  // a half-batch: set_half(c, *view, half) makes it the active view, with its stream and its
+  int half = 0;                    // n_active slots
+  const Work* work = nullptr;      // a paired problem: this Work becomes c->w
+  int* iters = nullptr;            // where a chain's iteration count is added when its loop ends (KCheck, KNewtonEnd; KAddIters):
+  int count_dir = -1;              // this array, or else the ACTIVE view's d_itf (0) / d_itb (1); -1: nowhere
+  int dir = -1;                    // its index into proj_rounds / proj_stable (0 forward, 1 reverse); -1: never predicts
+};
+
+// Newton / quasi-Newton loop (:999-1135) of n = 1 or 2 problems, every chain of a problem in lock step, the problems in lock
+// step on the host.  Leaves per-chain iters / err / ndq / nstat in each problem's work arrays.
+//   one problem: the active view (whole batch) on the current stream;
+//   two half-batch views: parts of one batch, each on its own stream (chmc_leapfrog_step with two halves);
+//   two paired problems (`mergeable`): the reverse retraction of step i on c->w and the forward retraction of step i + 1 on
+//     c->pw (its iterate pw.qb holds the forward-flowed point, KPairFlow), on the one stream.  Both are loops against the
+//     proposal slot's point (prev = 1) on an iterate in a work array (qsel = 1), so one forward scan serves both.
+// Round `it`, in this order:
+//   1. every problem whose prediction is due (below) waits for its count of round it - 1 and stops if nobody is left;
+//   2. mergeable and both still iterating: ONE forward scan for both (iteration_scan_pair) and, where the plan has pair_passes
+//      and the loop is Newton's, sweep, solve and update one launch per pass for both (iteration_after_scan_pair);
+//   3. per problem still iterating, in index order: its own scan and passes unless 2. served it, then its check (KCheck),
+//      which from round 1 on publishes the count of chains still iterating to the problem's pinned poll slot 2 i + (it & 1)
+//      from its last workgroup (no copy packet behind it; A/B on one box, three interleaved runs each: configs[1]
+//      46.3-46.8 k -> 46.7-47.1 k steps/s, SIR unchanged).  KCheck also adds a finished loop's iteration count to the step's
+//      counter and clears the next round's counter: no memset between the rounds;
+//   4. per problem, the count of round it - 1 is examined while the device runs round it.
+// Every kernel of a round is masked per chain (work.nw), so a round enqueued for chains that have all finished is a handful
+// of empty launches.  The host therefore never waits for the count of round `it` before round `it + 1` is queued.  (Waiting
+// first costs a 30 us stream bubble per round.)  The first count examined is that of the second round: no chain satisfies the
+// position tolerance after one update of an h2-flowed point.
+// Speculation has a price when the batch is regular: the round enqueued behind the last real one is empty (six launches).
+// When the last few retractions of a problem's direction all ended after the same number of rounds (FitzHugh-Nagumo at
+// configs[1]: always 4), the host does not speculate at that point: it waits for that round's count first and stops if nobody
+// is left (one host wake-up instead of an empty round: the same 30 us, but 12 launches fewer per step and the launched rounds
+// equal the rounds that had work).  Irregular batches (SIR) keep speculating; half-batches never predict and leave
+// proj_rounds / proj_stable alone.  A predicting problem that ends with fewer than `expect` rounds records `expect`, whichever
+// read-back ended it: the one-batch loop's rule, under which every recorded benchmark ran, so a paired problem is enqueued for
+// exactly the rounds a loop of its own would have been.  (Whether recording the shorter count is the better rule is a
+// separate question.)
+// Counters: diag[8] counts enqueued rounds per problem; counters[6] a round that had work, once per paired problem but once
+// for a batch or its two halves.
+static void run_lockstep(chmc_ctx* c, const Solver& s, int prev, int qsel, const Problem* pr, int n, bool mergeable) {
+  const Sys& sy = c->sy;
+  auto enter = [&](int i) {
+    if (pr[i].view) set_half(c, *pr[i].view, pr[i].half);
+    if (pr[i].work) c->w = *pr[i].work;
+  };
+  // (read at every use: d_itf / d_itb are those of the half-batch view that is active then)
+  auto iters_dst = [&](int i) {
+    const int dir = pr[i].count_dir;
+    return pr[i].iters ? pr[i].iters : dir < 0 ? nullptr : (dir ? c->d_itb : c->d_itf);
+  };
+  const bool one_batch = !mergeable;  // the problems are parts of one batch: a round counts once
+  bool done[2] = {true, true}, predict[2] = {false, false};
+  int rounds_done[2] = {0, 0};
+  for (int i = 0; i < n; ++i) {
+    enter(i);
+    if (sy.B > 0) launch(KNewtonBegin{c->w}, sy.B);
+    done[i] = sy.B <= 0;
+    predict[i] = pr[i].dir >= 0 && c->proj_stable[pr[i].dir] >= 3 && c->proj_rounds[pr[i].dir] >= 2;
+  }
+  // Time-parallel scans with one block per chain do not wait for a chain they cannot settle within a few sweeps: the chain
+  // sits the round out (mask 2, k_fwd_par) and its scan goes on in the next round's launch.  Rounds are therefore not
+  // iterations: the loop gets up to 64 / CHMC_PAR_MAXS_ROUND + 1 rounds per iteration (KCheck enforces max_iters per chain).
+  const bool carry = c->plan.fwd == FwdPar && sy.K == 1;
+  const int max_rounds = carry ? 12 * (s.max_iters + 1) : s.max_iters;
+  for (int it = 0; it < max_rounds && !(done[0] && done[1]); ++it) {
+    for (int i = 0; i < n; ++i)  // (the count of round it - 1 was requested in that round)
+      if (!done[i] && predict[i] && it >= c->proj_rounds[pr[i].dir] && poll_end(2 * i + ((it - 1) & 1)) == 0) done[i] = true;
+    if (done[0] && done[1]) break;
+    c->round = it;
+    const bool both = mergeable && !done[0] && !done[1];
+    const bool merged = both && s.newton && c->plan.pair_passes;
+    if (both) {
+      enter(0);
+      iteration_scan_pair(c, s.newton, prev, qsel, *pr[1].work);
+      if (merged) iteration_after_scan_pair(c, prev, qsel, *pr[1].work);
+    }
+    int worked = 0;
+    for (int i = 0; i < n; ++i) {
+      if (done[i]) continue;
+      enter(i);
+      // (first round: the state's own trajectory is the scan's guess; later ones: the previous iterate's)
+      if (!both) iteration_scan(c, s.newton, prev, qsel, it == 0 ? 2 : 1, 1);
+      if (!merged) iteration_after_scan(c, s.newton, prev, qsel);
+      const KCheck chk{c->w, s.ctol, s.ptol, s.dtol, s.max_iters, sy.B, iters_dst(i), it & 3};
+      if (it >= 1) launch_publish(chk, sy.B, c->w.n_active + (it & 3), 2 * i + (it & 1));
+      else launch(chk, sy.B);
+      c->diag[8]++;
+      if (it == 0) worked++;
+    }
+    for (int i = 0; i < n && it >= 1; ++i) {
+      if (done[i]) continue;
+      if (it >= 2 && poll_end(2 * i + ((it - 1) & 1)) == 0) {  // round it - 1 left no chain active: round it was empty
+        done[i] = true;  // (its pending read-back lands before any later one of the same stream: no need to wait for it)
+        continue;
+      }
+      worked++;
+      rounds_done[i] = it + 1;
+      if (it + 1 >= max_rounds) poll_end(2 * i + (it & 1));  // drain the last read-back before the slots are reused
+    }
+    c->counters[6] += one_batch ? worked > 0 : worked;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (pr[i].dir >= 0) {
+      int& expect = c->proj_rounds[pr[i].dir];
+      int& stable = c->proj_stable[pr[i].dir];
+      if (predict[i] && done[i] && rounds_done[i] < expect) rounds_done[i] = expect;
+      stable = rounds_done[i] == expect ? stable + 1 : 0;
+      expect = rounds_done[i];
+    }
+    enter(i);  // a chain the host left in the loop is a failure, never a silent success
+    if (sy.B > 0) launch(KNewtonEnd{c->w, iters_dst(i)}, sy.B);
+  }
+  c->round = 0;
+}
+
 // One 16-row block per chain on the compact rows (the SIR single-block layout): the whole Newton retraction of a chain in one
 // launch, one workgroup per chain (k_retract_chain, chmc_retract.h) -- no rounds, no read-backs, every chain iterates exactly
 // as long as it needs.  The batched path of these layouts does the same per-chain arithmetic bit for bit (k_fwd_par with the
@@ -547,104 +665,24 @@ static int traj_waves(const chmc_ctx* c, int n_inner, int newton) {
   const bool eligible = part_plan(c).traj_chain && chain_kernel_model(c) && n_inner == 1 && c->mom_tangent && c->halves == 1;
   return chain_kernel_waves(c->plan, eligible, c->sy.B, c->num_cus, newton != 0, false);
 }
-static int run_projection(chmc_ctx* c, int newton, int prev, int qsel, double ctol, double ptol, double dtol,
-                          int max_iters, const ViewSave* views = nullptr, int count_dir = -1) {
+// One retraction of the active view (views == nullptr) or of its two half-batches: the per-chain kernel where the plan has
+// one, else the lock-step loop.  count_dir: Problem::count_dir.
+static void run_projection(chmc_ctx* c, const Solver& s, int prev, int qsel, const ViewSave* views = nullptr,
+                           int count_dir = -1) {
   const Sys& sy = c->sy;
-  // (read at every use: d_itf / d_itb are those of the half-batch view that is active then)
-  auto iters_dst = [&] { return count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf); };
-  if (const int waves = retract_waves(c, newton, views)) {
+  if (const int waves = retract_waves(c, s.newton, views)) {
+    int* const iters_dst = count_dir < 0 ? nullptr : (count_dir ? c->d_itb : c->d_itf);
     dispatch(c, [&](auto inst) {
-      retract_chain<typename decltype(inst)::M, decltype(inst)::RM>(waves, (long)sy.B, sy, c->sl, c->w, prev, qsel, ctol, ptol,
-                                                                     dtol, max_iters, iters_dst());
+      retract_chain<typename decltype(inst)::M, decltype(inst)::RM>(waves, (long)sy.B, sy, c->sl, c->w, prev, qsel, s.ctol, s.ptol,
+                                                                     s.dtol, s.max_iters, iters_dst);
     });
     c->counters[6]++;  // (one launch that lasts as long as its slowest chain iterates)
     c->diag[2]++;
-    return 0;
+    return;
   }
-  const int nh = views ? 2 : 1;
-  auto enter = [&](int h) {
-    if (views) set_half(c, *views, h);
-  };
-  for (int h = 0; h < nh; ++h) {
-    enter(h);
-    if (sy.B > 0) launch(KNewtonBegin{c->w}, sy.B);
-  }
-  int fwd_guess = 2;  // first iteration: the state's own trajectory is the guess; later ones: the previous iterate's
-  // Time-parallel scans with one block per chain do not wait for a chain they cannot settle within a few sweeps: the chain
-  // sits the round out (mask 2, k_fwd_par) and its scan goes on in the next round's launch.  Rounds are therefore not
-  // iterations: the loop gets up to 64 / CHMC_PAR_MAXS_ROUND + 1 rounds per iteration (KCheck enforces max_iters per chain).
-  const bool carry = c->plan.fwd == FwdPar && sy.K == 1;
-  const int max_rounds = carry ? 12 * (max_iters + 1) : max_iters;
-  auto iteration = [&](int poll_slot) {  // poll_slot >= 0: the round's count of active chains goes to that pinned slot
-    iteration_scan(c, newton, prev, qsel, fwd_guess, 1);
-    iteration_after_scan(c, newton, prev, qsel);
-    // (KCheck also adds a finished loop's iteration count to the step's counter -- KAddIters folded in -- and clears the
-    // next round's counter: no memset between the rounds)
-    const KCheck chk{c->w, ctol, ptol, dtol, max_iters, sy.B, iters_dst(), c->round & 3};
-    // (the count reaches the pinned poll slot from the check's last workgroup: no copy packet behind it; A/B on one box,
-    // three interleaved runs each: configs[1] 46.3-46.8 k -> 46.7-47.1 k steps/s, SIR unchanged)
-    if (poll_slot >= 0) launch_publish(chk, sy.B, c->w.n_active + (c->round & 3), poll_slot);
-    else launch(chk, sy.B);
-  };
-  // Every kernel of an iteration is masked per chain (work.nw), so an iteration enqueued for chains that have all
-  // finished is a handful of empty launches.  The host therefore never waits for the active count of iteration
-  // `it` before iteration `it + 1` is queued: the count is copied back asynchronously and examined while the device
-  // already runs the next iteration.  (Waiting first costs a 30 us stream bubble per iteration.)  The first
-  // read-back is that of the second iteration: no chain satisfies the position tolerance after one update of an
-  // h2-flowed point.
-  bool done[2] = {false, nh == 1};
-  for (int h = 0; h < nh; ++h) {
-    enter(h);
-    if (sy.B <= 0) done[h] = true;
-  }
-  // Speculation has a price when the batch is regular: the round enqueued behind the last real one is empty (six launches).
-  // When the last few retractions of this direction all ended after the same number of rounds (FitzHugh-Nagumo at
-  // configs[1]: always 4), the host does not speculate at that point: it waits for that round's count first and stops if
-  // nobody is left (one host wake-up instead of an empty round: the same 30 us, but 12 launches fewer per step and the
-  // launched rounds equal the rounds that had work).  Irregular batches (SIR) keep speculating.
-  int& expect = c->proj_rounds[prev & 1];
-  int& stable = c->proj_stable[prev & 1];
-  const bool predict = !views && stable >= 3 && expect >= 2;
-  int rounds_done = 0;
-  for (int it = 0; it < max_rounds && !(done[0] && done[1]); ++it) {
-    if (predict && it >= expect && poll_end((it - 1) & 1) == 0) {  // (the count of round it - 1 was requested in that round)
-      done[0] = true;
-      break;
-    }
-    for (int h = 0; h < nh; ++h) {
-      if (done[h]) continue;
-      enter(h);
-      fwd_guess = it == 0 ? 2 : 1;
-      c->round = it;
-      iteration(it >= 1 ? 2 * h + (it & 1) : -1);
-      c->diag[8]++;
-    }
-    c->counters[6]++;
-    if (it == 0) continue;
-    bool all_empty = true;
-    for (int h = 0; h < nh; ++h) {
-      if (done[h]) continue;
-      if (it >= 2 && poll_end(2 * h + ((it - 1) & 1)) == 0) {  // iteration it - 1 left no chain active: iteration it was empty
-        done[h] = true;  // (its pending read-back lands before any later one of the same stream: no need to wait for it)
-        continue;
-      }
-      all_empty = false;
-      if (it + 1 >= max_rounds) poll_end(2 * h + (it & 1));  // drain the last read-back before the slots are reused
-    }
-    if (all_empty) c->counters[6]--;
-    else rounds_done = it + 1;
-  }
-  if (!views) {
-    if (predict && done[0] && rounds_done < expect) rounds_done = expect;  // (stopped by the prediction: `expect` rounds had work)
-    stable = rounds_done == expect ? stable + 1 : 0;
-    expect = rounds_done;
-  }
-  for (int h = 0; h < nh; ++h) {  // a chain the host left in the loop is a failure, never a silent success
-    enter(h);
-    if (sy.B > 0) launch(KNewtonEnd{c->w, iters_dst()}, sy.B);
-  }
-  c->round = 0;
-  return 0;
+  Problem pr[2];
+  for (int h = 0; h < 2; ++h) pr[h].view = views, pr[h].half = h, pr[h].count_dir = count_dir, pr[h].dir = views ? -1 : prev & 1;
+  run_lockstep(c, s, prev, qsel, pr, views ? 2 : 1, false);
 }
 
 // The arrays of the second problem's Work (chmc_ctx::pw), sized as chmc_layout.h sizes their counterparts.  Not in that list:
@@ -676,79 +714,16 @@ static void pair_alloc(chmc_ctx* c) {
   c->have_pair = true;
 }
 
-// The reverse retraction of step i (problem 0: run_projection(.., 1, 1, .., 1) exactly, on c->w) and the forward retraction of
-// step i + 1 (problem 1, on c->pw: its iterate pw.qb holds the forward-flowed point, KPairFlow) in ONE lock-step loop.  Both are
-// Newton loops against the proposal slot's point (prev = 1) on an iterate in a work array (qsel = 1).  A round is one forward
-// scan for both problems (iteration_scan_pair; the single form once one of them has finished), then sweep, solve and update
-// -- one launch per pass for both where the plan has pair_passes and both problems still iterate
-// (iteration_after_scan_pair), otherwise each problem's own -- and each problem's own check, on the one stream.  Each
-// problem keeps the read-backs, the speculation and the predicted stop of a loop of its own (run_projection), counted per
-// problem: poll slots 2 p + parity, proj_rounds / proj_stable of its direction -- so a problem is enqueued for exactly the rounds its own loop would have been, and counters[6] counts a round
-// once per problem that had work.
-static int run_projection_pair(chmc_ctx* c, int newton, double ctol, double ptol, double dtol, int max_iters) {
-  const Sys& sy = c->sy;
-  const int prev = 1, qsel = 1;
+// The reverse retraction of step i (problem 0: that of run_projection(.., 1, 1, nullptr, 1), on c->w) beside the forward
+// retraction of step i + 1 (problem 1, on c->pw, counting into d_itf_next) as the two mergeable problems of run_lockstep.
+// Returns on problem 0's Work.
+static void run_projection_pair(chmc_ctx* c, const Solver& s) {
   const Work wk[2] = {c->w, c->pw};
-  int* const iters_dst[2] = {c->d_itb, c->d_itf_next};
-  const int dir[2] = {1, 0};  // problem 0 is a reverse retraction, problem 1 a forward one
-  auto enter = [&](int p) { c->w = wk[p]; };
-  bool done[2], predict[2], stopped[2] = {false, false};
-  int rounds_done[2] = {0, 0};
-  for (int p = 0; p < 2; ++p) {
-    enter(p);
-    launch(KNewtonBegin{c->w}, sy.B);
-    done[p] = sy.B <= 0;
-    predict[p] = c->proj_stable[dir[p]] >= 3 && c->proj_rounds[dir[p]] >= 2;
-  }
-  for (int it = 0; it < max_iters && !(done[0] && done[1]); ++it) {
-    for (int p = 0; p < 2; ++p)  // (the count of round it - 1 was requested in that round)
-      if (!done[p] && predict[p] && it >= c->proj_rounds[dir[p]] && poll_end(2 * p + ((it - 1) & 1)) == 0)
-        done[p] = stopped[p] = true;
-    if (done[0] && done[1]) break;
-    c->round = it;
-    const bool both = !done[0] && !done[1];
-    const bool merged = both && newton && c->plan.pair_passes;  // every pass behind the scan once for both as well
-    if (both) {
-      enter(0);
-      iteration_scan_pair(c, newton, prev, qsel, wk[1]);
-      if (merged) iteration_after_scan_pair(c, prev, qsel, wk[1]);
-    } else {
-      enter(done[0] ? 1 : 0);
-      iteration_scan(c, newton, prev, qsel, it == 0 ? 2 : 1, 1);
-    }
-    for (int p = 0; p < 2; ++p) {
-      if (done[p]) continue;
-      enter(p);
-      if (!merged) iteration_after_scan(c, newton, prev, qsel);
-      const KCheck chk{c->w, ctol, ptol, dtol, max_iters, sy.B, iters_dst[p], it & 3};
-      if (it >= 1) launch_publish(chk, sy.B, c->w.n_active + (it & 3), 2 * p + (it & 1));
-      else launch(chk, sy.B);
-      c->counters[6]++, c->diag[8]++;
-    }
-    if (it == 0) continue;
-    for (int p = 0; p < 2; ++p) {
-      if (done[p]) continue;
-      if (it >= 2 && poll_end(2 * p + ((it - 1) & 1)) == 0) {  // round it - 1 left no chain active: round it was empty
-        done[p] = true;
-        c->counters[6]--;
-        continue;
-      }
-      rounds_done[p] = it + 1;
-      if (it + 1 >= max_iters) poll_end(2 * p + (it & 1));  // drain the last read-back before the slots are reused
-    }
-  }
-  for (int p = 0; p < 2; ++p) {
-    int& expect = c->proj_rounds[dir[p]];
-    int& stable = c->proj_stable[dir[p]];
-    if (stopped[p] && rounds_done[p] < expect) rounds_done[p] = expect;  // (stopped by the prediction: `expect` rounds had work)
-    stable = rounds_done[p] == expect ? stable + 1 : 0;
-    expect = rounds_done[p];
-    enter(p);  // a chain the host left in the loop is a failure, never a silent success
-    if (sy.B > 0) launch(KNewtonEnd{c->w, iters_dst[p]}, sy.B);
-  }
-  enter(0);
-  c->round = 0;
-  return 0;
+  Problem pr[2];
+  pr[0].work = &wk[0], pr[0].count_dir = 1, pr[0].dir = 1;
+  pr[1].work = &wk[1], pr[1].iters = c->d_itf_next, pr[1].dir = 0;
+  run_lockstep(c, s, 1, 1, pr, 2, true);
+  c->w = wk[0];
 }
 
 static int check_ctx(const chmc_ctx* c, const char* fn) {
@@ -1780,7 +1755,7 @@ extern "C" int chmc_project(chmc_ctx* ctx, int newton, const double* q, const do
   ctx->last_dt.clear();                        // the step-size cache of chmc_leapfrog_step is now stale
   begin_all(ctx, ctx->w.err, nullptr);
   launch(KCopyToOther{sy, ctx->sl, ctx->w.vin}, (long)sy.B * sy.Q);
-  run_projection(ctx, newton, 0, 0, ctol, ptol, dtol, max_iters);
+  run_projection(ctx, Solver{newton, ctol, ptol, dtol, max_iters}, 0, 0);
   if (mu_out) {
     launch(KMuFromMove{sy, ctx->sl, ctx->w, ctx->w.vin}, (long)sy.B * sy.Q);
     d2h(mu_out, ctx->w.mu, n);
@@ -1818,7 +1793,7 @@ extern "C" int chmc_gd_project_device(chmc_ctx* ctx, const int* mask, void* q_de
   ctx->last_dt.clear();                                 // the step-size cache of chmc_leapfrog_step is now stale
   begin_all(ctx, ctx->w.err, ctx->d_act);
   launch(KCopyToOther{sy, ctx->sl, (const double*)q_dev}, (long)sy.B * sy.Q);
-  run_projection(ctx, newton, 0, 0, ctol, ptol, dtol, max_iters);
+  run_projection(ctx, Solver{newton, ctol, ptol, dtol, max_iters}, 0, 0);
   std::vector<int> st(sy.B);
   d2h(st.data(), ctx->w.nstat, sizeof(int) * sy.B);
   if (iters) d2h(iters, ctx->w.iters, sizeof(int) * sy.B);
@@ -1855,15 +1830,23 @@ struct KInnerRestore {  // failed chains that had completed inner steps: back to
 // chmc_leapfrog_step in two parts: step_enqueue puts the whole step on the stream (the Newton loops wait for their
 // active-chain counts only), step_finish fetches the per-chain outputs.  `active_dev`: a device-resident mask used
 // instead of the host array (chmc_tree_step: the chains of a trajectory tree that are still running).
-// n_steps_host / n_steps_all / want_n_done: the per-chain trajectory kernel (traj_waves) takes that many steps per chain in
-// the one launch and leaves the steps done in ctx->d_ndone; every other path takes ONE step and ignores them.
-static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, const int* active_dev, int n_inner, int newton,
-                        double ctol, double ptol, double dtol, int max_iters, double rev_tol,
-                        const int* n_steps_host = nullptr, int n_steps_all = 1, bool want_n_done = false,
-                        bool skip_end_kick = false, bool pending_kick = false, bool pair_next = false) {
+struct StepOptions {
+  // the per-chain trajectory kernel (traj_waves) takes that many steps per chain in the one launch and leaves the steps done in
+  // ctx->d_ndone; every other path takes ONE step and ignores them
+  const int* n_steps_host = nullptr;
+  int n_steps_all = 1;
+  bool want_n_done = false;
+  bool skip_end_kick = false;  // the next step of the trajectory applies this step's closing A(dt/2) with its opening one
+  bool pending_kick = false;   // ... and this step owes the one of the step before
+  // the forward retraction of the NEXT step of the trajectory runs beside this step's reverse one (run_projection_pair); that
+  // step then opens by adopting the result instead of flowing and retracting
+  bool pair_next = false;
+};
+static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, const int* active_dev, int n_inner, const Solver& s,
+                        double rev_tol, const StepOptions& opt = StepOptions{}) {
   const Sys& sy = ctx->sy;
-  // pair_next: the forward retraction of the NEXT step of the trajectory runs beside this step's reverse one
-  // (run_projection_pair); that step then opens by adopting the result instead of flowing and retracting
+  const int* const n_steps_host = opt.n_steps_host;
+  const bool pending_kick = opt.pending_kick, pair_next = opt.pair_next;
   const bool adopt = pending_kick && ctx->pair_ready;
   ctx->pair_ready = false;
   if (pair_next) pair_alloc(ctx);
@@ -1893,19 +1876,19 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
     ctx->last_active_null = true;
   }
   if (n_inner > 1) ensure_array(ctx, ctx->d_q0), ensure_array(ctx, ctx->d_p0), ensure_array(ctx, ctx->d_ncommit);
-  if (const int waves = traj_waves(ctx, n_inner, newton)) {
+  if (const int waves = traj_waves(ctx, n_inner, s.newton)) {
     ensure_array(ctx, ctx->d_nsteps), ensure_array(ctx, ctx->d_ndone);
     if (n_steps_host) h2d(ctx->d_nsteps, n_steps_host, sizeof(int) * sy.B);
     begin_all(ctx, d_dt ? ctx->w.err : nullptr, d_active ? ctx->d_act : nullptr, 1.0);
     dev_zero(ctx->d_itf, sizeof(int) * sy.B), dev_zero(ctx->d_itb, sizeof(int) * sy.B);
     dispatch(ctx, [&](auto inst) {
       traj_chain<typename decltype(inst)::M, decltype(inst)::RM>(
-          waves, (long)sy.B, sy, ctx->sl, ctx->w, n_steps_host ? ctx->d_nsteps : nullptr, n_steps_all, ctol, ptol, dtol, max_iters,
-          rev_tol, ctx->d_itf, ctx->d_itb, want_n_done ? ctx->d_ndone : nullptr);
+          waves, (long)sy.B, sy, ctx->sl, ctx->w, n_steps_host ? ctx->d_nsteps : nullptr, opt.n_steps_all, s.ctol, s.ptol, s.dtol,
+          s.max_iters, rev_tol, ctx->d_itf, ctx->d_itb, opt.want_n_done ? ctx->d_ndone : nullptr);
     });
     ctx->rows_fresh = false;
     ctx->diag[3]++;
-    const int ns = n_steps_host ? 1 : n_steps_all;  // (counters: evaluations per chain of a full-length trajectory)
+    const int ns = n_steps_host ? 1 : opt.n_steps_all;  // (counters: evaluations per chain of a full-length trajectory)
     ctx->counters[0] += ns, ctx->counters[1] += ns, ctx->counters[3] += ns, ctx->counters[4] += ns, ctx->counters[6] += 2 * ns;
     return 0;
   }
@@ -1961,7 +1944,7 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
       }
     }
     if (!adopt)
-      run_projection(ctx, newton, 0, 0, ctol, ptol, dtol, max_iters, two ? &full : nullptr, 0);  // retraction onto the manifold
+      run_projection(ctx, s, 0, 0, two ? &full : nullptr, 0);  // retraction onto the manifold
     for (int h = 0; h < nh; ++h) {
       enter(h);
       state_eval_core(ctx, 1, last, 3);  // J, factors, log det at the new point; on the last inner step dh1_dpos as well
@@ -1985,17 +1968,18 @@ static int step_enqueue(chmc_ctx* ctx, const double* dt, const int* active, cons
       }
     }
     if (pair_next) {
-      run_projection_pair(ctx, newton, ctol, ptol, dtol, max_iters);
+      run_projection_pair(ctx, s);
       ctx->pair_ready = true;
-    } else
-    run_projection(ctx, newton, 1, 1, ctol, ptol, dtol, max_iters, two ? &full : nullptr, 1);
+    } else {
+      run_projection(ctx, s, 1, 1, two ? &full : nullptr, 1);
+    }
     for (int h = 0; h < nh; ++h) {
       enter(h);
       launch_colmax(KRevDiff{sy, ctx->sl, ctx->w}, (sy.Q + 1) / 2, sy.B, 8);
       launch(KRevCheck{ctx->w, rev_tol}, sy.B);
       if (last) {
         // A(dt/2) at the new point: the momentum was projected there above, so P(p - dt/2 dh1_dpos) = p - dt/2 pg
-        if (!skip_end_kick) launch_rows(KKickPg{sy, ctx->sl, ctx->w, 1, 0, kick}, sy.Q, sy.B, 8);
+        if (!opt.skip_end_kick) launch_rows(KKickPg{sy, ctx->sl, ctx->w, 1, 0, kick}, sy.Q, sy.B, 8);
         launch(KCommit{ctx->sl, ctx->w}, sy.B);
       } else {
         launch(KCommitInner{ctx->sl, ctx->w, ctx->d_ncommit}, sy.B);
@@ -2057,7 +2041,7 @@ extern "C" int chmc_leapfrog_step(chmc_ctx* ctx, const double* dt, const int* ac
   CHMC_ENTER("chmc_leapfrog_step")
   if (!dt) return fail("chmc_leapfrog_step: dt is required");
   if (n_inner < 1) return fail("chmc_leapfrog_step: n_inner_step must be at least 1");
-  if (step_enqueue(ctx, dt, active, nullptr, n_inner, newton, ctol, ptol, dtol, max_iters, rev_tol)) return -1;
+  if (step_enqueue(ctx, dt, active, nullptr, n_inner, Solver{newton, ctol, ptol, dtol, max_iters}, rev_tol)) return -1;
   step_finish(ctx, active != nullptr, n_inner, status, iters_fwd, iters_bwd, rev_err);
   CHMC_LEAVE("chmc_leapfrog_step")
 }
@@ -2079,6 +2063,7 @@ extern "C" int chmc_leapfrog_steps(chmc_ctx* ctx, const double* dt, const int* a
   if (!n_steps && n_steps_all < 0) return fail("chmc_leapfrog_steps: negative number of steps");
   const Sys& sy = ctx->sy;
   const int B = sy.B;
+  const Solver s{newton, ctol, ptol, dtol, max_iters};
   if (traj_waves(ctx, n_inner, newton)) {
     // one launch: every chain walks its own steps in its own workgroup (k_traj_chain) and stops at its first failed step
     int longest = n_steps_all;
@@ -2086,9 +2071,9 @@ extern "C" int chmc_leapfrog_steps(chmc_ctx* ctx, const double* dt, const int* a
       longest = 0;
       for (int c = 0; c < B; ++c) longest = n_steps[c] > longest ? n_steps[c] : longest;
     }
-    if (step_enqueue(ctx, dt, active, nullptr, n_inner, newton, ctol, ptol, dtol, max_iters, rev_tol, n_steps,
-                     n_steps ? longest : n_steps_all, true))
-      return -1;
+    StepOptions opt;
+    opt.n_steps_host = n_steps, opt.n_steps_all = longest, opt.want_n_done = true;
+    if (step_enqueue(ctx, dt, active, nullptr, n_inner, s, rev_tol, opt)) return -1;
     std::vector<int> nd(B), st(B);
     d2h(nd.data(), ctx->d_ndone, sizeof(int) * B);
     step_finish(ctx, active != nullptr, 1, st.data(), iters_fwd, iters_bwd, rev_err);
@@ -2129,9 +2114,9 @@ extern "C" int chmc_leapfrog_steps(chmc_ctx* ctx, const double* dt, const int* a
     // ... and the forward retraction of step k + 1 runs beside the reverse retraction of step k (KernelPlan::pair_retractions):
     // under the same conditions, where the merged scan launch fits the chip (pair_this_call, chmc_plan.h; the same bits)
     const bool pair = skip && ctx->halves == 1 && pair_this_call(ctx->plan, ctx->plan_in.wave_kernels, B, sy.K, ctx->num_cus);
-    if (step_enqueue(ctx, dt, run.data(), nullptr, n_inner, newton, ctol, ptol, dtol, max_iters, rev_tol, nullptr, 1, false, skip,
-                     pending, pair))
-      return -1;
+    StepOptions opt;
+    opt.skip_end_kick = skip, opt.pending_kick = pending, opt.pair_next = pair;
+    if (step_enqueue(ctx, dt, run.data(), nullptr, n_inner, s, rev_tol, opt)) return -1;
     pending = skip;
     step_finish(ctx, true, n_inner, st.data(), f.data(), b.data(), r1.data());
     for (int c = 0; c < B; ++c) {
@@ -2206,7 +2191,7 @@ extern "C" int chmc_tree_step(chmc_ctx* ctx, const double* dt, int n_inner, int 
   const Sys& sy = ctx->sy;
   TreeState& t = ctx->tree;
   h2d(t.u, u_leaf, sizeof(double) * sy.B);
-  if (step_enqueue(ctx, dt, nullptr, t.run, n_inner, newton, ctol, ptol, dtol, max_iters, rev_tol)) return -1;
+  if (step_enqueue(ctx, dt, nullptr, t.run, n_inner, Solver{newton, ctol, ptol, dtol, max_iters}, rev_tol)) return -1;
   hamiltonian_enqueue(ctx);
   launch(KTreeDecide{t, ctx->w.status, ctx->d_ham, max_delta_h}, sy.B);
   const int ng = rowsum_groups(sy.Q), nacc = 6 * n_check;

@@ -309,10 +309,9 @@ def check_tree_leaf(ctx, case, device, with_metric):
     ctx.set_metric(None)
 
 
-def halves_vs_single_batch(case, monkeypatch, part=0, n_steps=2, newton=True, masked=(), failing=()):
-    """The same leapfrog steps with the step run as ONE batch (CHMC_HALVES=1) and as two overlapped half-batches on two
-    streams (CHMC_HALVES=2).  Chains are independent and every per-chain reduction has a fixed order, so the two runs
-    must agree BITWISE: positions, momenta, statuses, iteration counts, reverse-check distances."""
+def _half_batch_inputs(case, masked, failing):
+    """One start point for every chain, momenta and step sizes of mixed sign per chain; `failing` chains get a step size
+    no retraction survives, `masked` ones are inactive."""
     B = case["B"]
     rng = np.random.default_rng(99)
     p = rng.standard_normal(case["q"].shape)
@@ -322,6 +321,52 @@ def halves_vs_single_batch(case, monkeypatch, part=0, n_steps=2, newton=True, ma
     dts[list(failing)] = 5.0
     act = np.ones(B, dtype=np.int32)
     act[list(masked)] = 0
+    return qq, p, xx, dts, act
+
+
+def rounds_follow_from_iteration_counts(case, monkeypatch, part=0, newton=True, n_steps=3, cap=12):
+    """The lock-step Newton loop (run_lockstep, csrc/chmc_api.inc) enqueues rounds by a fixed protocol, so while no loop
+    predicts -- a fresh context and at most 3 steps: proj_stable < 3 -- the rounds of a step follow from its iteration counts.
+    A problem is the batch (CHMC_HALVES=1) or one of the chain ranges [0, B // 2), [B // 2, B) (CHMC_HALVES=2); with m its
+    largest iteration count in a retraction and `cap` = max_iters it has work in `cap if m >= cap else max(m, 2)` rounds (the
+    first count the host looks at is round 1's) and is enqueued for one speculative round more, up to the cap:
+      newton_rounds (enqueued, per problem) grows by the sum over both retractions and their problems of the second figure,
+      projection_iterations (rounds with work, once per batch) by the sum over both retractions of the largest first figure.
+    Inputs of halves_vs_single_batch with chain 1 masked in the first step and chain 2 failing.  Prints each figure before
+    it asserts; returns the number of (step, mode) pairs checked."""
+    B = case["B"]
+    qq, p, xx, dts, act = _half_batch_inputs(case, masked=(1,), failing=(2,))
+    checked = 0
+    for halves in ("1", "2"):
+        monkeypatch.setenv("CHMC_HALVES", halves)
+        ctx = make_ctx(case)
+        ctx.set_state(qq, p, xx, part)
+        problems = [slice(0, B)] if halves == "1" else [slice(0, B // 2), slice(B // 2, B)]
+        for k in range(n_steps):
+            d0, c0 = ctx.diagnostics()["newton_rounds"], ctx.counters()["projection_iterations"]
+            r = ctx.leapfrog_step(dts, active=act if k == 0 else None, newton=newton, max_iters=cap)
+            enqueued = ctx.diagnostics()["newton_rounds"] - d0
+            counted = ctx.counters()["projection_iterations"] - c0
+            want_enqueued = want_counted = 0
+            for iters in (r["iters_fwd"], r["iters_bwd"]):
+                ms = [int(iters[s].max()) for s in problems]
+                worked = [cap if m >= cap else max(m, 2) for m in ms]
+                want_enqueued += sum(min(w + 1, cap) for w in worked)
+                want_counted += max(worked)
+            print(f"  halves={halves} part={part} step={k} fwd={r['iters_fwd'].tolist()} bwd={r['iters_bwd'].tolist()}: "
+                  f"enqueued {enqueued} (expected {want_enqueued}), counted {counted} (expected {want_counted})")
+            assert enqueued == want_enqueued and counted == want_counted, (halves, part, k)
+            checked += 1
+        assert r["status"][2] > 0
+        ctx.close()
+    return checked
+
+
+def halves_vs_single_batch(case, monkeypatch, part=0, n_steps=2, newton=True, masked=(), failing=()):
+    """The same leapfrog steps with the step run as ONE batch (CHMC_HALVES=1) and as two overlapped half-batches on two
+    streams (CHMC_HALVES=2).  Chains are independent and every per-chain reduction has a fixed order, so the two runs
+    must agree BITWISE: positions, momenta, statuses, iteration counts, reverse-check distances."""
+    qq, p, xx, dts, act = _half_batch_inputs(case, masked, failing)
     out = []
     for halves in ("1", "2"):
         monkeypatch.setenv("CHMC_HALVES", halves)

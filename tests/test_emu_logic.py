@@ -232,6 +232,18 @@ def test_half_batches_equal_one_batch(emu_lib, monkeypatch, model, T, S, R, nois
         halves_vs_single_batch(case, monkeypatch, part=part, newton=newton, masked=(1, 6), failing=(2, 4))
 
 
+@pytest.mark.parametrize("model,T,S,R,noisy,gaussian,newton", [
+    ("fhn", 12, 10, 5, True, False, True), ("fhn", 7, 5, 3, False, True, False)])
+def test_rounds_follow_from_the_iteration_counts(emu_lib, monkeypatch, model, T, S, R, noisy, gaussian, newton):
+    """The one lock-step loop, as one batch and as two half-batches (3 | 4 chains), both partitions: enqueued and counted
+    rounds of every step equal what the protocol gives for the step's iteration counts (quasi-Newton: the halves of the first
+    step need 6 | 9 and 5 | 10 rounds)."""
+    from helpers import rounds_follow_from_iteration_counts
+    case = make_case(model, T, S, R, noisy, B=7, seed=81, gaussian=gaussian)
+    for part in range(2):
+        assert rounds_follow_from_iteration_counts(case, monkeypatch, part=part, newton=newton) == 6
+
+
 def test_half_batches_equal_one_batch_sixteen_row_blocks(emu_lib, monkeypatch):
     """The same with 16-row blocks, K = [2, 3] (SIR, 13 observations per sub-sequence, interval 0.1): the views of every array
     with RM = 16 row slots per block.  (One 16-row block per chain always runs as one batch.)"""

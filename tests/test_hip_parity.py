@@ -673,6 +673,19 @@ def test_half_batches_on_two_streams_equal_one_batch(monkeypatch, model, T, S, R
         halves_vs_single_batch(case, monkeypatch, part=part, newton=newton, masked=(3, 36, 70), failing=(5, 40))
 
 
+@pytest.mark.parametrize("model,T,S,R,noisy,gaussian,newton,B", [
+    ("fhn", 12, 10, 5, True, False, True, 7), ("fhn", 7, 5, 3, False, True, False, 7),
+    ("fhn", 12, 16, 5, True, False, True, 7), ("fhn", 12, 16, 5, True, False, True, 71)])
+def test_rounds_follow_from_the_iteration_counts(monkeypatch, model, T, S, R, noisy, gaussian, newton, B):
+    """The one lock-step loop on the device, as one batch and as two half-batches (3 | 4 and 35 | 36 chains), both partitions:
+    enqueued and counted rounds of every step equal what the protocol gives for the step's iteration counts.  Multi-block
+    layouts: no scan carried over rounds, no per-chain retraction kernel."""
+    from helpers import rounds_follow_from_iteration_counts
+    case = make_case(model, T, S, R, noisy, B=B, seed=81, gaussian=gaussian)
+    for part in range(2):
+        assert rounds_follow_from_iteration_counts(case, monkeypatch, part=part, newton=newton) == 6
+
+
 def test_half_batches_full_size(monkeypatch):
     """The same at BASELINE.json configs[1]'s size (Q = 80106), 130 chains."""
     from helpers import halves_vs_single_batch
