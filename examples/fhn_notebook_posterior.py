@@ -16,6 +16,9 @@ the notebook's linear interpolation; candidates are screened in the same way.
 
 usage: fhn_notebook_posterior.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir] [static|dynamic]
                                  [--init linear-interpolation|gradient-descent] [--path-posterior STRIDE] [--forecast H]
+                                 [--spikes THETA]
+--spikes THETA: the posterior of the number of spikes of the observed component, counted as up-crossings of THETA along the
+latent path of every post-warm-up state (paths.PathEvents on the device, traced like the parameters).
 --forecast H: posterior predictive forecast of the observed component over H observation intervals beyond the last
 observation: 64 replicate futures of every post-warm-up state with fresh driving noise (paths.PredictivePosterior, simulated on
 the device); mean, sd and the 5 / 50 / 95 % points of the predictive CDF are printed per observation time and
@@ -60,7 +63,8 @@ def print_path_posterior(pp, pool, path, y, per_obs, verbose=True):
 
 
 def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=20200710, verbose=True,
-        transition="static", init="linear-interpolation", path_posterior=None, forecast=None):
+        transition="static", init="linear-interpolation", path_posterior=None, forecast=None,
+        spikes=None):
     """forecast: a number of observation intervals beyond the last observation (see the usage text).
     path_posterior: a stride (a divisor of the steps per observation); the posterior moments of the latent path x(t) at every
     stride-th step are accumulated over the main phase and written to `path_posterior.npz` next to the traces."""
@@ -125,6 +129,9 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
         from manifold_mcmc_for_diffusions_amd.paths import PredictivePosterior
         pred = PredictivePosterior(ctx, int(forecast), n_rep=64, levels=np.linspace(-3.0, 3.0, 241))
         extra["predictive"] = pred
+    if spikes is not None:
+        from manifold_mcmc_for_diffusions_amd.paths import PathEvents
+        extra["path_events"] = PathEvents(ctx, ctx.X, [float(spikes)], stride=int(path_posterior or 1), path_posterior=pp)
     t0 = time.time()
     if transition == "dynamic":
         from manifold_mcmc_for_diffusions_amd.dynamic import sample_dynamic_chmc
@@ -146,6 +153,12 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
     el = time.time() - t0
     if pp is not None:
         print_path_posterior(pp, res["path_posterior"], pp.save(tmp), d["y"], d["S"] // pp.stride, verbose)
+    if spikes is not None and verbose:
+        sm, ev = res["path_events_summary"], res["path_events"]
+        counts = np.bincount(ev[:, :, 5].astype(np.int64).ravel())
+        print(f"up-crossings of {spikes} by the observed component over {ev.shape[0]} draws x {ev.shape[1]} chains: mean "
+              f"{sm['mean']['upcross_0']:.3f} sd {sm['sd']['upcross_0']:.3f} r_hat {sm['r_hat']['upcross_0']:.3f} ess "
+              f"{sm['ess_bulk']['upcross_0']:.0f}; P(count = k), k = 0 ..: " + " ".join(f"{c / counts.sum():.3f}" for c in counts))
     if pred is not None:
         pool, path = res["predictive"], pred.save(tmp)
         qs = pred.quantiles([0.05, 0.5, 0.95], cdf=pool["cdf"])
@@ -234,5 +247,10 @@ if __name__ == "__main__":
         i = a.index("--forecast")
         forecast = int(a[i + 1])
         del a[i:i + 2]
-    run(*(int(x) for x in a[:4]), init=init, path_posterior=stride, forecast=forecast, out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
+    spikes = None
+    if "--spikes" in a:
+        i = a.index("--spikes")
+        spikes = float(a[i + 1])
+        del a[i:i + 2]
+    run(*(int(x) for x in a[:4]), init=init, path_posterior=stride, forecast=forecast, spikes=spikes, out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
         transition=a[5] if len(a) > 5 else "static")

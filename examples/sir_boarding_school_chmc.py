@@ -5,6 +5,11 @@ one sub-sequence of 14 observations, sigma_y = 1): batched initial states by the
 (sde/mici_extensions.py:1679-1801), then batched constrained HMC.
 usage: sir_boarding_school_chmc.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir]
        [--keyed-init] [--chain-offset N] [--total-chains N] [--path-posterior STRIDE] [--forecast DAYS]
+       [--peak] [--exceed COUNT]
+--peak: the posterior of the infected curve's peak size and the day it falls on: path-wise events of I(t) = obs_func(x) at
+every step of every post-warm-up state (paths.PathEvents, evaluated on the device and traced like the parameters).
+--exceed COUNT (with --forecast): P(the observed count reaches COUNT on some day of the forecast) and the first-passage day,
+from the event summaries of every replicate future (PredictivePosterior(events=...)).
 --forecast DAYS: posterior predictive forecast of the observed count for DAYS days after day 14: 64 replicate futures of every
 post-warm-up state with fresh driving and observation noise (paths.PredictivePosterior, simulated on the device); the band
 (mean, sd and the 5 / 50 / 95 % points of the predictive CDF over levels 0, 2, .. 800) is printed per day and `predictive.npz`
@@ -27,14 +32,18 @@ from manifold_mcmc_for_diffusions_amd.context import ChmcContext  # noqa: E402
 from manifold_mcmc_for_diffusions_amd.sampling import sample_static_chmc  # noqa: E402
 
 a = sys.argv[1:]
-opts = {"--keyed-init": False, "--chain-offset": 0, "--total-chains": None, "--path-posterior": None, "--forecast": None}
+opts = {"--keyed-init": False, "--chain-offset": 0, "--total-chains": None, "--path-posterior": None, "--forecast": None,
+        "--peak": False, "--exceed": None}
+FLAGS = ("--keyed-init", "--peak")
 for name in list(opts):
     if name in a:
         i = a.index(name)
-        opts[name] = True if name == "--keyed-init" else int(a[i + 1])
-        del a[i:i + (1 if name == "--keyed-init" else 2)]
+        opts[name] = True if name in FLAGS else int(a[i + 1])
+        del a[i:i + (1 if name in FLAGS else 2)]
 keyed, chain_offset, total_chains = opts["--keyed-init"], opts["--chain-offset"], opts["--total-chains"]
-path_stride, forecast = opts["--path-posterior"], opts["--forecast"]
+path_stride, forecast, peak, exceed = opts["--path-posterior"], opts["--forecast"], opts["--peak"], opts["--exceed"]
+if exceed is not None and not forecast:
+    sys.exit("--exceed needs --forecast DAYS")
 B = int(a[0]) if len(a) > 0 else 256
 n_iter = int(a[1]) if len(a) > 1 else 300
 n_warm = int(a[2]) if len(a) > 2 else 100
@@ -71,10 +80,15 @@ if path_stride:
 pred = None
 if forecast:
     from manifold_mcmc_for_diffusions_amd.paths import PredictivePosterior
-    pred = PredictivePosterior(ctx, forecast, n_rep=64, levels=np.arange(0.0, 801.0, 2.0))
+    events = None if exceed is None else dict(channel=ctx.X + 1, thresholds=[float(exceed)])  # y_rep over the whole horizon
+    pred = PredictivePosterior(ctx, forecast, n_rep=64, levels=np.arange(0.0, 801.0, 2.0), events=events)
+pe = None
+if peak:
+    from manifold_mcmc_for_diffusions_amd.paths import PathEvents
+    pe = PathEvents(ctx, ctx.X, stride=path_stride or 1, path_posterior=pp)  # with --path-posterior: on its scratch path
 t0 = time.time()
 res = sample_static_chmc(ctx, n_iter, n_step, 0.05, seed=7, n_adapt=n_warm, n_head=5, jitter_length=True, path_posterior=pp,
-                         **({} if pred is None else {"predictive": pred}),
+                         **({} if pred is None else {"predictive": pred}), **({} if pe is None else {"path_events": pe}),
                          chain_offset=chain_offset, total_chains=total_chains if keyed else None,
                          trace_dir=out_dir or os.path.join(ROOT, "gpurun_out", "sir_run"), trace_func=trace_func,
                          callback=lambda it, h, acc, e: (it % 25 == 0) and print(
@@ -102,3 +116,14 @@ if pred is not None:
     print("   day   E[count] +- sd      5 %    50 %    95 %")
     for p, t in enumerate(pred.times):
         print(f"  {t:5.1f}   {pool['mean'][p, -1]:7.1f} +- {pool['sd'][p, -1]:5.1f}  {qs[p, 0]:7.1f} {qs[p, 1]:7.1f} {qs[p, 2]:7.1f}")
+    if exceed is not None:
+        ev = pool["events"]
+        i = ev["names"].index("t_first_0")
+        print(f"P(count >= {exceed} on some day of the {forecast}-day forecast) = {ev['reached'][i]:.3f} "
+              f"({ev['n'][i]} of {pool['n']} replicate futures); first passage, given it happens: day {ev['mean'][i]:.1f} "
+              f"+- {np.sqrt(ev['var'][i]):.1f}; peak of the forecast count {ev['mean'][0]:.0f} +- {np.sqrt(ev['var'][0]):.0f}")
+if pe is not None:
+    sm = res["path_events_summary"]
+    print(f"peak of the infected curve over {res['path_events'].shape[0]} draws x {B} chains:")
+    for k, label in (("max", "size"), ("t_max", "day ")):
+        print(f"  {label} mean {sm['mean'][k]:8.2f} sd {sm['sd'][k]:7.2f}  r_hat {sm['r_hat'][k]:.3f} ess {sm['ess_bulk'][k]:7.0f}")

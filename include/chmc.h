@@ -292,6 +292,54 @@ int chmc_predict_device(chmc_ctx* ctx, unsigned long long seed, unsigned long lo
                         int stride, int origin, int n_rep, const int* mask, int n_levels, const double* levels, void* n_dev,
                         void* mean_dev, void* m2_dev, void* cdf_dev, void* paths_dev, int n_keep);
 
+/* Path-wise event summaries on the device: functionals of one whole path (its peak and the time of it, first passages,
+ * up-crossings, integrals), which no pointwise summary gives.
+ * The event vector.  Inputs: one channel's values v_p at the points p0 <= p <= p1 (an inclusive window of point indices),
+ * the point times t_p with constant spacing h, and L increasing thresholds theta_0 < ... < theta_{L-1}, 0 <= L <= 8.
+ * NE = 5 + 3 L doubles, in this order:
+ *   max, t_max     max_p v_p and the time of the FIRST point attaining it
+ *   min, t_min     min_p v_p and the time of the FIRST point attaining it
+ *   integral       h (sum_{p = p0 .. p1} v_p - (v_p0 + v_p1) / 2), the trapezoid rule; 0 for a one-point window
+ *   then per threshold l = 0 .. L - 1:
+ *   upcross_l      #{p0 < p <= p1 : v_{p-1} < theta_l <= v_p}, as a double
+ *   t_first_l      the time of the first p in [p0, p1] with v_p >= theta_l; NaN if there is none
+ *   time_above_l   h #{p0 < p <= p1 : v_p >= theta_l}
+ * If any v_p of the window is not finite, all NE entries are NaN.  Values outside the window never matter.
+ *
+ * chmc_path_events_device: the events of the latent path.  x_seq_dev [B][n_points][X] is any path buffer on the device, for
+ * example the scratch of chmc_path_stats_update_device / chmc_generate_x_seq_device at the same stride; point p has time
+ * t_p = p h with h = stride dl, dl = obs_interval / num_steps_per_obs.  channel in [0, X]: a state component, or X for
+ * obs_func(x).  thresholds: host, n_thresholds doubles.  events_dev [B][NE] receives the event vectors; mask (host [B],
+ * NULL = all): the row of a chain with mask[c] == 0 is not touched.
+ * With the compact rows allocated (the default) a wavefront per chain reduces the window (k_path_events: the integral's
+ * per-lane partial sums are added in one fixed order), under CHMC_COMPACT_ROWS=0 a work item per chain takes the points in
+ * order (KPathEvents); the two may differ in `integral` by rounding alone, every other entry is identical.  A chain's
+ * events depend on its own path alone: any sharding of the chains gives the same bits.
+ * Errors: NULL buffers; stride < 1 or not a divisor of num_steps_per_obs; channel outside [0, X]; n_points < 1; a window
+ * that is not 0 <= p0 <= p1 < n_points; n_thresholds outside [0, 8]; thresholds NULL or not increasing.
+ *
+ * chmc_predict_events_device: chmc_predict_device (same arguments, same keyed streams, same replicate paths; it leaves the
+ * same moments, CDF counts and kept paths, bit for bit) which also evaluates the event vector of every replicate.
+ * channel in [0, X + 1] (X + 1: y_rep); the window is over the emitted points, 0-based and inclusive, 0 <= p0 <= p1 < NPF;
+ * the times are those of chmc_predict_points and h = stride dl.
+ *   events_dev [B][n_rep][NE]  the replicates' event vectors of this call (overwritten by every call); NULL keeps none.
+ *   en_dev [B][NE] (long long), emean_dev, em2_dev [B][NE]: running moments per chain and entry over the FINITE values,
+ *   the caller's device buffers, zero before the first call.  One call merges, per entry, its groups of 64 consecutive
+ *   replicates in group order, as the predictive moments above: with R_g the number of finite values v of the group
+ *   (a group with none merges nothing), m_g = sum(v) / R_g, s_g = sum((v - m_g)^2), both sums in replicate order, then
+ *   Chan's merge with the entry's own count n = en.  So P(threshold l reached in the window) = en[t_first_l] / n_dev.
+ * Both forms of the predictive evaluate a replicate's events by the same code on the replicate's own path and share the fold,
+ * and a chain's events depend on (seed, draw, chain_offset + c), its own state and data alone: any sharding gives the same bits.
+ * Errors: those of chmc_predict_device, and: channel outside [0, X + 1]; a bad window; n_thresholds outside [0, 8];
+ * thresholds NULL or not increasing; a NULL en_dev, emean_dev or em2_dev. */
+int chmc_path_events_device(chmc_ctx* ctx, const void* x_seq_dev, int n_points, int stride, int channel, int p0, int p1,
+                            int n_thresholds, const double* thresholds, const int* mask, void* events_dev);
+int chmc_predict_events_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset, int horizon,
+                               int stride, int origin, int n_rep, const int* mask, int n_levels, const double* levels,
+                               void* n_dev, void* mean_dev, void* m2_dev, void* cdf_dev, void* paths_dev, int n_keep,
+                               int channel, int p0, int p1, int n_thresholds, const double* thresholds, void* events_dev,
+                               void* en_dev, void* emean_dev, void* em2_dev);
+
 /* ---- per-op entry points, evaluated at the current state ------------------------------------------------
  * Internally the library keeps the dc/dv rows of a state in a compact factored form (per step a row-independent X x V
  * matrix, per observation interval the RM x X adjoint frame; DESIGN.md section 4 "Compact rows") and the stepping path
@@ -484,9 +532,11 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *   out80[74]      launches of the time-parallel path scan (k_path_par: chmc_generate_x_seq* / chmc_path_stats_update_device
  *                  on the current states with the compact rows allocated)
  *   out80[75]      launches of the sequential path scan (KPath: a caller's q, or CHMC_COMPACT_ROWS=0)
- *   out80[76]      launches of the predictive wave kernel (k_predict: chmc_predict_device with the compact rows on)
- *   out80[77]      launches of the predictive functor form (KPredict: CHMC_COMPACT_ROWS=0)
- *   out80[78 .. 79] reserved (0)
+ *   out80[76]      launches of the predictive wave kernel (k_predict, k_predict_events: chmc_predict_device /
+ *                  chmc_predict_events_device with the compact rows on)
+ *   out80[77]      launches of the predictive functor form (KPredict, KPredictEvents: CHMC_COMPACT_ROWS=0)
+ *   out80[78]      launches of the path-events wave kernel (k_path_events: chmc_path_events_device, compact rows on)
+ *   out80[79]      launches of the path-events functor form (KPathEvents: CHMC_COMPACT_ROWS=0)
  * Synchronises the context's stream. */
 int chmc_get_diagnostics(chmc_ctx* ctx, long long* out80);
 

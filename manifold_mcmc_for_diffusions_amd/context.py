@@ -362,6 +362,32 @@ class ChmcContext:
                                          C.c_void_p(cdf_dev_ptr), C.c_void_p(paths_dev_ptr), int(n_keep)),
               "chmc_predict_device")
 
+    # ---- path-wise events (chmc_path_events_device, chmc_predict_events_device; paths.PathEvents / PredictivePosterior)
+    def path_events_device(self, x_seq_dev_ptr, n_points, stride, channel, p0, p1, thresholds, events_dev_ptr, mask=None):
+        """The event vectors [B][5 + 3 L] of one channel of the device path buffer x_seq [B][n_points][X] over the points
+        p0 .. p1 (chmc_path_events_device, include/chmc.h)."""
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        th = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        check(self.L.chmc_path_events_device(self.h, C.c_void_p(x_seq_dev_ptr), int(n_points), int(stride), int(channel),
+                                             int(p0), int(p1), len(th), ptr(th) if len(th) else None, iptr(m),
+                                             C.c_void_p(events_dev_ptr)), "chmc_path_events_device")
+
+    def predict_events_device(self, seed, draw, chain_offset, horizon, stride, origin, n_rep, n_dev_ptr, mean_dev_ptr,
+                              m2_dev_ptr, channel, p0, p1, thresholds, en_dev_ptr, emean_dev_ptr, em2_dev_ptr,
+                              events_dev_ptr=None, mask=None, levels=None, cdf_dev_ptr=None, paths_dev_ptr=None, n_keep=0):
+        """predict_device which also evaluates every replicate's event vector and folds it per chain and entry
+        (chmc_predict_events_device, include/chmc.h)."""
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        lv = None if levels is None else as_c(levels).reshape(-1)
+        th = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        check(self.L.chmc_predict_events_device(self.h, int(seed), int(draw), int(chain_offset), int(horizon), int(stride),
+                                                int(origin), int(n_rep), iptr(m), 0 if lv is None else len(lv), ptr(lv),
+                                                C.c_void_p(n_dev_ptr), C.c_void_p(mean_dev_ptr), C.c_void_p(m2_dev_ptr),
+                                                C.c_void_p(cdf_dev_ptr), C.c_void_p(paths_dev_ptr), int(n_keep), int(channel),
+                                                int(p0), int(p1), len(th), ptr(th) if len(th) else None,
+                                                C.c_void_p(events_dev_ptr), C.c_void_p(en_dev_ptr), C.c_void_p(emean_dev_ptr),
+                                                C.c_void_p(em2_dev_ptr)), "chmc_predict_events_device")
+
     # ---- per-op
     @property
     def dim_c(self):
@@ -608,6 +634,7 @@ class ChmcContext:
                     newton_fsm_launches=int(v[68]), newton_factor8_launches=int(v[69]), pair_scan_rounds=int(v[70]),
                     newton_scan_launches=int(v[71]), newton_rounds=int(v[72]), path_par_launches=int(v[74]),
                     path_seq_launches=int(v[75]), predict_wave_launches=int(v[76]), predict_seq_launches=int(v[77]),
+                    path_events_wave_launches=int(v[78]), path_events_seq_launches=int(v[79]),
                     extra=v[68:80])
 
     def counters(self):

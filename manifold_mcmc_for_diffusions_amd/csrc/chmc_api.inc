@@ -57,6 +57,8 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   double* d_pred_x = nullptr;       // ... [B][T + 1][X] the chains' paths at the observation times (the forecast's start state)
   double* d_pred_lev = nullptr;     // ... the CDF levels, d_pred_lev_cap doubles
   size_t d_pred_lev_cap = 0;
+  double* d_pred_ev = nullptr;      // chmc_predict_events_device: [NPF] point times, then the raw events where the caller keeps none
+  size_t d_pred_ev_cap = 0;
   TreeState tree{};                                     // chmc_tree_begin / _subtree / _step: per-chain tree decisions
   bool have_tree = false;
   bool rows_fresh = false;  // Slots::Jv holds the full rows of the current states (see ensure_rows)
@@ -72,7 +74,8 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
                               // call whose passes behind the scan served two problems as well (KernelPlan::pair_passes: interval
                               // sums, combine, solve and J^T lambda update one launch each; a subset of [6]), [10] launches of
                               // the time-parallel path scan, [11] of the sequential one (KPath), [12] of the predictive wave
-                              // kernel, [13] of its functor form (KPredict)
+                              // kernel, [13] of its functor form (KPredict), [14] of the path-events wave kernel, [15] of its
+                              // functor form (KPathEvents)
   // Paired retractions (KernelPlan::pair_retractions): the second problem of a paired run_lockstep call -- the forward
   // retraction of the NEXT step -- works in a Work of its own: every array a round's kernels, KNewtonBegin, KCheck or KNewtonEnd
   // write (pair_alloc), everything they only read shared with `w`.  Whole batch only, allocated on first use.
@@ -1231,24 +1234,50 @@ extern "C" int chmc_predict_points(const chmc_ctx* ctx, int horizon, int stride,
     for (int p = 1; p <= NPF; ++p) times[p - 1] = t0 + p * (stride * sy.dl);
   return 0;
 }
-extern "C" int chmc_predict_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset,
-                                   int horizon, int stride, int origin, int n_rep, const int* mask, int n_levels,
-                                   const double* levels, void* n_dev, void* mean_dev, void* m2_dev, void* cdf_dev,
-                                   void* paths_dev, int n_keep) {
-  CHMC_ENTER("chmc_predict_device")
-  if (!n_dev || !mean_dev || !m2_dev) return fail("chmc_predict_device: null argument");
-  if (predict_check(ctx, "chmc_predict_device", horizon, stride, origin)) return -1;
-  if (!ctx->have_state) return fail("chmc_predict_device: no state has been set");
-  if (n_rep < 1 || n_rep > 65536) return fail("chmc_predict_device: n_rep must be in [1, 65536]");
+// the events of a chmc_predict_events_device call (null: chmc_predict_device)
+struct PredictEventCall {
+  int channel, p0, p1, n_thresholds;
+  const double* thresholds;
+  void *events_dev, *en_dev, *emean_dev, *em2_dev;
+};
+static int event_thresholds(const std::string& fn, int L, const double* th, EventArgs& e) {
+  if (L < 0 || L > kEventLevels) return fail(fn + ": the number of thresholds must be in [0, 8]");
+  if (L > 0 && !th) return fail(fn + ": thresholds must not be null");
+  for (int l = 0; l < L; ++l) {
+    if (!(th[l] == th[l]) || (l && !(th[l] > th[l - 1]))) return fail(fn + ": thresholds must be increasing");
+    e.theta[l] = th[l];
+  }
+  e.L = L;
+  return 0;
+}
+static int predict_call(chmc_ctx* ctx, const char* name, unsigned long long seed, unsigned long long draw, int chain_offset,
+                        int horizon, int stride, int origin, int n_rep, const int* mask, int n_levels, const double* levels,
+                        void* n_dev, void* mean_dev, void* m2_dev, void* cdf_dev, void* paths_dev, int n_keep,
+                        const PredictEventCall* ev) {
+  CHMC_ENTER(name)
+  const std::string fn = name;
+  if (!n_dev || !mean_dev || !m2_dev) return fail(fn + ": null argument");
+  if (predict_check(ctx, fn.c_str(), horizon, stride, origin)) return -1;
+  if (!ctx->have_state) return fail(fn + ": no state has been set");
+  if (n_rep < 1 || n_rep > 65536) return fail(fn + ": n_rep must be in [1, 65536]");
   if ((long long)ctx->sy.B * n_rep >= (1LL << 31) || (long long)ctx->sy.B * (horizon * ctx->sy.S / stride) >= (1LL << 31))
-    return fail("chmc_predict_device: chains x replicates and chains x points must stay below 2^31");
-  if (n_keep < 0 || n_keep > n_rep) return fail("chmc_predict_device: n_keep must be in [0, n_rep]");
-  if (draw >= (1ULL << 45)) return fail("chmc_predict_device: draw must be below 2^45");
-  if (n_levels < 0) return fail("chmc_predict_device: n_levels must not be negative");
-  if (n_levels > 0 && (!levels || !cdf_dev)) return fail("chmc_predict_device: n_levels > 0 needs levels and cdf_dev");
+    return fail(fn + ": chains x replicates and chains x points must stay below 2^31");
+  if (n_keep < 0 || n_keep > n_rep) return fail(fn + ": n_keep must be in [0, n_rep]");
+  if (draw >= (1ULL << 45)) return fail(fn + ": draw must be below 2^45");
+  if (n_levels < 0) return fail(fn + ": n_levels must not be negative");
+  if (n_levels > 0 && (!levels || !cdf_dev)) return fail(fn + ": n_levels > 0 needs levels and cdf_dev");
   for (int l = 1; l < n_levels; ++l)
-    if (!(levels[l] > levels[l - 1])) return fail("chmc_predict_device: levels must be increasing");
+    if (!(levels[l] > levels[l - 1])) return fail(fn + ": levels must be increasing");
   const Sys& sy = ctx->sy;
+  EventArgs e{};
+  if (ev) {
+    const int NPF = horizon * sy.S / stride;
+    if (!ev->en_dev || !ev->emean_dev || !ev->em2_dev) return fail(fn + ": null argument");
+    if (ev->channel < 0 || ev->channel > sy.X + 1) return fail(fn + ": channel must be in [0, X + 1]");
+    if (ev->p0 < 0 || ev->p1 < ev->p0 || ev->p1 >= NPF) return fail(fn + ": window must satisfy 0 <= p0 <= p1 < n_points");
+    if (event_thresholds(fn, ev->n_thresholds, ev->thresholds, e)) return -1;
+    e.channel = ev->channel, e.p0 = ev->p0, e.p1 = ev->p1, e.h = stride * sy.dl;
+  }
   if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)sy.B);
   PredictArgs a{};
   a.seed = seed, a.key0 = CHMC_PREDICT_DRAW | (draw << 16);
@@ -1271,11 +1300,71 @@ extern "C" int chmc_predict_device(chmc_ctx* ctx, unsigned long long seed, unsig
     h2d(ctx->d_pred_lev, levels, sizeof(double) * n_levels);
     a.levels = ctx->d_pred_lev;
   }
+  if (!ev) {
+    dispatch(ctx, [&](auto inst) {
+      predict_pass<typename decltype(inst)::M>(ctx, a, (long long*)n_dev, (double*)mean_dev, (double*)m2_dev, (long long*)cdf_dev);
+    });
+    CHMC_LEAVE(name)
+  }
+  // the point times, as chmc_predict_points gives them, and the replicates' raw events (the caller's buffer or scratch)
+  const int NE = 5 + 3 * e.L;
+  const size_t n_ev = ev->events_dev ? 0 : (size_t)sy.B * n_rep * NE;
+  if (ctx->d_pred_ev_cap < a.NPF + n_ev)
+    ctx->d_pred_ev = alloc<double>(ctx, a.NPF + n_ev), ctx->d_pred_ev_cap = a.NPF + n_ev;
+  std::vector<double> times(a.NPF);
+  const double t0 = origin == 0 ? sy.T * ctx->cfg.obs_interval : 0.0;
+  for (int p = 1; p <= a.NPF; ++p) times[p - 1] = t0 + p * (stride * sy.dl);
+  h2d(ctx->d_pred_ev, times.data(), sizeof(double) * a.NPF);
+  e.times = ctx->d_pred_ev;
+  double* evraw = ev->events_dev ? (double*)ev->events_dev : ctx->d_pred_ev + a.NPF;
   dispatch(ctx, [&](auto inst) {
-    predict_pass<typename decltype(inst)::M>(ctx, a, (long long*)n_dev, (double*)mean_dev, (double*)m2_dev, (long long*)cdf_dev);
+    predict_events_pass<typename decltype(inst)::M>(ctx, a, e, evraw, (long long*)n_dev, (double*)mean_dev, (double*)m2_dev,
+                                                    (long long*)cdf_dev);
   });
-  CHMC_LEAVE("chmc_predict_device")
+  event_fold(ctx, a, e, evraw, (long long*)ev->en_dev, (double*)ev->emean_dev, (double*)ev->em2_dev);
+  CHMC_LEAVE(name)
 }
+extern "C" int chmc_predict_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset,
+                                   int horizon, int stride, int origin, int n_rep, const int* mask, int n_levels,
+                                   const double* levels, void* n_dev, void* mean_dev, void* m2_dev, void* cdf_dev,
+                                   void* paths_dev, int n_keep) {
+  return predict_call(ctx, "chmc_predict_device", seed, draw, chain_offset, horizon, stride, origin, n_rep, mask, n_levels,
+                      levels, n_dev, mean_dev, m2_dev, cdf_dev, paths_dev, n_keep, nullptr);
+}
+extern "C" int chmc_predict_events_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset,
+                                          int horizon, int stride, int origin, int n_rep, const int* mask, int n_levels,
+                                          const double* levels, void* n_dev, void* mean_dev, void* m2_dev, void* cdf_dev,
+                                          void* paths_dev, int n_keep, int channel, int p0, int p1, int n_thresholds,
+                                          const double* thresholds, void* events_dev, void* en_dev, void* emean_dev,
+                                          void* em2_dev) {
+  const PredictEventCall ev{channel, p0, p1, n_thresholds, thresholds, events_dev, en_dev, emean_dev, em2_dev};
+  return predict_call(ctx, "chmc_predict_events_device", seed, draw, chain_offset, horizon, stride, origin, n_rep, mask,
+                      n_levels, levels, n_dev, mean_dev, m2_dev, cdf_dev, paths_dev, n_keep, &ev);
+}
+
+// path-wise events of a path buffer (include/chmc.h): path_events_pass picks the kernel
+extern "C" int chmc_path_events_device(chmc_ctx* ctx, const void* x_seq_dev, int n_points, int stride, int channel, int p0,
+                                       int p1, int n_thresholds, const double* thresholds, const int* mask, void* events_dev) {
+  CHMC_ENTER("chmc_path_events_device")
+  const std::string fn = "chmc_path_events_device";
+  if (!x_seq_dev || !events_dev) return fail(fn + ": null argument");
+  const Sys& sy = ctx->sy;
+  if (stride < 1 || sy.S % stride != 0) return fail(fn + ": stride must be at least 1 and divide num_steps_per_obs");
+  if (channel < 0 || channel > sy.X) return fail(fn + ": channel must be in [0, X]");
+  if (n_points < 1 || (long long)sy.B * n_points >= (1LL << 31)) return fail(fn + ": n_points must be positive, chains x points below 2^31");
+  if (p0 < 0 || p1 < p0 || p1 >= n_points) return fail(fn + ": window must satisfy 0 <= p0 <= p1 < n_points");
+  EventArgs e{};
+  if (event_thresholds(fn, n_thresholds, thresholds, e)) return -1;
+  e.channel = channel, e.p0 = p0, e.p1 = p1, e.h = stride * sy.dl;
+  if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)sy.B);
+  int* d_mask = nullptr;
+  if (mask) h2d(d_mask = ctx->d_path_ints + sy.B, mask, sizeof(int) * sy.B);
+  dispatch(ctx, [&](auto inst) {
+    path_events_pass<typename decltype(inst)::M>(ctx, n_points, e, d_mask, (const double*)x_seq_dev, (double*)events_dev);
+  });
+  CHMC_LEAVE("chmc_path_events_device")
+}
+
 
 // padded [B][Kmax][RM] <-> packed [B][C] conversion of block-row vectors (host side, small)
 static void unpad_rows(const chmc_ctx* c, const std::vector<double>& pad, double* out, int ncomp) {

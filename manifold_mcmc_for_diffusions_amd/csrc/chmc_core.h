@@ -2317,6 +2317,168 @@ struct KPredictFold {
   }
 };
 
+// ------------------------------------------------------------------------------------------
+// Path-wise event summaries (chmc_path_events_device / chmc_predict_events_device, include/chmc.h): extremes, the trapezoid
+// integral and, per threshold, up-crossings, first passage and time above, of ONE channel over an inclusive window of points.
+// The event vector has NE = 5 + 3 L doubles: max, t_max, min, t_min, integral, then per threshold upcross, t_first,
+// time_above.  EventAcc is the running form over points taken in order: KPathEvents (a work item per chain), every replicate
+// of the predictive in both of its forms (a work item or a lane per replicate), and every lane of k_path_events
+// (chmc_wave.h) over its own points, whose lanes are then reduced.
+constexpr int kEventLevels = 8;
+struct EventArgs {
+  int channel, p0, p1, L;
+  double h;             // point spacing; the time of point p is times[p] where a table is given, p * h otherwise
+  const double* times;  // device table or null
+  double theta[kEventLevels];
+};
+CHMC_HD CHMC_FI inline bool event_finite(double v) { return v - v == 0.0; }
+CHMC_HD CHMC_FI inline double event_time(const EventArgs& e, int p) { return e.times ? e.times[p] : p * e.h; }
+struct EventAcc {
+  double vmax, vmin, sum;
+  int imax, imin, bad, n;
+  int up[kEventLevels], above[kEventLevels], first[kEventLevels];
+  // the window's first point: it has no predecessor, so it neither up-crosses nor counts as time above
+  CHMC_HD CHMC_FI inline void open(const EventArgs& e, int p, double v) {
+    vmax = vmin = sum = v, imax = imin = p, bad = event_finite(v) ? 0 : 1, n = 1;
+    CHMC_UNROLL
+    for (int l = 0; l < kEventLevels; ++l) up[l] = above[l] = 0, first[l] = l < e.L && v >= e.theta[l] ? p : -1;
+  }
+  CHMC_HD CHMC_FI inline void add(const EventArgs& e, int p, double v, double prev) {
+    if (!event_finite(v)) bad = 1;
+    if (v > vmax) vmax = v, imax = p;
+    if (v < vmin) vmin = v, imin = p;
+    sum += v, ++n;
+    CHMC_UNROLL
+    for (int l = 0; l < kEventLevels; ++l)
+      if (l < e.L && v >= e.theta[l]) {
+        ++above[l];
+        if (first[l] < 0) first[l] = p;
+        if (prev < e.theta[l]) ++up[l];
+      }
+  }
+};
+// the event vector from the window's totals; vfirst, vlast: the values at p0 and p1
+CHMC_HD CHMC_FI inline void event_write(const EventArgs& e, double* out, bool bad, double vmax, int imax, double vmin, int imin,
+                                        double sum, double vfirst, double vlast, const int* up, const int* first,
+                                        const int* above) {
+  const int NE = 5 + 3 * e.L;
+  if (bad) {
+    for (int i = 0; i < NE; ++i) out[i] = __builtin_nan("");
+    return;
+  }
+  out[0] = vmax, out[1] = event_time(e, imax), out[2] = vmin, out[3] = event_time(e, imin);
+  out[4] = e.p1 > e.p0 ? e.h * (sum - 0.5 * (vfirst + vlast)) : 0.0;
+  CHMC_UNROLL
+  for (int l = 0; l < kEventLevels; ++l)
+    if (l < e.L) {
+      out[5 + 3 * l] = (double)up[l];
+      out[6 + 3 * l] = first[l] >= 0 ? event_time(e, first[l]) : __builtin_nan("");
+      out[7 + 3 * l] = e.h * (double)above[l];
+    }
+}
+// one emitted point of a replicate (points arrive in order; those outside the window are skipped)
+CHMC_HD CHMC_FI inline void event_point(const EventArgs& e, EventAcc& acc, int p, double v, double& vfirst, double& prev) {
+  if (p < e.p0 || p > e.p1) return;
+  if (p == e.p0)
+    acc.open(e, p, v), vfirst = v;
+  else
+    acc.add(e, p, v, prev);
+  prev = v;
+}
+// the channel's value at one point of a path buffer x [..][X]: a state component, or obs(x) for channel X
+template <class M>
+CHMC_HD CHMC_FI inline double event_channel(const double* xp, int channel) {
+  return channel < M::X ? xp[channel] : M::obs(xp);
+}
+// The functor form of the latent-path events: one work item per chain, the window's points in order.
+template <class M>
+struct KPathEvents {
+  int NP;
+  EventArgs e;
+  const int* mask;
+  const double* x;  // [B][NP][X]
+  double* out;      // [B][NE]
+  CHMC_HD void operator()(int c) const {
+    if (mask && !mask[c]) return;
+    const double* xc = x + (size_t)c * NP * M::X;
+    EventAcc a;
+    const double vfirst = event_channel<M>(xc + (size_t)e.p0 * M::X, e.channel);
+    double prev = vfirst;
+    a.open(e, e.p0, vfirst);
+    for (int p = e.p0 + 1; p <= e.p1; ++p) {
+      const double v = event_channel<M>(xc + (size_t)p * M::X, e.channel);
+      a.add(e, p, v, prev);
+      prev = v;
+    }
+    event_write(e, out + (size_t)c * (5 + 3 * e.L), a.bad != 0, a.vmax, a.imax, a.vmin, a.imin, a.sum, vfirst, prev, a.up,
+                a.first, a.above);
+  }
+};
+// The predictive's events, functor form (pass 1 of chmc_predict_events_device): KPredict with the replicate's event vector
+// accumulated in the emit callback; evraw [B][n_rep][NE].
+template <class M>
+struct KPredictEvents {
+  Sys sy;
+  Slots sl;
+  PredictArgs a;
+  double* raw;
+  EventArgs e;
+  double* evraw;
+  CHMC_HD void operator()(int tid) const {
+    constexpr int XC = M::X + 2;
+    const int c = tid / a.n_rep, r = tid - c * a.n_rep;
+    if (a.mask && !a.mask[c]) return;
+    const double* q = pick(sl.q, sl.cur[c]) + (size_t)c * sy.Q;
+    double* o = raw + ((size_t)c * a.n_rep + r) * a.NPF * XC;
+    double* k = a.paths && r < a.n_keep ? a.paths + ((size_t)c * a.n_keep + r) * a.NPF * XC : nullptr;
+    EventAcc acc;
+    double vfirst = 0.0, prev = 0.0;
+    predict_replicate<M>(sy, a, q, c, r, [&](int p, const double* ch) {
+      for (int i = 0; i < XC; ++i) o[(size_t)p * XC + i] = ch[i];
+      if (k)
+        for (int i = 0; i < XC; ++i) k[(size_t)p * XC + i] = ch[i];
+      event_point(e, acc, p, ch[e.channel], vfirst, prev);
+    });
+    event_write(e, evraw + ((size_t)c * a.n_rep + r) * (5 + 3 * e.L), acc.bad != 0, acc.vmax, acc.imax, acc.vmin, acc.imin,
+                acc.sum, vfirst, prev, acc.up, acc.first, acc.above);
+  }
+};
+// The fold of the predictive's events, pass 2 of both forms: one work item per (chain, entry) merges the call's groups of 64
+// consecutive replicates, in group order, over the FINITE values of that entry (R_g of them; none: no merge), two passes
+// per group, into en / emean / em2 [B][NE] by Chan's rule with the entry's own count.
+struct KEventFold {
+  int NE, n_rep;
+  const int* mask;
+  const double* evraw;  // [B][n_rep][NE]
+  long long* en;
+  double *emean, *em2;
+  CHMC_HD void operator()(int tid) const {
+    const int c = tid / NE, i = tid - c * NE;
+    if (mask && !mask[c]) return;
+    const double* v = evraw + (size_t)c * n_rep * NE + i;
+    long long nn = en[tid];
+    double mu = emean[tid], s2 = em2[tid];
+    for (int g = 0; g < n_rep; g += 64) {
+      const int R = n_rep - g < 64 ? n_rep - g : 64;
+      int Rg = 0;
+      double sum = 0.0, sq = 0.0;
+      for (int k = 0; k < R; ++k) {
+        const double x = v[(size_t)(g + k) * NE];
+        if (event_finite(x)) sum += x, ++Rg;
+      }
+      if (!Rg) continue;
+      const double mg = sum / Rg;
+      for (int k = 0; k < R; ++k) {
+        const double x = v[(size_t)(g + k) * NE];
+        if (event_finite(x)) sq += (x - mg) * (x - mg);
+      }
+      predict_merge((double)nn, (double)Rg, mg, sq, mu, s2);
+      nn += Rg;
+    }
+    en[tid] = nn, emean[tid] = mu, em2[tid] = s2;
+  }
+};
+
 // "Deal a try into a row" (chmc_adam_begin_tries_device): zero moments and gradient of the listed rows, and the row's work
 // trajectory -- the guess the time-parallel scan of the comparator target would otherwise inherit from whatever was
 // evaluated in that row before.  One work item per (listed row, element), the longer of the two spans.

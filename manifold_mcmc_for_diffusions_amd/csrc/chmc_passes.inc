@@ -73,6 +73,25 @@ static void predict_seq(chmc_ctx* c, const PredictArgs& a, long long* n, double*
   predict_fold<M>(c, a, 0, raw, n, mean, m2, cdf);
 }
 
+// the predictive with events by the generic functors (KPredictEvents), and the events' fold of both forms (KEventFold)
+template <class M>
+static void predict_events_seq(chmc_ctx* c, const PredictArgs& a, const EventArgs& e, double* evraw, long long* n, double* mean,
+                               double* m2, long long* cdf) {
+  double* raw = predict_scratch(c, (size_t)c->sy.B * a.n_rep * a.NPF * (M::X + 2));
+  launch(KPredictEvents<M>{c->sy, c->sl, a, raw, e, evraw}, (long)c->sy.B * a.n_rep, 7), c->diag[13]++;
+  predict_fold<M>(c, a, 0, raw, n, mean, m2, cdf);
+}
+static void event_fold(chmc_ctx* c, const PredictArgs& a, const EventArgs& e, const double* evraw, long long* en, double* emean,
+                       double* em2) {
+  const int NE = 5 + 3 * e.L;
+  launch(KEventFold{NE, a.n_rep, a.mask, evraw, en, emean, em2}, (long)c->sy.B * NE, 8);
+}
+// the latent-path events by the generic functor: one work item per chain
+template <class M>
+static void path_events_seq(chmc_ctx* c, int NP, const EventArgs& e, const int* mask, const double* x, double* out) {
+  launch(KPathEvents<M>{NP, e, mask, x, out}, c->sy.B, 7), c->diag[15]++;
+}
+
 #ifdef CHMC_WAVE_KERNELS
 constexpr bool kWaveKernels = true;  // PlanInput::wave_kernels of every context of this build
 // chmc_predict_device: a wavefront per (chain, group of 64 replicates) where the library keeps the compact rows (the
@@ -85,6 +104,23 @@ static void predict_pass(chmc_ctx* c, const PredictArgs& a, long long* n, double
   double* grp = predict_scratch(c, (size_t)c->sy.B * G * a.NPF * (2 * (M::X + 2) + a.n_levels));
   launch_blocks(k_predict<M>, (long)c->sy.B * G, 64, 7, c->sy, c->sl, a, grp), c->diag[12]++;
   predict_fold<M>(c, a, 1, grp, n, mean, m2, cdf);
+}
+// chmc_predict_events_device: predict_pass's rule, with the EVENTS instantiation of the wave kernel
+template <class M>
+static void predict_events_pass(chmc_ctx* c, const PredictArgs& a, const EventArgs& e, double* evraw, long long* n, double* mean,
+                                double* m2, long long* cdf) {
+  if (!c->plan.pb_allocated) return predict_events_seq<M>(c, a, e, evraw, n, mean, m2, cdf);
+  const int G = (a.n_rep + 63) / 64;
+  double* grp = predict_scratch(c, (size_t)c->sy.B * G * a.NPF * (2 * (M::X + 2) + a.n_levels));
+  launch_blocks(k_predict_events<M>, (long)c->sy.B * G, 64, 7, c->sy, c->sl, a, grp, e, evraw), c->diag[12]++;
+  predict_fold<M>(c, a, 1, grp, n, mean, m2, cdf);
+}
+// chmc_path_events_device: a wavefront per chain where the library keeps the compact rows (path_scan's rule), the functor
+// form under CHMC_COMPACT_ROWS=0
+template <class M>
+static void path_events_pass(chmc_ctx* c, int NP, const EventArgs& e, const int* mask, const double* x, double* out) {
+  if (!c->plan.pb_allocated) return path_events_seq<M>(c, NP, e, mask, x, out);
+  launch_blocks(k_path_events<M>, (long)c->sy.B, 64, 7, c->sy.B, NP, e, mask, x, out), c->diag[14]++;
 }
 // chain-level Woodbury solve: one wavefront per chain up to 64 blocks
 template <class M, int RM, int SYM, int TGT>
@@ -509,6 +545,15 @@ static void path_scan(chmc_ctx* c, const double* q, int stride, double* out, int
 template <class M>
 static void predict_pass(chmc_ctx* c, const PredictArgs& a, long long* n, double* mean, double* m2, long long* cdf) {
   predict_seq<M>(c, a, n, mean, m2, cdf);
+}
+template <class M>
+static void predict_events_pass(chmc_ctx* c, const PredictArgs& a, const EventArgs& e, double* evraw, long long* n, double* mean,
+                                double* m2, long long* cdf) {
+  predict_events_seq<M>(c, a, e, evraw, n, mean, m2, cdf);
+}
+template <class M>
+static void path_events_pass(chmc_ctx* c, int NP, const EventArgs& e, const int* mask, const double* x, double* out) {
+  path_events_seq<M>(c, NP, e, mask, x, out);
 }
 template <class M, int RM>
 static void nld_sweeps(chmc_ctx*, const Sys&, int, int, double*) { no_wave_kernels("the comparator target"); }

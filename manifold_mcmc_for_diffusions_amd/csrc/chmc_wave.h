@@ -5800,8 +5800,12 @@ __device__ __forceinline__ double wave_allsum(double v) {
   v += __shfl_xor(v, 32, 64);
   return v;
 }
-template <class M>
-__global__ void __launch_bounds__(64) k_predict(Sys sy, Slots sl, PredictArgs a, double* grp) {
+// EVENTS (k_predict_events, chmc_predict_events_device): every lane also keeps the running event accumulator of its replicate
+// (EventAcc, chmc_core.h) in the emit callback and stores the replicate's event vector into evraw [B][n_rep][NE] at the end;
+// without it the body is the text of k_predict as it was.
+template <class M, bool EVENTS>
+__device__ __forceinline__ void predict_wave(const Sys& sy, const Slots& sl, const PredictArgs& a, double* grp,
+                                             const EventArgs* e, double* evraw) {
   constexpr int X = M::X, XC = X + 2;
   const int lane = threadIdx.x & 63;
   const int G = (a.n_rep + 63) / 64;
@@ -5815,7 +5819,10 @@ __global__ void __launch_bounds__(64) k_predict(Sys sy, Slots sl, PredictArgs a,
   const double* q = pick(sl.q, sl.cur[c]) + (size_t)c * sy.Q;
   double* keep = a.paths && act && r < a.n_keep ? a.paths + ((size_t)c * a.n_keep + r) * a.NPF * XC : nullptr;
   double* rec0 = grp + ((size_t)c * G + g) * a.NPF * REC;
+  EventAcc acc;
+  double vfirst = 0.0, prev = 0.0;
   predict_replicate<M>(sy, a, q, c, r, [&](int p, const double* ch) {
+    if constexpr (EVENTS) event_point(*e, acc, p, ch[e->channel], vfirst, prev);
     if (keep) {
 #pragma unroll
       for (int i = 0; i < XC; ++i) keep[(size_t)p * XC + i] = ch[i];
@@ -5835,6 +5842,67 @@ __global__ void __launch_bounds__(64) k_predict(Sys sy, Slots sl, PredictArgs a,
       if (lane == (l & 63)) rec[2 * XC + l] = (double)cnt;
     }
   });
+  if constexpr (EVENTS) {
+    if (act)
+      event_write(*e, evraw + ((size_t)c * a.n_rep + r) * (5 + 3 * e->L), acc.bad != 0, acc.vmax, acc.imax, acc.vmin, acc.imin,
+                  acc.sum, vfirst, prev, acc.up, acc.first, acc.above);
+  }
+}
+template <class M>
+__global__ void __launch_bounds__(64) k_predict(Sys sy, Slots sl, PredictArgs a, double* grp) {
+  predict_wave<M, false>(sy, sl, a, grp, nullptr, nullptr);
+}
+template <class M>
+__global__ void __launch_bounds__(64) k_predict_events(Sys sy, Slots sl, PredictArgs a, double* grp, EventArgs e, double* evraw) {
+  predict_wave<M, true>(sy, sl, a, grp, &e, evraw);
+}
+
+// Path-wise events of the latent path (chmc_path_events_device): one wavefront per chain over x [B][NP][X].  Lane j takes
+// the window's points p0 + j, p0 + j + 64, ... so that a wavefront's loads are consecutive points; the predecessor of each
+// point is read by the same lane (a second load of a line its neighbour has just fetched, no shuffle on the path).  Every
+// lane opens its accumulator on the window's first point -- a point of the window, so extremes and first passages are
+// unaffected and a lane without points needs no special case -- and keeps it out of its sum unless it is lane 0.  The
+// lanes are then reduced: (value, index) pairs of the extremes with the smaller index winning a tie, first passages by the
+// smallest index, counts by integer sums, the non-finite flag by a ballot, and the trapezoid partial sums by wave_allsum:
+// the integral of a chain has one summation order, whatever B is.  Lane 0 writes the NE doubles.
+template <class M>
+__global__ void __launch_bounds__(64) k_path_events(int B, int NP, EventArgs e, const int* mask, const double* x, double* out) {
+  constexpr int X = M::X;
+  const int lane = threadIdx.x & 63, c = blockIdx.x;
+  if (c >= B) return;
+  if (mask && !mask[c]) return;
+  const double* xc = x + (size_t)c * NP * X;
+  const double vfirst = event_channel<M>(xc + (size_t)e.p0 * X, e.channel);
+  const double vlast = event_channel<M>(xc + (size_t)e.p1 * X, e.channel);
+  EventAcc a;
+  a.open(e, e.p0, vfirst);
+  if (lane) a.sum = 0.0;
+  for (int p = e.p0 + lane; p <= e.p1; p += 64) {
+    if (p == e.p0) continue;
+    const double v = event_channel<M>(xc + (size_t)p * X, e.channel);
+    const double prev = event_channel<M>(xc + (size_t)(p - 1) * X, e.channel);
+    a.add(e, p, v, prev);
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const double vx = __shfl_xor(a.vmax, m, 64), vn = __shfl_xor(a.vmin, m, 64);
+    const int ix = __shfl_xor(a.imax, m, 64), in = __shfl_xor(a.imin, m, 64);
+    if (vx > a.vmax || (vx == a.vmax && ix < a.imax)) a.vmax = vx, a.imax = ix;
+    if (vn < a.vmin || (vn == a.vmin && in < a.imin)) a.vmin = vn, a.imin = in;
+#pragma unroll
+    for (int l = 0; l < kEventLevels; ++l)
+      if (l < e.L) {
+        a.up[l] += __shfl_xor(a.up[l], m, 64);
+        a.above[l] += __shfl_xor(a.above[l], m, 64);
+        const int f = __shfl_xor(a.first[l], m, 64);
+        if (f >= 0 && (a.first[l] < 0 || f < a.first[l])) a.first[l] = f;
+      }
+  }
+  const bool bad = __ballot(a.bad != 0) != 0ULL;
+  const double sum = wave_allsum(a.sum);
+  if (lane == 0)
+    event_write(e, out + (size_t)c * (5 + 3 * e.L), bad, a.vmax, a.imax, a.vmin, a.imin, sum, vfirst, vlast, a.up, a.first,
+                a.above);
 }
 
 // (An LDS-staged variant of the forward scan -- 8 lanes fetching one block's 128-byte tile, tiles parked in LDS with a

@@ -151,7 +151,7 @@ class DynamicTransition:
 
 def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0, total_chains=None, n_head=6,
                         trace_dir=None, trace_func=None, callback=None, per_chain_step_size=True, path_posterior=None,
-                        groups=None, n_groups=None, predictive=None, **kw):
+                        groups=None, n_groups=None, predictive=None, path_events=None, **kw):
     """Momentum refresh -> dynamic transition -> partition switch, `n_iter` times for all chains of `ctx`, with
     dual-averaging step-size adaptation on the tree's accept statistic during warm-up: the reference's sampling loop
     (scripts/utils.py:292-306, 338-365), batched.  As in Mici every chain adapts its own step size during warm-up (the
@@ -168,7 +168,10 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     gives the numbers of the call without `groups`).  Needs per_chain_step_size.
     predictive: a `paths.PredictivePosterior` of `ctx`; after warm-up every state (after the partition switch) gets
     `predictive.update(seed, it, chain_offset)`, out["predictive"] is its `pooled()` result and, with `groups`,
-    out["predictive_groups"] the list of the G groups' pooled results."""
+    out["predictive_groups"] the list of the G groups' pooled results.
+    path_events: a `paths.PathEvents` of `ctx`; after warm-up every state (after the partition switch) gets `update()`,
+    out["path_events"] is [n_main, B, NE] and out["path_events_summary"] `traces.summarize` of it under the object's `names`
+    (per group with `groups`)."""
     import time
     from .sampling import (DualAveragingStepSize, PerChainDualAveragingStepSize, _mean_over_all_chains,
                            _group_sums_over_all_chains, check_groups)
@@ -183,6 +186,7 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     if n_adapt > 0:
         adapter = PerChainDualAveragingStepSize(step_size, B) if per_chain_step_size else DualAveragingStepSize(step_size)
     heads = np.empty((n_iter, B, n_head))
+    event_draws = []
     acc_hist, eps_hist, nstep_hist = np.empty(n_iter), np.empty(n_iter), np.empty(n_iter)
     err_hist = np.empty(n_iter)
     # per chain, main phase (after warm-up): transitions that moved the chain / did not, trees ended by an integrator error,
@@ -201,6 +205,8 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
             path_posterior.update()
         if predictive is not None and it >= n_adapt:
             predictive.update(seed, it, chain_offset)
+        if path_events is not None and it >= n_adapt:
+            event_draws.append(path_events.update())
         heads[it] = ctx.get_head(n_head)
         if trace_dir is not None:
             from .traces import TraceWriter
@@ -246,6 +252,12 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
         out["group_step_sizes"] = group_eps
     if path_posterior is not None:
         out["path_posterior"] = path_posterior.pooled()
+    if path_events is not None:
+        from .traces import summarize
+        ev = np.stack(event_draws) if event_draws else np.empty((0, B, path_events.NE))
+        out["path_events"] = ev
+        out["path_events_summary"] = summarize({k: ev[:, :, i].T for i, k in enumerate(path_events.names)}, path_events.names,
+                                               groups=groups)
     if predictive is not None:
         out["predictive"] = predictive.pooled()
         if groups is not None:

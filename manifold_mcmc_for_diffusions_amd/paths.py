@@ -44,6 +44,108 @@ def merge_ranks(acc):
     return out
 
 
+def merge_moments_per_entry(a, b):
+    """merge_moments with a count per entry: (n, mean, m2) arrays of one shape; entries with n_b == 0 keep a's numbers and
+    entries with n_a == 0 take b's."""
+    na, ma, sa = a
+    nb, mb, sb = b
+    n = na + nb
+    fa, fb = na.astype(np.float64), nb.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = mb - ma
+        mean = ma + d * (fb / n)
+        m2 = sa + sb + d * d * (fa * fb / n)
+    mean = np.where(nb == 0, ma, np.where(na == 0, mb, mean))
+    m2 = np.where(nb == 0, sa, np.where(na == 0, sb, m2))
+    return n, mean, m2
+
+
+def merge_ranks_per_entry(acc):
+    """Under torch.distributed with more than one rank: the ranks' per-entry (n, mean, m2) merged in rank order."""
+    try:
+        import torch
+        import torch.distributed as dist
+    except ImportError:
+        return acc
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return acc
+    dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
+    t = torch.from_numpy(np.concatenate([acc[0].astype(np.float64), acc[1], acc[2]])).to(dev)
+    parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, t)
+    k = len(acc[0])
+    out = (np.zeros(k, dtype=np.int64), np.zeros(k), np.zeros(k))
+    for p in parts:
+        p = p.cpu().numpy()
+        out = merge_moments_per_entry(out, (np.rint(p[:k]).astype(np.int64), p[k:2 * k], p[2 * k:]))
+    return out
+
+
+def event_names(n_thresholds):
+    """The labels of the NE = 5 + 3 L entries of an event vector (include/chmc.h)."""
+    names = ["max", "t_max", "min", "t_min", "integral"]
+    for l in range(n_thresholds):
+        names += [f"upcross_{l}", f"t_first_{l}", f"time_above_{l}"]
+    return names
+
+
+def _event_thresholds(thresholds):
+    th = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    if len(th) > 8 or not (np.diff(th) > 0).all() or np.isnan(th).any():
+        raise ValueError("thresholds must be at most 8 increasing numbers")
+    return th
+
+
+class PathEvents:
+    """Path-wise events of the latent path of every chain's current state (chmc_path_events_device, include/chmc.h):
+    extremes and their times, the trapezoid integral and, per threshold, up-crossings, first passage and time above, of
+    one channel (a state component, or X for obs_func(x)) over the inclusive window (p0, p1) of points at `stride` (None:
+    the whole path).  `update` returns [B, NE] host doubles, small enough to trace like the head components.
+    path_posterior: a `PathPosterior` of the same stride whose scratch path of its LAST update is evaluated instead of
+    scanning the path again (call its update first)."""
+
+    def __init__(self, ctx, channel, thresholds=(), stride=1, window=None, path_posterior=None):
+        self.ctx, self.channel, self.stride = ctx, int(channel), int(stride)
+        self.thresholds = _event_thresholds(thresholds)
+        self.NP = ctx.path_points(self.stride)[0]
+        self.times = np.arange(self.NP) * (self.stride * (ctx._obs_interval / ctx.S))  # t_p = p h, the library's product
+        self.window = (0, self.NP - 1) if window is None else (int(window[0]), int(window[1]))
+        if not 0 <= self.channel <= ctx.X:
+            raise ValueError("channel must be in [0, X] (X: obs_func(x))")
+        if not 0 <= self.window[0] <= self.window[1] < self.NP:
+            raise ValueError("window must satisfy 0 <= p0 <= p1 < NP")
+        if path_posterior is not None and (path_posterior.ctx is not ctx or path_posterior.stride != self.stride):
+            raise ValueError("path_posterior must belong to the same context and have the same stride")
+        self.path_posterior = path_posterior
+        self.names = event_names(len(self.thresholds))
+        self.NE = len(self.names)
+        B = ctx.B
+        self._hip = ctx.L.chmc_backend() == b"hip:gfx950"
+        if self._hip:  # torch-ROCm tensors; the library works on their pointers
+            import torch
+            dev = torch.device("cuda", ctx.device)
+            self._ev = torch.zeros((B, self.NE), dtype=torch.float64, device=dev)
+            self._x = None if path_posterior is not None else torch.zeros((B, self.NP, ctx.X), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)
+        else:  # the library's "device" is host memory (the emulation build of the tests)
+            self._ev = np.zeros((B, self.NE))
+            self._x = None if path_posterior is not None else np.zeros((B, self.NP, ctx.X))
+
+    def _ptr(self, a):
+        return a.data_ptr() if self._hip else a.ctypes.data
+
+    def update(self, mask=None):
+        """[B, NE]: the events of every chain's current path (rows of chains with mask[c] == 0 keep their last values)."""
+        if self.path_posterior is not None:
+            x_ptr = self.path_posterior._ptr("x")
+        else:
+            self.ctx.generate_x_seq_device(self.stride, self._ptr(self._x))
+            x_ptr = self._ptr(self._x)
+        self.ctx.path_events_device(x_ptr, self.NP, self.stride, self.channel, self.window[0], self.window[1],
+                                    self.thresholds, self._ptr(self._ev), mask=mask)
+        return self._ev.cpu().numpy() if self._hip else self._ev.copy()
+
+
 class PathPosterior:
     def __init__(self, ctx, stride=1):
         self.ctx, self.stride = ctx, int(stride)
@@ -127,9 +229,14 @@ class PredictivePosterior:
     `n_rep` replicate futures of each chain's current state over `horizon` observation intervals -- origin "end": beyond
     the last observation (a forecast); "start": from x_0 (replicated data; horizon = T and stride = S give data sets for a
     posterior predictive check) -- and folds them into running moments per (chain, point, channel) and, with `levels`, into
-    counts of y_rep <= level.  Channels: the X state components, obs_func(x), y_rep = obs_func(x) + sigma eps."""
+    counts of y_rep <= level.  Channels: the X state components, obs_func(x), y_rep = obs_func(x) + sigma eps.
+    events = dict(channel=, thresholds=(), window=None): every replicate's path-wise event vector (chmc_predict_events_device:
+    extremes, integral, per threshold up-crossings, first passage, time above; of one channel, X + 1 = y_rep, over the
+    inclusive window (p0, p1) of emitted points, None: all) folded per chain and entry over its finite values
+    (`event_moments`, `pooled()["events"]`); keep_events: also the raw vectors of the last update (`last_events`)."""
 
-    def __init__(self, ctx, horizon, stride=None, n_rep=64, origin="end", levels=None, n_keep=0):
+    def __init__(self, ctx, horizon, stride=None, n_rep=64, origin="end", levels=None, n_keep=0, events=None,
+                 keep_events=False):
         if origin not in ("end", "start"):
             raise ValueError('origin must be "end" (forecast) or "start" (replication)')
         self.ctx, self.horizon, self.n_rep, self.n_keep = ctx, int(horizon), int(n_rep), int(n_keep)
@@ -149,6 +256,25 @@ class PredictivePosterior:
             f64["paths"] = (B, self.n_keep, self.NPF, self.XC)
         if nl:
             i64["cdf"] = (B, self.NPF, nl)
+        self.events = None
+        if events is not None:
+            unknown = set(events) - {"channel", "thresholds", "window"}
+            if unknown or "channel" not in events:
+                raise ValueError("events must be dict(channel=, thresholds=(), window=None)")
+            win = events.get("window")
+            win = (0, self.NPF - 1) if win is None else (int(win[0]), int(win[1]))
+            th = _event_thresholds(events.get("thresholds", ()))
+            if not 0 <= int(events["channel"]) < self.XC or not 0 <= win[0] <= win[1] < self.NPF:
+                raise ValueError("events: channel must be in [0, X + 1] and the window 0 <= p0 <= p1 < NPF")
+            self.events = dict(channel=int(events["channel"]), thresholds=th, window=win)
+            self.event_names = event_names(len(th))
+            ne = len(self.event_names)
+            f64.update(emean=(B, ne), em2=(B, ne))
+            i64["en"] = (B, ne)
+            if keep_events:
+                f64["events"] = (B, self.n_rep, ne)
+        elif keep_events:
+            raise ValueError("keep_events needs events=")
         if ctx.L.chmc_backend() == b"hip:gfx950":  # torch-ROCm tensors; the library works on their pointers
             import torch
             dev = torch.device("cuda", ctx.device)
@@ -166,9 +292,47 @@ class PredictivePosterior:
     def update(self, seed, draw, chain_offset=0, mask=None):
         """n_rep replicates of every chain's current state (chains with mask[c] != 0; None: all), keyed by (seed, draw,
         chain_offset + c): a chain's replicates do not depend on how the chains are sharded."""
-        self.ctx.predict_device(seed, draw, chain_offset, self.horizon, self.stride, self.origin, self.n_rep, self._ptr("n"),
-                                self._ptr("mean"), self._ptr("m2"), mask=mask, levels=self.levels,
-                                cdf_dev_ptr=self._ptr("cdf"), paths_dev_ptr=self._ptr("paths"), n_keep=self.n_keep)
+        kw = dict(mask=mask, levels=self.levels, cdf_dev_ptr=self._ptr("cdf"), paths_dev_ptr=self._ptr("paths"),
+                  n_keep=self.n_keep)
+        if self.events is None:
+            self.ctx.predict_device(seed, draw, chain_offset, self.horizon, self.stride, self.origin, self.n_rep,
+                                    self._ptr("n"), self._ptr("mean"), self._ptr("m2"), **kw)
+        else:
+            ev = self.events
+            self.ctx.predict_events_device(seed, draw, chain_offset, self.horizon, self.stride, self.origin, self.n_rep,
+                                           self._ptr("n"), self._ptr("mean"), self._ptr("m2"), ev["channel"], ev["window"][0],
+                                           ev["window"][1], ev["thresholds"], self._ptr("en"), self._ptr("emean"),
+                                           self._ptr("em2"), events_dev_ptr=self._ptr("events"), **kw)
+
+    def _need_events(self):
+        if self.events is None:
+            raise ValueError("no events were asked for (events=)")
+
+    def event_moments(self):
+        """en [B, NE] (finite values per chain and entry), emean, em2 [B, NE] as they stand on the device."""
+        self._need_events()
+        return self._host("en"), self._host("emean"), self._host("em2")
+
+    def last_events(self):
+        """[B, n_rep, NE]: the replicates' event vectors of the last update."""
+        self._need_events()
+        if "events" not in self._buf:
+            raise ValueError("no events are kept (keep_events=False)")
+        return self._host("events")
+
+    def _pool_events(self, chains, across_ranks, nn):
+        en, emean, em2 = self.event_moments()
+        ne = en.shape[1]
+        acc = (np.zeros(ne, dtype=np.int64), np.zeros(ne), np.zeros(ne))
+        for c in chains:  # in chain order, every entry with its own count
+            acc = merge_moments_per_entry(acc, (en[c], emean[c], em2[c]))
+        if across_ranks:
+            acc = merge_ranks_per_entry(acc)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            var = np.where(acc[0] > 1, acc[2] / (acc[0] - 1), np.nan)
+            mean = np.where(acc[0] > 0, acc[1], np.nan)
+            reached = acc[0] / nn if nn else np.full(ne, np.nan)
+        return dict(names=list(self.event_names), n=acc[0], mean=mean, var=var, m2=acc[2], reached=reached)
 
     def last_paths(self):
         """[B, n_keep, NPF, X + 2]: the first n_keep replicates of the last update."""
@@ -216,6 +380,8 @@ class PredictivePosterior:
             if across_ranks:
                 cnt = sum_ranks(cnt)
             out["cdf"] = cnt / nn if nn else np.full(cnt.shape, np.nan)
+        if self.events is not None:  # reached: the share of replicate paths whose entry is finite (t_first: P(reached))
+            out["events"] = self._pool_events(chains, across_ranks, nn)
         return out
 
     def cdf(self):
@@ -242,11 +408,18 @@ class PredictivePosterior:
 
     def save(self, directory):
         """`predictive.npz` in `directory`: times, per-chain n and means, pooled n, mean and sd, and with levels the levels and
-        the pooled CDF."""
+        the pooled CDF, and with events their names, per-chain counts and means and the pooled n, mean, var and reached."""
         os.makedirs(directory, exist_ok=True)
         n, mean, _ = self.per_chain()
         pool = self.pooled()
         extra = {} if self.levels is None else dict(levels=self.levels, cdf=pool["cdf"])
+        if self.events is not None:
+            en, emean, _ = self.event_moments()
+            ev = pool["events"]
+            extra.update(event_names=np.array(self.event_names), event_channel=self.events["channel"],
+                         event_window=np.array(self.events["window"]), event_thresholds=self.events["thresholds"],
+                         event_chain_n=en, event_chain_mean=emean, event_n=ev["n"], event_mean=ev["mean"],
+                         event_var=ev["var"], event_reached=ev["reached"])
         path = os.path.join(directory, "predictive.npz")
         np.savez(path, times=self.times, horizon=self.horizon, stride=self.stride, origin=self.origin, n_rep=self.n_rep, n=n,
                  chain_mean=mean, pooled_n=pool["n"], mean=pool["mean"], sd=pool["sd"], **extra)

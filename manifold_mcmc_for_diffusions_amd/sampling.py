@@ -111,7 +111,8 @@ def check_groups(groups, n_groups, num_chains):
 def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_adapt=0, solver=None, rng=None,
                        n_head=6, callback=None, trace_dir=None, trace_func=None, total_chains=None,
                        jitter_length=False, metric_adapter=None, metric_window=0.75, metric_skip=0.25,
-                       path_posterior=None, groups=None, n_groups=None, metric_per_group=False, predictive=None):
+                       path_posterior=None, groups=None, n_groups=None, metric_per_group=False, predictive=None,
+                       path_events=None):
     """Runs n_iter transitions on all chains of `ctx`; returns traces of the first `n_head` position components
     ([n_iter, B, n_head]), accept statistics and the step size used.  Directions are sampled per chain and
     transition (forward / backward in time), failed trajectories are rejected.
@@ -145,7 +146,10 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     every group's dual averaging restarts from that group's current step size, and out["metric_M_0"] is [G, U, U].
     predictive: a `paths.PredictivePosterior` of `ctx`; after warm-up every state (after the partition switch) gets
     `predictive.update(seed, it, chain_offset)`, out["predictive"] is its `pooled()` result and, with `groups`,
-    out["predictive_groups"] the list of the G groups' pooled results."""
+    out["predictive_groups"] the list of the G groups' pooled results.
+    path_events: a `paths.PathEvents` of `ctx`; after warm-up every state (after the partition switch) gets `update()`,
+    out["path_events"] is [n_main, B, NE] and out["path_events_summary"] `traces.summarize` of it under the object's `names`
+    (per group with `groups`)."""
     if metric_per_group and (groups is None or metric_adapter is None):
         raise ValueError("metric_per_group needs groups and a metric_adapter")
     group_metrics = None
@@ -179,6 +183,7 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     # not converge (status 1), diverged (2), non-reversible step (3)] -- the diagnosis of a chain that does not move
     outcome = np.zeros((B, 5), dtype=np.int64)
     heads = np.empty((n_iter, B, n_head))
+    event_draws = []
     acc_hist, eps_hist, fail_hist = np.empty(n_iter), np.empty(n_iter), np.empty(n_iter)
     if groups is not None:
         eps_hist, group_acc_hist = np.empty((n_iter, G)), np.empty((n_iter, G))
@@ -221,6 +226,8 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
             path_posterior.update()
         if predictive is not None and it >= n_adapt:
             predictive.update(seed, it, chain_offset)
+        if path_events is not None and it >= n_adapt:
+            event_draws.append(path_events.update())
         heads[it] = ctx.get_head(n_head)
         if trace_dir is not None:
             vals = {k: np.asarray(v) for k, v in trace_func(heads[it], ctx.hamiltonian()[:, 0]).items()}
@@ -265,6 +272,12 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
         out["group_accept_stat"] = group_acc_hist
     if path_posterior is not None:
         out["path_posterior"] = path_posterior.pooled()
+    if path_events is not None:
+        from .traces import summarize
+        ev = np.stack(event_draws) if event_draws else np.empty((0, B, path_events.NE))
+        out["path_events"] = ev
+        out["path_events_summary"] = summarize({k: ev[:, :, i].T for i, k in enumerate(path_events.names)}, path_events.names,
+                                               groups=groups)
     if predictive is not None:
         out["predictive"] = predictive.pooled()
         if groups is not None:
