@@ -5,7 +5,15 @@ one sub-sequence of 14 observations, sigma_y = 1): batched initial states by the
 (sde/mici_extensions.py:1679-1801), then batched constrained HMC.
 usage: sir_boarding_school_chmc.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir]
        [--keyed-init] [--chain-offset N] [--total-chains N] [--path-posterior STRIDE] [--forecast DAYS]
-       [--peak] [--exceed COUNT]
+       [--peak] [--exceed COUNT] [--coarse-warmup M]
+--coarse-warmup M: the initial states are found and the warm-up runs in a context with 20 / M steps per observation (M = 2, 4
+or 5); the chains are then carried into the context with 20 steps (resolution.coarse_to_fine_static_chmc: the driving noise
+refined as the same Brownian path, the observation noise solved from the constraint), the step size is re-tuned there over
+a fifth of the warm-up transitions and the main phase runs as without the option.  The printed `n moved by at most` is the
+change of the observation-noise part on arrival, in units of sigma_y.  With these data (counts near 300, sigma_y = 1) the
+Euler-Maruyama path at 10 or 5 steps per day differs from the one at 20 by about 1e2 sigma_y around the peak (measured: 95
+for M = 2, 120 for M = 4), so the chains arrive far from equilibrium and the sampling context has to settle them again:
+here the option shows the mechanics; it pays where `moved` is small (examples/fhn_coarse_to_fine_chmc.py: below 1e-1).
 --peak: the posterior of the infected curve's peak size and the day it falls on: path-wise events of I(t) = obs_func(x) at
 every step of every post-warm-up state (paths.PathEvents, evaluated on the device and traced like the parameters).
 --exceed COUNT (with --forecast): P(the observed count reaches COUNT on some day of the forecast) and the first-passage day,
@@ -33,7 +41,7 @@ from manifold_mcmc_for_diffusions_amd.sampling import sample_static_chmc  # noqa
 
 a = sys.argv[1:]
 opts = {"--keyed-init": False, "--chain-offset": 0, "--total-chains": None, "--path-posterior": None, "--forecast": None,
-        "--peak": False, "--exceed": None}
+        "--peak": False, "--exceed": None, "--coarse-warmup": None}
 FLAGS = ("--keyed-init", "--peak")
 for name in list(opts):
     if name in a:
@@ -42,6 +50,9 @@ for name in list(opts):
         del a[i:i + (1 if name in FLAGS else 2)]
 keyed, chain_offset, total_chains = opts["--keyed-init"], opts["--chain-offset"], opts["--total-chains"]
 path_stride, forecast, peak, exceed = opts["--path-posterior"], opts["--forecast"], opts["--peak"], opts["--exceed"]
+coarse_m = opts["--coarse-warmup"]
+if coarse_m is not None and (coarse_m < 2 or 20 % coarse_m):
+    sys.exit("--coarse-warmup M needs M >= 2 that divides 20")
 if exceed is not None and not forecast:
     sys.exit("--exceed needs --forecast DAYS")
 B = int(a[0]) if len(a) > 0 else 256
@@ -52,7 +63,7 @@ out_dir = a[4] if len(a) > 4 else None
 data = np.load(os.path.join(ROOT, "tests", "golden", "reference_data", "sir_model_boarding_school_data.npz"))
 y, obs_interval = np.asarray(data["y_seq"], dtype=np.float64).reshape(-1), float(data["obs_interval"])
 m = em.sir
-ctx = ChmcContext("sir", obs_interval, 20, 14, y, sigma=1.0, num_chains=B)
+ctx = ChmcContext("sir", obs_interval, 20 // (coarse_m or 1), 14, y, sigma=1.0, num_chains=B)
 print(f"SIR: {B} chains, dim_q = {ctx.Q}, {ctx.num_blocks} sub-sequence of {len(y)} observations, {ctx.RM}-row kernels")
 rng = np.random.default_rng(20200710)
 t0 = time.time()
@@ -73,6 +84,10 @@ def trace_func(head, ham):  # scripts/sir_model_chmc_experiment.py:75-94
             "hamiltonian": ham}
 
 
+coarse = None
+if coarse_m:  # everything below belongs to the sampling context; the warm-up context hands its chains over
+    coarse, ctx = ctx, ctx.sibling(20)
+    print(f"warm-up at {coarse.S} steps per observation (dim_q = {coarse.Q}), sampling at {ctx.S}")
 pp = None
 if path_stride:
     from manifold_mcmc_for_diffusions_amd.paths import PathPosterior
@@ -87,12 +102,27 @@ if peak:
     from manifold_mcmc_for_diffusions_amd.paths import PathEvents
     pe = PathEvents(ctx, ctx.X, stride=path_stride or 1, path_posterior=pp)  # with --path-posterior: on its scratch path
 t0 = time.time()
+if coarse is not None:
+    from manifold_mcmc_for_diffusions_amd.resolution import coarse_to_fine_static_chmc
+
+    def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, n_adapt, **kw):  # noqa: F811
+        """The call below with the warm-up in the coarse context: a fifth of it re-tunes the step size in `ctx`."""
+        n_fine = max(2, n_adapt // 5)
+        return coarse_to_fine_static_chmc(coarse, ctx, max(1, n_adapt - n_fine), n_fine, n_iter - n_adapt, n_step, step_size,
+                                          seed=seed, **kw)
 res = sample_static_chmc(ctx, n_iter, n_step, 0.05, seed=7, n_adapt=n_warm, n_head=5, jitter_length=True, path_posterior=pp,
                          **({} if pred is None else {"predictive": pred}), **({} if pe is None else {"path_events": pe}),
                          chain_offset=chain_offset, total_chains=total_chains if keyed else None,
                          trace_dir=out_dir or os.path.join(ROOT, "gpurun_out", "sir_run"), trace_func=trace_func,
                          callback=lambda it, h, acc, e: (it % 25 == 0) and print(
                              f"  iter {it:4d} accept {acc:.2f} step {e:.3f}", flush=True))
+if coarse is not None:
+    for r in res["rungs"]:
+        print(f"  S = {r['S']:3d}: {r['seconds']:.1f} s, step size {float(r['first_step_size']):.3f} -> "
+              f"{float(r['final_step_size']):.3f}, accept {r['mean_accept_stat']:.2f}"
+              + ("" if r["moved"] is None else f", n moved by at most {r['moved'].max():.1e} on arrival"))
+    n_fine = max(2, n_warm // 5)
+    n_iter, n_warm = n_fine + n_iter - n_warm, n_fine  # (the traces below are the sampling context's)
 el = time.time() - t0
 sm = res["summary"]
 print(f"{n_iter} transitions x <= {n_step} steps x {B} chains in {el:.1f} s; final step size "

@@ -104,6 +104,43 @@ int chmc_get_observations(chmc_ctx* ctx, double* y_seq, double* sigma);
  * posterior (simulation-based calibration needs no initial-state finder and no burn-in). */
 #define CHMC_SIMULATE_DRAW (1ULL << 62) /* (momentum refresh: the transition number; the finders: 2^63 | ...) */
 int chmc_simulate_observations_device(chmc_ctx* ctx, unsigned long long seed, int chain_offset, int partition);
+/* Carrying positions between time resolutions: a context's num_steps_per_obs S is fixed at chmc_create, this call maps
+ * positions of a context with S_src steps per observation interval to positions of `ctx` (the DESTINATION; S_dst = its S),
+ * same model, T and noisy.  q_src_dev [B][U + V0 + T S_src V + (noisy ? T : 0)], q_dst_dev [B][Q], two distinct device
+ * buffers.  u, v_0 and n are copied; v_seq is mapped per coarse step, which covers the m fine steps k = 0 .. m - 1:
+ *   Euler-Maruyama components (SIR's three):       a = m^-1/2 sum_k a_k
+ *   strong-order-1.5 pairs (a, b) = (v[j], v[dim_noise + j]) (both FitzHugh-Nagumo models, one pair), from
+ *   Delta W = sqrt(delta) a = sum_k Delta W_k and
+ *   Delta Z = delta^3/2 (a + b / sqrt 3) / 2 = sum_k Delta Z_k + h sum_k (m - 1 - k) Delta W_k   (h = delta / m):
+ *                                                  a = m^-1/2 sum_k a_k
+ *                                                  b = m^-3/2 sum_k [sqrt(3) (m - 1 - 2 k) a_k + b_k]
+ *   These rows form A, one row per coarse normal, one column per fine normal of the coarse step, A A^T = I.
+ *   S_src = m S_dst (m >= 2):  coarsening  v = A w; deterministic, seed and draw are ignored.
+ *   S_dst = m S_src (m >= 2):  refinement  w = xi + A^T (v - A xi) with fresh xi ~ N(0, I): A w = v exactly -- the fine
+ *     sequence drives a refinement of the SAME Brownian path -- and w ~ N(0, I) whenever v is.  xi of destination
+ *     component j of chain c is column j of the keyed row of chmc_fill_normal* for (seed, stream = chain_offset + c,
+ *     draw = CHMC_RESAMPLE_DRAW | draw), draw < 2^45 (the columns of u, v_0 and n go unused): bit 60 is disjoint from the
+ *     momentum refresh, CHMC_PREDICT_DRAW (bit 61), CHMC_SIMULATE_DRAW (bit 62) and the finders (bit 63).
+ *   S_src = S_dst:  a copy.  Any other ratio is an error; m need not be a power of two and may exceed 64.
+ * The sums over k in A xi and A w are formed in ascending k whatever the launch geometry, so a chain's result depends on
+ * (seed, draw, chain_offset + c) and its own row alone: any sharding gives the same bits.  Rows of chains with mask[c] == 0
+ * (host [B]; NULL = all chains) are not touched.  The chain state of `ctx` is neither read nor changed.
+ * Errors: NULL buffers, S_src < 1, S_src and S_dst not in an integer ratio, draw >= 2^45, chain_offset < 0. */
+#define CHMC_RESAMPLE_DRAW (1ULL << 60)
+int chmc_resample_q_device(chmc_ctx* ctx, const void* q_src_dev, int S_src, unsigned long long seed,
+                           unsigned long long draw, int chain_offset, const int* mask, void* q_dst_dev);
+/* A refined position is not on the fine manifold: the fine path differs from the coarse one by the discretisation error at
+ * the observation times.  With observation noise (noisy == 1 or 2) the constraint fixes n, so the point is placed exactly,
+ * without a solver.  For every chain c, from row c of q_dev [B][Q] (device):
+ *   x_obs_seq = the path of the row at the observation times (scanned from q itself, never from a stored x_obs_seq);
+ *   n_t := (y_t - obs_func(x(t_obs))) / sigma_c   (sigma_c: the context's, the chain's own after chmc_set_observations,
+ *   or exp(u[dim_z]) for noisy == 2); pos = the row with this n; mom = 0, the given partition, and the state caches
+ *   evaluated as by chmc_set_state: the state is bitwise that of chmc_set_state(q', NULL, x_obs', partition) for the
+ *   q', x_obs' chmc_get_state returns.  Every observation row and every state row of the constraint is zero to rounding.
+ *   moved[c] = max_t |n_t new - n_t given| (host [B]; may be NULL).
+ * A context WITHOUT observation noise (noisy == 0) is not supported and returns an error: there x_obs_seq must satisfy
+ * obs_func(x) = y and is part of the constraint's definition; moving it is a separate design, out of scope here. */
+int chmc_set_state_solve_noise_device(chmc_ctx* ctx, const void* q_dev, int partition, double* moved);
 /* find_initial_state_by_linear_interpolation (sde/mici_extensions.py:1479-1547) for all chains at once, on the
  * device: given u [B][U], v_0 [B][V0] and full states at the observation times x_obs_seq_init [B][T][X]
  * (generate_x_obs_seq_init of the scripts), solves per time step for the noise increments that make the discretised

@@ -39,6 +39,9 @@ SYMBOLS = [
     ("chmc_set_observations", C.c_int, [C.c_void_p, dp, dp]),
     ("chmc_get_observations", C.c_int, [C.c_void_p, dp, dp]),
     ("chmc_simulate_observations_device", C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]),
+    ("chmc_resample_q_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_int, ip,
+                                         C.c_void_p]),
+    ("chmc_set_state_solve_noise_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, dp]),
     ("chmc_init_linear_interpolation", C.c_int, [C.c_void_p, dp, dp, dp, C.c_int]),
     ("chmc_set_metric", C.c_int, [C.c_void_p, dp]),
     ("chmc_set_metrics", C.c_int, [C.c_void_p, dp]),

@@ -61,6 +61,8 @@ class ChmcContext:
         self.sigma = sigma
         self.device = int(device)
         self._obs_interval = float(obs_interval)
+        self._model, self._num_obs_per_subseq = model, num_obs_per_subseq  # (sibling)
+        self._use_gaussian_splitting = bool(use_gaussian_splitting)
         self.partition = 0
         self.blocks = []
         keys = ("obs0", "nobs", "first", "last", "row0", "nrows", "ny", "col0", "ncols", "step0", "nsteps", "_")
@@ -104,6 +106,42 @@ class ChmcContext:
         y, sg = np.empty((self.B, self.T)), np.empty(self.B)
         check(self.L.chmc_get_observations(self.h, ptr(y), ptr(sg)), "chmc_get_observations")
         return y, sg
+
+    # ---- carrying chains between time resolutions (chmc_resample_q_device, chmc_set_state_solve_noise_device; resolution.py)
+    def sibling(self, num_steps_per_obs):
+        """A new context with `num_steps_per_obs` steps per observation interval and everything else as here: model, T, R,
+        obs_interval, noise kind, splitting, B and device, the per-chain observations and the metric (per chain or shared)."""
+        sigma = self.sigma
+        if sigma is not None and not isinstance(sigma, str) and np.ndim(sigma) > 0:
+            sigma = float(np.asarray(sigma)[0])  # (the chains' own levels follow with the observations)
+        sib = ChmcContext(self._model, self._obs_interval, int(num_steps_per_obs), self._num_obs_per_subseq, self._y,
+                          sigma=sigma, use_gaussian_splitting=self._use_gaussian_splitting, num_chains=self.B,
+                          device=self.device)
+        if self.per_chain_observations:
+            y, sg = self.observations()
+            sib.set_observations(y, sg if self.noisy and not self.variable_sigma else None)
+        if self.M_0 is not None:
+            sib.set_metric(self.M_0)
+        return sib
+
+    def resample_q_device(self, q_src_dev_ptr, S_src, seed, q_dst_dev_ptr, draw=0, chain_offset=0, mask=None):
+        """Positions q_src [B, U + V0 + T S_src V (+ T)] of a context with S_src steps per interval (device) -> positions
+        q_dst [B, Q] of this one (device): refined with fresh keyed normals (S = m S_src), coarsened (S_src = m S) or copied
+        (chmc_resample_q_device, include/chmc.h).  Rows of chains with mask[c] == 0 are not touched."""
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        check(self.L.chmc_resample_q_device(self.h, C.c_void_p(q_src_dev_ptr), int(S_src), int(seed), int(draw),
+                                            int(chain_offset), iptr(m), C.c_void_p(q_dst_dev_ptr)),
+              "chmc_resample_q_device")
+
+    def set_state_solve_noise(self, q_dev_ptr, partition=0):
+        """The rows of q [B, Q] (device) become the chains' states with the observation-noise part n solved from the
+        constraint, n_t = (y_t - obs_func(x_t)) / sigma, momentum 0 (chmc_set_state_solve_noise_device, include/chmc.h;
+        contexts with observation noise only).  Returns moved [B] = max_t |n_t new - n_t given|."""
+        moved = np.empty(self.B)
+        check(self.L.chmc_set_state_solve_noise_device(self.h, C.c_void_p(q_dev_ptr), int(partition), ptr(moved)),
+              "chmc_set_state_solve_noise_device")
+        self.partition = int(partition)
+        return moved
 
     def close(self):
         if getattr(self, "h", None):

@@ -1726,6 +1726,73 @@ extern "C" int chmc_simulate_observations_device(chmc_ctx* ctx, unsigned long lo
   ctx->mom_tangent = true;  // zero momentum
   CHMC_LEAVE("chmc_simulate_observations_device")
 }
+// The map between time resolutions (include/chmc.h): positions of a context with S_src steps per interval -> positions of
+// this one; resample_pass picks the kernel
+extern "C" int chmc_resample_q_device(chmc_ctx* ctx, const void* q_src_dev, int S_src, unsigned long long seed,
+                                      unsigned long long draw, int chain_offset, const int* mask, void* q_dst_dev) {
+  CHMC_ENTER("chmc_resample_q_device")
+  const std::string fn = "chmc_resample_q_device";
+  if (!q_src_dev || !q_dst_dev) return fail(fn + ": null argument");
+  if (S_src < 1) return fail(fn + ": S_src must be at least 1");
+  if (draw >= (1ULL << 45)) return fail(fn + ": draw must be below 2^45");
+  if (chain_offset < 0) return fail(fn + ": negative chain_offset");
+  const Sys& sy = ctx->sy;
+  const int S_big = S_src > sy.S ? S_src : sy.S, S_small = S_src > sy.S ? sy.S : S_src;
+  if (S_big % S_small != 0)
+    return fail(fn + ": S_src and the context's num_steps_per_obs must be in an integer ratio (non-integer ratios are not supported)");
+  const int NT = sy.noisy ? sy.T : 0;
+  const long long Qs = (long long)sy.U + sy.V0 + (long long)sy.T * S_src * sy.V + NT;
+  if (Qs > 0x7fffffffLL || (long long)sy.B * sy.T * S_big > 0x7fffffffLL) return fail(fn + ": too many steps for one call");
+  if (S_src == sy.S) {  // a copy of the rows asked for
+    for (int c0 = 0; c0 < sy.B;) {
+      int c1 = c0;
+      while (c1 < sy.B && (!mask || mask[c1])) ++c1;
+      if (c1 > c0) d2d((double*)q_dst_dev + (size_t)c0 * sy.Q, (const double*)q_src_dev + (size_t)c0 * sy.Q, sizeof(double) * (size_t)(c1 - c0) * sy.Q);
+      c0 = c1 + 1;
+    }
+    CHMC_LEAVE("chmc_resample_q_device")
+  }
+  if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)sy.B);
+  ResampleArgs a{};
+  a.seed = seed, a.key = CHMC_RESAMPLE_DRAW | draw, a.chain_offset = chain_offset;
+  a.B = sy.B, a.U = sy.U, a.V0 = sy.V0, a.T = sy.T, a.NT = NT;
+  a.Sc = S_small, a.m = S_big / S_small, a.refine = sy.S > S_src;
+  a.Qs = Qs, a.Qd = sy.Q;
+  a.src = (const double*)q_src_dev, a.dst = (double*)q_dst_dev;
+  if (mask) {
+    int* d_mask = ctx->d_path_ints + sy.B;
+    h2d(d_mask, mask, sizeof(int) * sy.B);
+    a.mask = d_mask;
+  }
+  dispatch(ctx, [&](auto inst) { resample_pass<typename decltype(inst)::M>(ctx, a); });
+  CHMC_LEAVE("chmc_resample_q_device")
+}
+// A position placed on the manifold of the chain's data through its observation-noise part (include/chmc.h): the sequence
+// of chmc_simulate_observations_device with n solved for in place of y -- the path scan from q, one small per-chain kernel
+// (KSolveNoise), then chmc_set_state's evaluation
+extern "C" int chmc_set_state_solve_noise_device(chmc_ctx* ctx, const void* q_dev, int partition, double* moved) {
+  CHMC_ENTER("chmc_set_state_solve_noise_device")
+  const std::string fn = "chmc_set_state_solve_noise_device";
+  if (!q_dev) return fail(fn + ": null argument");
+  if (partition < 0 || partition >= ctx->num_partition) return fail(fn + ": partition out of range");
+  const Sys& sy = ctx->sy;
+  if (!sy.noisy)
+    return fail(fn + ": a context without observation noise is not supported (x_obs_seq is part of the constraint there; "
+                     "placing a refined state in it is out of scope)");
+  const size_t n = sizeof(double) * (size_t)sy.B * sy.Q;
+  dev_zero(ctx->sl.cur, sizeof(int) * sy.B);
+  d2d(ctx->sl.q[0], q_dev, n);
+  dev_zero(ctx->sl.p[0], n);
+  update_x_obs(ctx);  // x_obs_seq of the given positions
+  dispatch(ctx, [&](auto inst) { launch(KSolveNoise<typename decltype(inst)::M>{sy, ctx->sl, ctx->d_xobs, ctx->d_ham}, sy.B, 8); });
+  if (moved) d2h(moved, ctx->d_ham, sizeof(double) * sy.B);
+  select_partition(ctx, partition);
+  begin_all(ctx, nullptr, nullptr);
+  state_eval(ctx, 0);
+  ctx->have_state = true;
+  ctx->mom_tangent = true;  // zero momentum
+  CHMC_LEAVE("chmc_set_state_solve_noise_device")
+}
 // "Deal a try into a row" for the device-resident finder (init.py): keyed start points, zero moments and gradient, and the
 // row's carried scan guess back to the cold guess of a new context, so that every evaluation of a try depends on that try's
 // own (point, previous iterate) only, whichever row it runs in and whatever ran there before

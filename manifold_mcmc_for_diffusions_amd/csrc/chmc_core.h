@@ -3589,4 +3589,154 @@ struct KGdAdopt {
   }
 };
 
+// ------------------------------------------------------------------------------------------
+// The map between time resolutions (chmc_resample_q_device, include/chmc.h).  One coarse step of length delta covers the m
+// fine steps k = 0 .. m - 1 of length delta / m.  With A the matrix that takes the fine normals of a coarse step to the
+// coarse ones -- per Euler-Maruyama component a = m^-1/2 sum_k a_k, per strong-order-1.5 pair (M::NPAIR of them)
+//   a = m^-1/2 sum_k a_k,    b = m^-3/2 sum_k [sqrt(3) (m - 1 - 2 k) a_k + b_k]
+// (the increment Delta W and its time integral Delta Z of the same Brownian path), A A^T = I --
+//   coarsening is v = A w,   refinement is w = xi + A^T (v - A xi) with fresh xi ~ N(0, I):  A w = v exactly.
+// The arithmetic is the three functions below, shared by the functor form (KResample, a work item per coarse step) and by
+// the wave kernel (k_resample, chmc_wave.h: a lane per fine step).  Every multiply-add is an explicit fma and every sum over
+// k runs in ascending k, so that the two forms give the same bits whatever the launch geometry is.
+struct ResampleArgs {
+  unsigned long long seed, key;  // key = CHMC_RESAMPLE_DRAW | draw: xi of destination column j is normal j of that keyed row
+  int chain_offset;
+  int B, U, V0, T, NT;  // NT: length of the n part (T with observation noise, else 0)
+  int Sc, m;            // coarse steps per observation interval; the fine side has m Sc
+  int refine;           // 1: src coarse, dst fine; 0: src fine, dst coarse
+  long long Qs, Qd;     // row lengths of src and dst
+  const int* mask;      // [B] or null
+  const double* src;
+  double* dst;
+};
+template <class M>
+struct ResampleSum {  // A x of one coarse step: add() the fine steps k = 0, 1, .. in order, then close() for A x itself
+  double s[M::V];
+  CHMC_HD CHMC_FI inline void open() {
+    CHMC_UNROLL
+    for (int i = 0; i < M::V; ++i) s[i] = 0.0;
+  }
+  CHMC_HD CHMC_FI inline void add(int m, int k, const double* x) {
+    constexpr int NP = M::NPAIR;
+    const double ck = 1.7320508075688772935 * (double)(m - 1 - 2 * k);
+    CHMC_UNROLL
+    for (int j = 0; j < NP; ++j) {
+      s[j] += x[j];
+      s[NP + j] += fma(ck, x[j], x[NP + j]);
+    }
+    CHMC_UNROLL
+    for (int i = 2 * NP; i < M::V; ++i) s[i] += x[i];
+  }
+  CHMC_HD CHMC_FI inline void close(int m) {
+    constexpr int NP = M::NPAIR;
+    const double rm = 1.0 / sqrt((double)m), rm3 = rm / (double)m;
+    CHMC_UNROLL
+    for (int i = 0; i < M::V; ++i) s[i] *= (i >= NP && i < 2 * NP) ? rm3 : rm;
+  }
+};
+// r = the rows' weights times (v - A xi): what resample_spread adds to the fine normals of every step of the coarse one.
+// `ax`: the sums over xi, NOT closed -- the weight enters v - A xi through the fma, so no product is left next to a
+// difference for the compiler to contract or not
+template <class M>
+CHMC_HD CHMC_FI inline void resample_residual(int m, const double* v, const ResampleSum<M>& ax, double* r) {
+  constexpr int NP = M::NPAIR;
+  const double rm = 1.0 / sqrt((double)m), rm3 = rm / (double)m;
+  CHMC_UNROLL
+  for (int i = 0; i < M::V; ++i) {
+    const double wgt = (i >= NP && i < 2 * NP) ? rm3 : rm;
+    r[i] = wgt * fma(-wgt, ax.s[i], v[i]);
+  }
+}
+// x += (A^T (v - A xi)) at fine step k
+template <class M>
+CHMC_HD CHMC_FI inline void resample_spread(int m, int k, const double* r, double* x) {
+  constexpr int NP = M::NPAIR;
+  const double ck = 1.7320508075688772935 * (double)(m - 1 - 2 * k);
+  CHMC_UNROLL
+  for (int j = 0; j < NP; ++j) {
+    x[j] += fma(ck, r[NP + j], r[j]);
+    x[NP + j] += r[NP + j];
+  }
+  CHMC_UNROLL
+  for (int i = 2 * NP; i < M::V; ++i) x[i] += r[i];
+}
+// the V fresh normals of the destination columns col .. col + V - 1 (a pair of the stream is drawn once while both of its
+// normals are read)
+template <class M>
+CHMC_HD CHMC_FI inline void resample_xi(NormalCursor& cur, uint32_t col, double* x) {
+  CHMC_UNROLL
+  for (int i = 0; i < M::V; ++i) x[i] = cur.at(col + (uint32_t)i);
+}
+// u, v_0 and n go through unchanged: entries i, i + stride, .. of the two ends of a row
+CHMC_HD inline void resample_copy_ends(const ResampleArgs& a, const double* src, double* dst, int i0, int stride) {
+  const int head = a.U + a.V0;
+  for (int i = i0; i < head; i += stride) dst[i] = src[i];
+  const double* ns = src + (a.Qs - a.NT);
+  double* nd = dst + (a.Qd - a.NT);
+  for (int i = i0; i < a.NT; i += stride) nd[i] = ns[i];
+}
+// the functor form: a work item per (chain, coarse step); refinement draws the step's xi twice (for A xi, then for w)
+template <class M>
+struct KResample {
+  ResampleArgs a;
+  CHMC_HD void operator()(int tid) const {
+    constexpr int V = M::V;
+    const int NS = a.T * a.Sc, m = a.m;
+    const int c = tid / NS, s = tid - c * NS;
+    if (a.mask && !a.mask[c]) return;
+    const double* src = a.src + (size_t)c * (size_t)a.Qs;
+    double* dst = a.dst + (size_t)c * (size_t)a.Qd;
+    const int head = a.U + a.V0;
+    if (s == 0) resample_copy_ends(a, src, dst, 0, 1);
+    ResampleSum<M> ax;
+    ax.open();
+    if (!a.refine) {
+      const double* w = src + head + (size_t)s * m * V;
+      for (int k = 0; k < m; ++k) ax.add(m, k, w + (size_t)k * V);
+      ax.close(m);
+      for (int i = 0; i < V; ++i) dst[head + (size_t)s * V + i] = ax.s[i];
+      return;
+    }
+    NormalCursor cur;
+    cur.open(a.seed, a.key, (uint32_t)(a.chain_offset + c));
+    const uint32_t col0 = (uint32_t)head + (uint32_t)s * (uint32_t)m * (uint32_t)V;
+    double x[V], r[V];
+    for (int k = 0; k < m; ++k) {
+      resample_xi<M>(cur, col0 + (uint32_t)k * V, x);
+      ax.add(m, k, x);
+    }
+    resample_residual<M>(m, src + head + (size_t)s * V, ax, r);
+    for (int k = 0; k < m; ++k) {
+      resample_xi<M>(cur, col0 + (uint32_t)k * V, x);
+      resample_spread<M>(m, k, r, x);
+      for (int i = 0; i < V; ++i) dst[col0 + (size_t)k * V + i] = x[i];
+    }
+  }
+};
+// chmc_set_state_solve_noise_device: with observation noise the constraint fixes n, so a position is put on the manifold
+// of the chain's data by n_t := (y_t - obs_func(x_t)) / sigma_c from x_obs_seq of the position itself (KXobs); one work item
+// per chain, moved[c] = max_t |n_t new - n_t given|
+template <class M>
+struct KSolveNoise {
+  Sys sy;
+  Slots sl;
+  const double* xobs;
+  double* moved;  // [B]
+  CHMC_HD void operator()(int c) const {
+    double* q = pick(sl.q, sl.cur[c]) + (size_t)c * sy.Q;
+    const double sg = sigma_at(sy, q, c);
+    const double* y = y_of(sy, c);
+    double* n = q + sy.U + sy.NV;
+    double mv = 0.0;
+    for (int t = 0; t < sy.T; ++t) {
+      const double nn = (y[t] - M::obs(xobs + ((size_t)c * sy.T + t) * M::X)) / sg;
+      const double d = fabs(nn - n[t]);
+      mv = d > mv || d != d ? d : mv;
+      n[t] = nn;
+    }
+    moved[c] = mv;
+  }
+};
+
 }  // namespace chmc

@@ -9,6 +9,9 @@
 namespace chmc {
 
 struct FhnModel {
+  // driving noise of a step: NPAIR strong-order-1.5 pairs (a, b) = (v[j], v[NPAIR + j]), the rest Euler-Maruyama singles
+  // (the map between time resolutions, resample_* in chmc_core.h)
+  static constexpr int NPAIR = 1;
   static constexpr int ID = 0, X = CHMC_FHN_X, V = CHMC_FHN_V, Z = CHMC_FHN_Z, V0 = CHMC_FHN_V0, NK = CHMC_FHN_NK;
   static constexpr int NABS = 0;     // no absorbing components
   CHMC_HD static bool absorbed(double) { return false; }
@@ -40,6 +43,7 @@ struct FhnModel {
 // FitzHugh-Nagumo with the priors of the reference's notebook (FitzHugh-Nagumo_example.ipynb cells 7-18): same
 // one-step map, different generate_z / generate_x_0.
 struct FhnNbModel {
+  static constexpr int NPAIR = 1;
   static constexpr int ID = 2, X = CHMC_FHNNB_X, V = CHMC_FHNNB_V, Z = CHMC_FHNNB_Z, V0 = CHMC_FHNNB_V0, NK = CHMC_FHNNB_NK;
   static constexpr int NABS = 0;     // no absorbing components
   CHMC_HD static bool absorbed(double) { return false; }
@@ -72,6 +76,7 @@ struct FhnNbModel {
 // below at -500 before a step and a clipped component keeps its (clipped) value
 // (sde/example_models/sir.py:54-70); derivatives through a clipped component are zero.
 struct SirModel {
+  static constexpr int NPAIR = 0;    // three Euler-Maruyama components
   static constexpr int ID = 1, X = CHMC_SIR_X, V = CHMC_SIR_V, Z = CHMC_SIR_Z, V0 = CHMC_SIR_V0, NK = CHMC_SIR_NK;
   static constexpr int NXI = X + V + Z;
   static constexpr int U = Z;        // dim_u: the global parameters (fixed observation noise)

@@ -91,6 +91,12 @@ template <class M>
 static void path_events_seq(chmc_ctx* c, int NP, const EventArgs& e, const int* mask, const double* x, double* out) {
   launch(KPathEvents<M>{NP, e, mask, x, out}, c->sy.B, 7), c->diag[15]++;
 }
+// the map between time resolutions by the generic functor: one work item per (chain, coarse step)
+template <class M>
+static void resample_seq(chmc_ctx* c, const ResampleArgs& a) {
+  (void)c;
+  launch(KResample<M>{a}, (long)a.B * a.T * a.Sc, 8);
+}
 
 #ifdef CHMC_WAVE_KERNELS
 constexpr bool kWaveKernels = true;  // PlanInput::wave_kernels of every context of this build
@@ -121,6 +127,17 @@ template <class M>
 static void path_events_pass(chmc_ctx* c, int NP, const EventArgs& e, const int* mask, const double* x, double* out) {
   if (!c->plan.pb_allocated) return path_events_seq<M>(c, NP, e, mask, x, out);
   launch_blocks(k_path_events<M>, (long)c->sy.B, 64, 7, c->sy.B, NP, e, mask, x, out), c->diag[14]++;
+}
+// chmc_resample_q_device: workgroups of 256 lanes over tiles of a chain where the library keeps the compact rows
+// (path_scan's rule), the functor form under CHMC_COMPACT_ROWS=0.  A tile: 256 coarse steps (coarsening), 256 / m whole
+// coarse steps (refinement by m <= 256: a lane per fine step), one coarse step (m > 256)
+template <class M>
+static void resample_pass(chmc_ctx* c, const ResampleArgs& a) {
+  if (!c->plan.pb_allocated) return resample_seq<M>(c, a);
+  const long NS = (long)a.T * a.Sc;
+  const int nseg = !a.refine ? 256 : a.m <= 256 ? 256 / a.m : 1;
+  const long ntile = (NS + nseg - 1) / nseg;
+  launch_blocks(k_resample<M>, (long)a.B * ntile, 256, 8, a, nseg, (int)ntile);
 }
 // chain-level Woodbury solve: one wavefront per chain up to 64 blocks
 template <class M, int RM, int SYM, int TGT>
@@ -554,6 +571,10 @@ static void predict_events_pass(chmc_ctx* c, const PredictArgs& a, const EventAr
 template <class M>
 static void path_events_pass(chmc_ctx* c, int NP, const EventArgs& e, const int* mask, const double* x, double* out) {
   path_events_seq<M>(c, NP, e, mask, x, out);
+}
+template <class M>
+static void resample_pass(chmc_ctx* c, const ResampleArgs& a) {
+  resample_seq<M>(c, a);
 }
 template <class M, int RM>
 static void nld_sweeps(chmc_ctx*, const Sys&, int, int, double*) { no_wave_kernels("the comparator target"); }

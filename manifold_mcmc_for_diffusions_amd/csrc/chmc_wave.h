@@ -5905,6 +5905,108 @@ __global__ void __launch_bounds__(64) k_path_events(int B, int NP, EventArgs e, 
                 a.above);
 }
 
+// The map between time resolutions (chmc_resample_q_device; the arithmetic is chmc_core.h's resample_*).  A workgroup of 256
+// lanes takes a tile of one chain; tile 0 also copies u, v_0 and n.
+//   refine, m <= 256: a lane per FINE step, so that a wavefront stores consecutive doubles.  A tile is nseg = 256 / m whole
+//     coarse steps ("segments" of m lanes; the remaining 256 - nseg m lanes idle), so no segment straddles a workgroup and m
+//     need neither divide 64 nor stay below it.  Every lane draws the xi of its step once (a Philox pair per two columns)
+//     and parks it in LDS; the segment's first lane forms A xi over the m parked entries in ascending k -- the order of the
+//     functor form -- and parks the residual; every lane then adds its row of A^T to the xi it kept in registers.
+//   refine, m > 256: a tile is one coarse step, walked in chunks of 256 fine steps.  xi is parked in the destination row
+//     itself (each lane reads back what it wrote), lane 0 carries A xi across the chunks.
+//   coarsen: a lane per COARSE step sums its m fine steps in ascending k (reads m V doubles, stores V).
+template <class M>
+__global__ void __launch_bounds__(256) k_resample(ResampleArgs a, int nseg, int ntile) {
+  constexpr int V = M::V;
+  __shared__ double sx[256 * V];
+  __shared__ double sr[256 * V];
+  const int tid = threadIdx.x, m = a.m;
+  const int c = blockIdx.x / ntile, tile = blockIdx.x - c * ntile;
+  if (c >= a.B) return;
+  if (a.mask && !a.mask[c]) return;  // uniform per workgroup
+  const double* src = a.src + (size_t)c * (size_t)a.Qs;
+  double* dst = a.dst + (size_t)c * (size_t)a.Qd;
+  const int NS = a.T * a.Sc, head = a.U + a.V0;
+  if (tile == 0) resample_copy_ends(a, src, dst, tid, 256);
+  if (!a.refine) {
+    const int s = tile * 256 + tid;
+    if (s >= NS) return;
+    ResampleSum<M> ax;
+    ax.open();
+    const double* w = src + head + (size_t)s * m * V;
+    for (int k = 0; k < m; ++k) ax.add(m, k, w + (size_t)k * V);
+    ax.close(m);
+#pragma unroll
+    for (int i = 0; i < V; ++i) dst[head + (size_t)s * V + i] = ax.s[i];
+    return;
+  }
+  NormalCursor cur;
+  cur.open(a.seed, a.key, (uint32_t)(a.chain_offset + c));
+  double x[V], r[V];
+  if (m <= 256) {
+    const int seg = tid / m, k = tid - seg * m;
+    const int s = tile * nseg + seg;
+    const bool on = seg < nseg && s < NS;
+    const uint32_t col = (uint32_t)head + ((uint32_t)s * (uint32_t)m + (uint32_t)k) * (uint32_t)V;
+    if (on) {
+      resample_xi<M>(cur, col, x);
+#pragma unroll
+      for (int i = 0; i < V; ++i) sx[tid * V + i] = x[i];
+    }
+    __syncthreads();
+    if (on && k == 0) {
+      ResampleSum<M> ax;
+      ax.open();
+      for (int kk = 0; kk < m; ++kk) ax.add(m, kk, sx + (tid + kk) * V);
+      resample_residual<M>(m, src + head + (size_t)s * V, ax, r);
+#pragma unroll
+      for (int i = 0; i < V; ++i) sr[seg * V + i] = r[i];
+    }
+    __syncthreads();
+    if (on) {
+#pragma unroll
+      for (int i = 0; i < V; ++i) r[i] = sr[seg * V + i];
+      resample_spread<M>(m, k, r, x);
+#pragma unroll
+      for (int i = 0; i < V; ++i) dst[col + i] = x[i];
+    }
+    return;
+  }
+  const int s = tile;  // (nseg == 1, ntile == NS)
+  const uint32_t col0 = (uint32_t)head + (uint32_t)s * (uint32_t)m * (uint32_t)V;
+  ResampleSum<M> ax;
+  ax.open();
+  for (int k0 = 0; k0 < m; k0 += 256) {
+    const int k = k0 + tid;
+    if (k < m) {
+      resample_xi<M>(cur, col0 + (uint32_t)k * V, x);
+#pragma unroll
+      for (int i = 0; i < V; ++i) sx[tid * V + i] = x[i], dst[col0 + (size_t)k * V + i] = x[i];
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const int n = m - k0 < 256 ? m - k0 : 256;
+      for (int kk = 0; kk < n; ++kk) ax.add(m, k0 + kk, sx + kk * V);
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    resample_residual<M>(m, src + head + (size_t)s * V, ax, r);
+#pragma unroll
+    for (int i = 0; i < V; ++i) sr[i] = r[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < V; ++i) r[i] = sr[i];
+  for (int k = tid; k < m; k += 256) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) x[i] = dst[col0 + (size_t)k * V + i];
+    resample_spread<M>(m, k, r, x);
+#pragma unroll
+    for (int i = 0; i < V; ++i) dst[col0 + (size_t)k * V + i] = x[i];
+  }
+}
+
 // (An LDS-staged variant of the forward scan -- 8 lanes fetching one block's 128-byte tile, tiles parked in LDS with a
 // 144-byte row stride, trajectory tiles written back the same way -- was built and measured at 2x the time of the
 // plain lane-per-block scan of chmc_core.h: with one wavefront per SIMD the extra LDS round trips sit on the
