@@ -5,7 +5,15 @@ one sub-sequence of 14 observations, sigma_y = 1): batched initial states by the
 (sde/mici_extensions.py:1679-1801), then batched constrained HMC.
 usage: sir_boarding_school_chmc.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir]
        [--keyed-init] [--chain-offset N] [--total-chains N] [--path-posterior STRIDE] [--forecast DAYS]
-       [--peak] [--exceed COUNT] [--coarse-warmup M]
+       [--peak] [--exceed COUNT] [--coarse-warmup M] [--sequential K]
+--sequential K: the data arrive a day at a time.  The first K days are fitted as usual (finder, warm-up, main phase); every
+later day is added by sequential.sequential_static_chmc: the chains are carried into a context with one more observation
+(64 keyed forecast candidates per chain, weighed by the count that arrived, one drawn in proportion to its weight), the step
+size is re-tuned over a fifth of the warm-up transitions and the main phase runs again.  Per day the table shows the log
+predictive score of that day's count given the days before (log-mean-exp over the chains), the candidates' effective sample
+size (median and minimum over the chains), `moved` (the change of the observation-noise part on arrival, in units of
+sigma_y), the re-tuned step size, the main-phase accept statistic and the seconds; with --forecast also the one-day-ahead
+forecast band of that day's count from the fit of the days before.  The other options are ignored.
 --coarse-warmup M: the initial states are found and the warm-up runs in a context with 20 / M steps per observation (M = 2, 4
 or 5); the chains are then carried into the context with 20 steps (resolution.coarse_to_fine_static_chmc: the driving noise
 refined as the same Brownian path, the observation noise solved from the constraint), the step size is re-tuned there over
@@ -41,7 +49,7 @@ from manifold_mcmc_for_diffusions_amd.sampling import sample_static_chmc  # noqa
 
 a = sys.argv[1:]
 opts = {"--keyed-init": False, "--chain-offset": 0, "--total-chains": None, "--path-posterior": None, "--forecast": None,
-        "--peak": False, "--exceed": None, "--coarse-warmup": None}
+        "--peak": False, "--exceed": None, "--coarse-warmup": None, "--sequential": None}
 FLAGS = ("--keyed-init", "--peak")
 for name in list(opts):
     if name in a:
@@ -50,7 +58,7 @@ for name in list(opts):
         del a[i:i + (1 if name in FLAGS else 2)]
 keyed, chain_offset, total_chains = opts["--keyed-init"], opts["--chain-offset"], opts["--total-chains"]
 path_stride, forecast, peak, exceed = opts["--path-posterior"], opts["--forecast"], opts["--peak"], opts["--exceed"]
-coarse_m = opts["--coarse-warmup"]
+coarse_m, sequential = opts["--coarse-warmup"], opts["--sequential"]
 if coarse_m is not None and (coarse_m < 2 or 20 % coarse_m):
     sys.exit("--coarse-warmup M needs M >= 2 that divides 20")
 if exceed is not None and not forecast:
@@ -63,6 +71,45 @@ out_dir = a[4] if len(a) > 4 else None
 data = np.load(os.path.join(ROOT, "tests", "golden", "reference_data", "sir_model_boarding_school_data.npz"))
 y, obs_interval = np.asarray(data["y_seq"], dtype=np.float64).reshape(-1), float(data["obs_interval"])
 m = em.sir
+if sequential is not None and not 2 <= sequential < len(y):
+    sys.exit(f"--sequential K needs 2 <= K < {len(y)}")
+if sequential is not None:
+    from manifold_mcmc_for_diffusions_amd.paths import PredictivePosterior
+    from manifold_mcmc_for_diffusions_amd.sequential import sequential_static_chmc
+    K = sequential
+    ctx = ChmcContext("sir", obs_interval, 20, None, y[:K], sigma=1.0, num_chains=B)
+    print(f"SIR, sequential: {B} chains, days 1-{K} fitted first (dim_q = {ctx.Q}), then a day at a time to day {len(y)}")
+    t0 = time.time()
+    q, xo, tries = init.find_initial_states_by_gradient_descent_noisy_system(
+        ctx, np.random.default_rng(20200710), adam_step_size=1e-1, max_iters=5000, log=print)
+    print(f"initial states in {time.time() - t0:.1f} s, |c|max {np.abs(ctx.constr()).max():.1e}")
+    bands = {}
+
+    def stage_kw(i, c):  # the one-day-ahead forecast of the next day's count from this stage's fit
+        if not forecast or c.T == len(y):
+            return {}
+        bands[c.T + 1] = PredictivePosterior(c, 1, n_rep=64, levels=np.arange(0.0, 801.0, 2.0))
+        return {"predictive": bands[c.T + 1]}
+
+    t0 = time.time()
+    res = sequential_static_chmc(ctx, [y[d:d + 1] for d in range(K, len(y))], n_warm, max(2, n_warm // 5), n_iter - n_warm,
+                                 n_step, 0.05, seed=7, n_cand=64, stage_kw=stage_kw, n_head=5, jitter_length=True)
+    print(f"days {K + 1}-{len(y)} added in {time.time() - t0:.1f} s including the first fit "
+          f"({res['stages'][0]['seconds']:.1f} s, step size {float(res['stages'][0]['final_step_size']):.3f}, accept "
+          f"{res['stages'][0]['mean_accept_stat']:.2f})")
+    print("   day  count  log_pred  ESS med  min   moved    step  accept  seconds" + ("   forecast E +- sd     5 %    50 %    95 %" if forecast else ""))
+    for st in res["stages"][1:]:
+        row = (f"  {st['T']:4d} {y[st['T'] - 1]:6.0f} {st['log_pred']:9.2f} {np.median(st['ess_cand']):8.1f} {st['ess_cand'].min():4.1f} "
+               f"{st['moved'].max():7.1e} {float(st['final_step_size']):7.3f} {st['mean_accept_stat']:7.2f} {st['seconds']:8.1f}")
+        if forecast and st["T"] in bands:
+            pool = bands[st["T"]].pooled()
+            qs = bands[st["T"]].quantiles([0.05, 0.5, 0.95], cdf=pool["cdf"])
+            row += f"   {pool['mean'][0, -1]:7.1f} +- {pool['sd'][0, -1]:5.1f} {qs[0, 0]:7.1f} {qs[0, 1]:7.1f} {qs[0, 2]:7.1f}"
+        print(row)
+    total = sum(st["log_pred"] for st in res["stages"][1:])
+    print(f"log p(y_{K + 1}..{len(y)} | y_1..{K}) = {total:.2f} (sum of the days' scores); final max |constraint| "
+          f"{np.abs(res['ctx'].constr()).max():.1e}")
+    sys.exit(0)
 ctx = ChmcContext("sir", obs_interval, 20 // (coarse_m or 1), 14, y, sigma=1.0, num_chains=B)
 print(f"SIR: {B} chains, dim_q = {ctx.Q}, {ctx.num_blocks} sub-sequence of {len(y)} observations, {ctx.RM}-row kernels")
 rng = np.random.default_rng(20200710)

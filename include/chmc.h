@@ -329,6 +329,47 @@ int chmc_predict_device(chmc_ctx* ctx, unsigned long long seed, unsigned long lo
                         int stride, int origin, int n_rep, const int* mask, int n_levels, const double* levels, void* n_dev,
                         void* mean_dev, void* m2_dev, void* cdf_dev, void* paths_dev, int n_keep);
 
+/* Scoring observations that arrived behind the fit, and a state for the longer record.  A context's num_obs T is fixed at
+ * chmc_create; this call, on the context that holds the fit of y_1..T, weighs forecast candidates by the H = horizon
+ * observations y_future [B][H] (host) that arrived next.  For chain c, with sigma_c as chmc_predict_device defines it:
+ *   candidates  r = 0 .. n_cand - 1 is forecast replicate r of chmc_predict_device(seed, draw, chain_offset, horizon,
+ *               stride = S, origin = 0): the same start state x_T (rebuilt from the position by the path scan, never read
+ *               from x_obs_seq), the same keyed stream (seed, chain_offset + c, CHMC_PREDICT_DRAW | draw << 16 | r) and the
+ *               same recursion, so o_p^r = obs_func(x) at point p = 1 .. H has the same bits; the eps part of the stream is
+ *               not used.
+ *   weights     n_p^r = (y_future[c][p-1] - o_p^r) / sigma_c;
+ *               logw_r = -1/2 sum_p (n_p^r)^2 - H (log sigma_c + 1/2 log 2 pi), the sum in ascending p (each term added by
+ *               one fused multiply-add, the affine map by another); a candidate with a non-finite o_p has logw_r = -inf.
+ *   score       m = max_r logw_r;  s = sum_r exp(logw_r - m) in ascending r, always in that one order;
+ *               log_pred[c] = m + log s - log n_cand  = log p(y_{T+1..T+H} | y_{1..T}, this draw), by n_cand replicates.
+ *               Every candidate -inf: log_pred[c] = -inf, picked[c] = -1, and the chain's tail_dev row is not written.
+ *   pick        z = normal 0 of the keyed row (seed, chain_offset + c, CHMC_FUTURE_DRAW | draw) of chmc_fill_normal*;
+ *               u = Phi(z) = 1/2 erfc(-z / sqrt 2); picked[c] = the smallest r whose running sum of exp(logw_r' - m) over
+ *               r' <= r exceeds u s (if rounding leaves none: the last candidate with a finite weight) -- a candidate drawn in
+ *               proportion to its weight.
+ *   tail        row c of tail_dev [B][H S V + H] = [ v of the picked candidate: the H S V step normals, the bits
+ *               chmc_fill_normal* returns for its key | n_p of the picked candidate (H) ].  Spliced behind the chain's
+ *               [u | v_0 | v_seq] and [n], it is a position of the context with T + H observations whose observation-noise
+ *               part already solves the new constraint rows to rounding (chmc_set_state_solve_noise_device places it).
+ * Bit 59: CHMC_FUTURE_DRAW | draw, draw < 2^45, has bits 60 - 63 clear and is therefore disjoint from CHMC_RESAMPLE_DRAW
+ * (bit 60), CHMC_PREDICT_DRAW (bit 61; its draw << 16 reaches bit 60 but never clears bit 61), CHMC_SIMULATE_DRAW (bit 62)
+ * and the finders (bit 63); the momentum refresh uses the transition number, far below 2^59.
+ * log_pred [B] and picked [B] (may be NULL) are host arrays; logw_dev [B][n_cand] (may be NULL) receives the weights;
+ * tail_dev may be NULL.  mask (host [B], NULL = all): no buffer of a chain with mask[c] == 0, nor its log_pred / picked
+ * entry, is touched.  A chain's outputs depend on (seed, draw, chain_offset + c), its own state and its own data alone: any
+ * sharding of the chains gives the same bits.  The chain state is not changed.
+ * Two forms: a work item per (chain, candidate) (KFutureScore, the default: the faster one at every measured shape, DESIGN.md
+ * section 4.13) and, under CHMC_FUTURE_WAVE=1 where the compact rows are allocated, a wavefront per (chain, group of 64
+ * candidates) with a lane per candidate (k_future_score).  Neither reduces over candidates and both use the same
+ * accumulator, so the two forms give the same bits.
+ * Errors: no state set; noisy == 0 (not supported: without observation noise the weights are degenerate and placing the
+ * state is a projection, out of scope as in chmc_set_state_solve_noise_device); horizon < 1; n_cand outside [1, 65536];
+ * draw >= 2^45; chain_offset < 0; a NULL y_future or log_pred; a non-finite y_future. */
+#define CHMC_FUTURE_DRAW (1ULL << 59)
+int chmc_score_future_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset, int horizon,
+                             const double* y_future, int n_cand, const int* mask, double* log_pred, int* picked,
+                             void* logw_dev, void* tail_dev);
+
 /* Path-wise event summaries on the device: functionals of one whole path (its peak and the time of it, first passages,
  * up-crossings, integrals), which no pointwise summary gives.
  * The event vector.  Inputs: one channel's values v_p at the points p0 <= p <= p1 (an inclusive window of point indices),
@@ -570,8 +611,10 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *                  on the current states with the compact rows allocated)
  *   out80[75]      launches of the sequential path scan (KPath: a caller's q, or CHMC_COMPACT_ROWS=0)
  *   out80[76]      launches of the predictive wave kernel (k_predict, k_predict_events: chmc_predict_device /
- *                  chmc_predict_events_device with the compact rows on)
- *   out80[77]      launches of the predictive functor form (KPredict, KPredictEvents: CHMC_COMPACT_ROWS=0)
+ *                  chmc_predict_events_device with the compact rows on), and of k_future_score (chmc_score_future_device under
+ *                  CHMC_FUTURE_WAVE=1: the same recursion and geometry; no slot is free for a counter of its own)
+ *   out80[77]      launches of the predictive functor form (KPredict, KPredictEvents: CHMC_COMPACT_ROWS=0), and of
+ *                  KFutureScore (chmc_score_future_device's default)
  *   out80[78]      launches of the path-events wave kernel (k_path_events: chmc_path_events_device, compact rows on)
  *   out80[79]      launches of the path-events functor form (KPathEvents: CHMC_COMPACT_ROWS=0)
  * Synchronises the context's stream. */

@@ -17,6 +17,7 @@ from .system import (  # noqa: F401
     conditioned_diffusion_neg_log_dens_and_grad, generate_from_model)
 from .paths import PathPosterior  # noqa: F401
 from .resolution import transfer_state, coarse_to_fine_static_chmc  # noqa: F401
+from .sequential import extend_state, sequential_static_chmc  # noqa: F401
 from .init import find_initial_states_by_gradient_descent, fhn_x_obs_seq_init  # noqa: F401
 from .integrators import ConstrainedLeapfrogIntegrator  # noqa: F401
 from .adapters import OnlineBlockDiagonalMetricAdapter  # noqa: F401

@@ -75,6 +75,8 @@ SYMBOLS = [
     ("chmc_predict_points", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, dp]),
     ("chmc_predict_device", C.c_int, [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       ip, C.c_int, dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    ("chmc_score_future_device", C.c_int, [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, dp, C.c_int, ip, dp, ip,
+                                           C.c_void_p, C.c_void_p]),
     ("chmc_path_events_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, ip,
                                           C.c_void_p]),
     ("chmc_predict_events_device", C.c_int, [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int,

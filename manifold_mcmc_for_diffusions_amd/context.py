@@ -400,6 +400,56 @@ class ChmcContext:
                                          C.c_void_p(cdf_dev_ptr), C.c_void_p(paths_dev_ptr), int(n_keep)),
               "chmc_predict_device")
 
+    # ---- scoring arrived observations and carrying chains to a longer record (chmc_score_future_device; sequential.py)
+    def score_future_device(self, seed, draw, chain_offset, y_future, n_cand=64, mask=None, logw_dev_ptr=None,
+                            tail_dev_ptr=None, log_pred=None, picked=None):
+        """n_cand keyed forecast candidates of every chain's current state over the next H observation intervals, weighed by
+        the observations y_future [H] or [B, H] that arrived (chmc_score_future_device, include/chmc.h).  Returns
+        (log_pred [B], picked [B]); logw_dev_ptr [B, n_cand] and tail_dev_ptr [B, H S V + H] are optional device buffers.
+        log_pred / picked: arrays to write into (the entries of chains with mask[c] == 0 are left as they are)."""
+        y = as_c(y_future)
+        if y.ndim == 1:
+            y = as_c(np.broadcast_to(y, (self.B, y.shape[0])))
+        if y.ndim != 2 or y.shape[0] != self.B:
+            raise ValueError(f"y_future must have shape (H,) or ({self.B}, H), got {y.shape}")
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        lp = np.full(self.B, np.nan) if log_pred is None else log_pred
+        pk = np.full(self.B, -2, dtype=np.int32) if picked is None else picked
+        if lp.dtype != np.float64 or pk.dtype != np.int32 or lp.shape != (self.B,) or pk.shape != (self.B,) or \
+                not lp.flags.c_contiguous or not pk.flags.c_contiguous:
+            raise ValueError(f"log_pred must be float64 [{self.B}] and picked int32 [{self.B}]")
+        check(self.L.chmc_score_future_device(self.h, int(seed), int(draw), int(chain_offset), int(y.shape[1]), ptr(y),
+                                              int(n_cand), iptr(m), ptr(lp), iptr(pk), C.c_void_p(logw_dev_ptr),
+                                              C.c_void_p(tail_dev_ptr)), "chmc_score_future_device")
+        return lp, pk
+
+    def extended(self, y_new):
+        """A new context with T + H observations: this context's data, shared or per chain, with y_new [H] or [B, H]
+        appended, and everything else as `sibling` carries it: model, S, R, obs_interval, noise kind and the chains' own
+        sigma, splitting, B, device and the metric (per chain or shared)."""
+        y_new = np.asarray(y_new, dtype=np.float64)
+        if y_new.ndim == 3 and y_new.shape[2] == 1:
+            y_new = y_new[:, :, 0]
+        if y_new.ndim not in (1, 2) or y_new.shape[-1] < 1 or (y_new.ndim == 2 and y_new.shape[0] != self.B):
+            raise ValueError(f"y_new must have shape (H,) or ({self.B}, H), got {y_new.shape}")
+        sigma = self.sigma
+        if sigma is not None and not isinstance(sigma, str) and np.ndim(sigma) > 0:
+            sigma = float(np.asarray(sigma)[0])  # (the chains' own levels follow with the observations)
+        per_chain = self.per_chain_observations or y_new.ndim == 2
+        if per_chain:
+            y_old, sg = self.observations()
+            y_all = np.concatenate([y_old, np.broadcast_to(y_new, (self.B, y_new.shape[-1]))], 1)
+        else:
+            y_all = np.concatenate([self._y, y_new])
+        ext = ChmcContext(self._model, self._obs_interval, self.S, self._num_obs_per_subseq, y_all[0] if per_chain else y_all,
+                          sigma=sigma, use_gaussian_splitting=self._use_gaussian_splitting, num_chains=self.B,
+                          device=self.device)
+        if per_chain:
+            ext.set_observations(y_all, sg if self.per_chain_observations and self.noisy and not self.variable_sigma else None)
+        if self.M_0 is not None:
+            ext.set_metric(self.M_0)
+        return ext
+
     # ---- path-wise events (chmc_path_events_device, chmc_predict_events_device; paths.PathEvents / PredictivePosterior)
     def path_events_device(self, x_seq_dev_ptr, n_points, stride, channel, p0, p1, thresholds, events_dev_ptr, mask=None):
         """The event vectors [B][5 + 3 L] of one channel of the device path buffer x_seq [B][n_points][X] over the points

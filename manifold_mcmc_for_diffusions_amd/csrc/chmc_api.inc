@@ -59,6 +59,8 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   size_t d_pred_lev_cap = 0;
   double* d_pred_ev = nullptr;      // chmc_predict_events_device: [NPF] point times, then the raw events where the caller keeps none
   size_t d_pred_ev_cap = 0;
+  double* d_fut = nullptr;          // chmc_score_future_device: [B][H] y_future, [B] log_pred, [B] ints picked (padded to doubles),
+  size_t d_fut_cap = 0;             // then [B][n_cand][H] the candidates' n and, where the caller keeps none, [B][n_cand] logw
   TreeState tree{};                                     // chmc_tree_begin / _subtree / _step: per-chain tree decisions
   bool have_tree = false;
   bool rows_fresh = false;  // Slots::Jv holds the full rows of the current states (see ensure_rows)
@@ -1340,6 +1342,67 @@ extern "C" int chmc_predict_events_device(chmc_ctx* ctx, unsigned long long seed
   const PredictEventCall ev{channel, p0, p1, n_thresholds, thresholds, events_dev, en_dev, emean_dev, em2_dev};
   return predict_call(ctx, "chmc_predict_events_device", seed, draw, chain_offset, horizon, stride, origin, n_rep, mask,
                       n_levels, levels, n_dev, mean_dev, m2_dev, cdf_dev, paths_dev, n_keep, &ev);
+}
+
+// scoring observations that arrived behind the fit (include/chmc.h): the forecast candidates of chmc_predict_device at
+// stride S weighed by y_future; future_pass picks the kernel, future_pick scores, picks and fills the tail; ONE read-back of
+// [B] log_pred and [B] picked
+extern "C" int chmc_score_future_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset,
+                                        int horizon, const double* y_future, int n_cand, const int* mask, double* log_pred,
+                                        int* picked, void* logw_dev, void* tail_dev) {
+  CHMC_ENTER("chmc_score_future_device")
+  const std::string fn = "chmc_score_future_device";
+  if (!y_future || !log_pred) return fail(fn + ": null argument");
+  const Sys& sy = ctx->sy;
+  if (predict_check(ctx, fn.c_str(), horizon, sy.S, 0)) return -1;
+  if (!ctx->have_state) return fail(fn + ": no state has been set");
+  if (!sy.noisy)
+    return fail(fn + ": a context without observation noise is not supported (the weights are degenerate there and placing "
+                     "the state is a projection; out of scope)");
+  if (n_cand < 1 || n_cand > 65536) return fail(fn + ": n_cand must be in [1, 65536]");
+  if ((long long)sy.B * n_cand >= (1LL << 31) || (long long)sy.B * ((long long)horizon * sy.S * sy.V + horizon) >= (1LL << 31))
+    return fail(fn + ": chains x candidates and chains x tail length must stay below 2^31");
+  if (draw >= (1ULL << 45)) return fail(fn + ": draw must be below 2^45");
+  if (chain_offset < 0) return fail(fn + ": negative chain_offset");
+  const size_t nBH = (size_t)sy.B * horizon;
+  for (size_t i = 0; i < nBH; ++i)
+    if (!(y_future[i] - y_future[i] == 0.0)) return fail(fn + ": y_future must be finite");
+  if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)sy.B);
+  // scratch: y | log_pred | picked | n of every candidate | logw where the caller keeps none
+  const size_t nB = (size_t)sy.B, nC = nB * n_cand, nI = (nB + 1) / 2;
+  const size_t need = nBH + nB + nI + nC * horizon + (logw_dev ? 0 : nC);
+  if (ctx->d_fut_cap < need) ctx->d_fut = alloc<double>(ctx, need), ctx->d_fut_cap = need;
+  double* d_y = ctx->d_fut;
+  double* d_lp = d_y + nBH;
+  int* d_pk = reinterpret_cast<int*>(d_lp + nB);
+  h2d(d_y, y_future, sizeof(double) * nBH);
+  PredictArgs a{};
+  a.seed = seed, a.key0 = CHMC_PREDICT_DRAW | (draw << 16);
+  a.chain_offset = chain_offset, a.HS = horizon * sy.S, a.stride = sy.S, a.NPF = horizon;
+  a.n_rep = n_cand;
+  if (!ctx->d_pred_x) ctx->d_pred_x = alloc<double>(ctx, (size_t)sy.B * (sy.T + 1) * sy.X);
+  path_run(ctx, nullptr, sy.S, ctx->d_pred_x, nullptr);  // x_T from the position, as the forecast takes it
+  a.xstart = ctx->d_pred_x + (size_t)sy.T * sy.X, a.xld = (long long)(sy.T + 1) * sy.X;
+  if (mask) {
+    int* d_mask = ctx->d_path_ints + sy.B;
+    h2d(d_mask, mask, sizeof(int) * sy.B);
+    a.mask = d_mask;
+  }
+  FutureArgs f{};
+  f.H = horizon, f.n_cand = n_cand, f.y = d_y;
+  f.nscr = d_lp + nB + nI;
+  f.logw = logw_dev ? (double*)logw_dev : f.nscr + nC * horizon;
+  dispatch(ctx, [&](auto inst) { future_pass<typename decltype(inst)::M>(ctx, a, f); });
+  future_pick(ctx, a, f, CHMC_FUTURE_DRAW | draw, d_lp, d_pk, (double*)tail_dev);
+  std::vector<double> h(nB + nI);
+  d2h(h.data(), d_lp, sizeof(double) * (nB + nI));
+  const int* hp = reinterpret_cast<const int*>(h.data() + nB);
+  for (int c = 0; c < sy.B; ++c) {
+    if (mask && !mask[c]) continue;
+    log_pred[c] = h[c];
+    if (picked) picked[c] = hp[c];
+  }
+  CHMC_LEAVE("chmc_score_future_device")
 }
 
 // path-wise events of a path buffer (include/chmc.h): path_events_pass picks the kernel

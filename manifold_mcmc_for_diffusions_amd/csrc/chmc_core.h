@@ -2318,6 +2318,132 @@ struct KPredictFold {
 };
 
 // ------------------------------------------------------------------------------------------
+// Scoring observations that arrived behind the fit (chmc_score_future_device, include/chmc.h): candidate r of chain c is
+// forecast replicate r of chmc_predict_device at stride S -- predict_replicate with the PredictArgs that call builds, the
+// eps part of the stream unread -- weighed by the Gaussian density of y_future around its obs channel.  The candidate's
+// arithmetic is ONE accumulator, FutureAcc, shared by the functor form (KFutureScore, a work item per candidate) and the
+// wave kernel (k_future_score, chmc_wave.h: a lane per candidate); neither reduces over candidates, so the two write the
+// same bits.  The sum of squares and the final affine map are explicit fma calls: no contraction choice is left to the
+// compiler that could differ between the two instantiations.
+#define CHMC_INF (__builtin_huge_val())
+struct FutureArgs {
+  int H, n_cand;
+  const double* y;  // [B][H] on the device
+  double* logw;     // [B][n_cand]
+  double* nscr;     // [B][n_cand][H]: n_p of every candidate
+};
+struct FutureAcc {
+  double ss;
+  int bad;
+  CHMC_HD void open() { ss = 0.0, bad = 0; }
+  // point p (0-based) with obs channel o: returns n_p
+  CHMC_HD CHMC_FI inline double add(double y, double o, double sig) {
+    const double n = (y - o) / sig;
+    if (!(o - o == 0.0)) bad = 1;  // o is not finite
+    ss = fma(n, n, ss);
+    return n;
+  }
+  CHMC_HD CHMC_FI inline double logw(int H, double sig) const {
+    if (bad) return -CHMC_INF;
+    const double cst = (double)H * (log(sig) + 0.91893853320467274178032973640562);  // 1/2 log 2 pi
+    return fma(-0.5, ss, -cst);
+  }
+};
+template <class M>
+struct KFutureScore {
+  Sys sy;
+  Slots sl;
+  PredictArgs a;
+  FutureArgs f;
+  CHMC_HD void operator()(int tid) const {
+    const int c = tid / f.n_cand, r = tid - c * f.n_cand;
+    if (a.mask && !a.mask[c]) return;
+    const double* q = pick(sl.q, sl.cur[c]) + (size_t)c * sy.Q;
+    const double sig = sigma_at(sy, q, c);
+    const double* y = f.y + (size_t)c * f.H;
+    double* ns = f.nscr + ((size_t)c * f.n_cand + r) * f.H;
+    FutureAcc acc;
+    acc.open();
+    predict_replicate<M>(sy, a, q, c, r, [&](int p, const double* ch) { ns[p] = acc.add(y[p], ch[M::X], sig); });
+    f.logw[(size_t)c * f.n_cand + r] = acc.logw(f.H, sig);
+  }
+};
+// Score and pick, a work item per chain (both forms): m = max_r logw_r, s = sum_r exp(logw_r - m) in ascending r,
+// log_pred = m + log s - log n_cand; u = Phi(z) with z normal 0 of the keyed row (seed, chain_offset + c, key); picked = the
+// smallest r whose running sum exceeds u s, else the last candidate with a finite weight; every weight -inf: log_pred = -inf,
+// picked = -1 and the tail row is left alone.  The picked candidate's n row goes behind the H S V normals of the tail row.
+struct KFuturePick {
+  FutureArgs f;
+  unsigned long long seed, key;
+  int chain_offset;
+  const int* mask;
+  double* log_pred;  // [B]
+  int* picked;       // [B]
+  double* tail;      // [B][ld] or null
+  long long ld, nv;  // nv = H S V
+  CHMC_HD void operator()(int c) const {
+    if (mask && !mask[c]) return;
+    const double* lw = f.logw + (size_t)c * f.n_cand;
+    double m = -CHMC_INF;
+    CHMC_UNROLL4
+    for (int r = 0; r < f.n_cand; ++r)
+      if (lw[r] > m) m = lw[r];
+    if (!(m > -CHMC_INF)) {
+      log_pred[c] = -CHMC_INF, picked[c] = -1;
+      return;
+    }
+    double s = 0.0;
+    CHMC_UNROLL4
+    for (int r = 0; r < f.n_cand; ++r) s += exp(lw[r] - m);
+    log_pred[c] = m + log(s) - log((double)f.n_cand);
+    double z, z1;
+    philox_normal_pair(seed, key, (uint32_t)(chain_offset + c), 0u, z, z1);
+    const double u = 0.5 * erfc(-z * 0.70710678118654752440084436210485);
+    const double thr = u * s;
+    int pk = -1, last = -1;
+    double run = 0.0;
+    for (int r = 0; r < f.n_cand; ++r) {
+      if (lw[r] > -CHMC_INF) last = r;
+      run += exp(lw[r] - m);
+      if (run > thr) {
+        pk = r;
+        break;
+      }
+    }
+    if (pk < 0) pk = last;
+    picked[c] = pk;
+    if (tail) {
+      const double* ns = f.nscr + ((size_t)c * f.n_cand + pk) * f.H;
+      double* t = tail + (size_t)c * (size_t)ld + nv;
+      for (int p = 0; p < f.H; ++p) t[p] = ns[p];
+    }
+  }
+};
+// The tail's normals: the H S V step normals of the picked candidate's keyed row, regenerated from the key (KNormalFillRows
+// on a per-chain key): a work item per (chain, component pair).
+struct KFutureTail {
+  unsigned long long seed, key0;
+  int chain_offset;
+  const int* mask;
+  const int* picked;
+  long long nv, ld;
+  double* tail;
+  CHMC_HD void operator()(int tid) const {
+    const long long npair = (nv + 1) / 2;
+    const int c = (int)(tid / npair);
+    const long long j = tid - c * npair;
+    if (mask && !mask[c]) return;
+    const int pk = picked[c];
+    if (pk < 0) return;
+    double n0, n1;
+    philox_normal_pair(seed, key0 | (unsigned long long)pk, (uint32_t)(chain_offset + c), (uint32_t)j, n0, n1);
+    double* p = tail + (size_t)c * (size_t)ld + 2 * j;
+    p[0] = n0;
+    if (2 * j + 1 < nv) p[1] = n1;
+  }
+};
+
+// ------------------------------------------------------------------------------------------
 // Path-wise event summaries (chmc_path_events_device / chmc_predict_events_device, include/chmc.h): extremes, the trapezoid
 // integral and, per threshold, up-crossings, first passage and time above, of ONE channel over an inclusive window of points.
 // The event vector has NE = 5 + 3 L doubles: max, t_max, min, t_min, integral, then per threshold upcross, t_first,

@@ -91,6 +91,20 @@ template <class M>
 static void path_events_seq(chmc_ctx* c, int NP, const EventArgs& e, const int* mask, const double* x, double* out) {
   launch(KPathEvents<M>{NP, e, mask, x, out}, c->sy.B, 7), c->diag[15]++;
 }
+// chmc_score_future_device by the generic functor: a work item per (chain, candidate); counted with the predictive's
+// functor form (every diagnostics slot is taken)
+template <class M>
+static void future_seq(chmc_ctx* c, const PredictArgs& a, const FutureArgs& f) {
+  launch(KFutureScore<M>{c->sy, c->sl, a, f}, (long)c->sy.B * f.n_cand, 7), c->diag[13]++;
+}
+// score, pick and tail of both forms: a work item per chain (KFuturePick), then the picked candidates' normals, a work item
+// per (chain, component pair) (KFutureTail)
+static void future_pick(chmc_ctx* c, const PredictArgs& a, const FutureArgs& f, unsigned long long key, double* log_pred,
+                        int* picked, double* tail) {
+  const long long nv = (long long)a.HS * c->sy.V, ld = nv + f.H;
+  launch(KFuturePick{f, a.seed, key, a.chain_offset, a.mask, log_pred, picked, tail, ld, nv}, c->sy.B, 8);
+  if (tail) launch(KFutureTail{a.seed, a.key0, a.chain_offset, a.mask, picked, nv, ld, tail}, (long)(c->sy.B * ((nv + 1) / 2)), 8);
+}
 // the map between time resolutions by the generic functor: one work item per (chain, coarse step)
 template <class M>
 static void resample_seq(chmc_ctx* c, const ResampleArgs& a) {
@@ -120,6 +134,15 @@ static void predict_events_pass(chmc_ctx* c, const PredictArgs& a, const EventAr
   double* grp = predict_scratch(c, (size_t)c->sy.B * G * a.NPF * (2 * (M::X + 2) + a.n_levels));
   launch_blocks(k_predict_events<M>, (long)c->sy.B * G, 64, 7, c->sy, c->sl, a, grp, e, evraw), c->diag[12]++;
   predict_fold<M>(c, a, 1, grp, n, mean, m2, cdf);
+}
+// chmc_score_future_device: the functor form unless CHMC_FUTURE_WAVE=1 asks for the wave kernel -- a wavefront per (chain,
+// group of 64 candidates), counted with the predictive wave kernel -- where predict_pass's rule allows it (the compact rows
+// are allocated; KernelPlan::future_wave).  Bitwise equal; the functor form was the faster one at every measured shape
+// (profiles/future_score_timing.txt), so it is the default
+template <class M>
+static void future_pass(chmc_ctx* c, const PredictArgs& a, const FutureArgs& f) {
+  if (!c->plan.future_wave) return future_seq<M>(c, a, f);
+  launch_blocks(k_future_score<M>, (long)c->sy.B * ((f.n_cand + 63) / 64), 64, 7, c->sy, c->sl, a, f), c->diag[12]++;
 }
 // chmc_path_events_device: a wavefront per chain where the library keeps the compact rows (path_scan's rule), the functor
 // form under CHMC_COMPACT_ROWS=0
@@ -567,6 +590,10 @@ template <class M>
 static void predict_events_pass(chmc_ctx* c, const PredictArgs& a, const EventArgs& e, double* evraw, long long* n, double* mean,
                                 double* m2, long long* cdf) {
   predict_events_seq<M>(c, a, e, evraw, n, mean, m2, cdf);
+}
+template <class M>
+static void future_pass(chmc_ctx* c, const PredictArgs& a, const FutureArgs& f) {
+  future_seq<M>(c, a, f);
 }
 template <class M>
 static void path_events_pass(chmc_ctx* c, int NP, const EventArgs& e, const int* mask, const double* x, double* out) {

@@ -43,6 +43,11 @@
 //                           merged launch still has a compute unit per workgroup (pair_this_call); both give the same bits
 //   CHMC_PAIR_PASSES=0      a paired loop launches every pass behind the scan once per problem instead of once for both
 //                           (KernelPlan::pair_passes; the A/B partner of the merged passes, same bits)
+//   CHMC_FUTURE_WAVE=1      chmc_score_future_device runs its wave kernel (k_future_score) where the compact rows are allocated
+//                           (KernelPlan::future_wave) instead of the functor form (KFutureScore), the default because it was the
+//                           faster one at every measured shape: the A/B partner on the SAME state and
+//                           start state -- CHMC_COMPACT_ROWS=0 also changes the stepping kernels and the path scan, and with them
+//                           the inputs at rounding level; same bits
 #pragma once
 #include <climits>
 #include <cstdlib>
@@ -68,6 +73,7 @@ struct Switches {
   bool no_fwd_scan = false, step_fusions = true;
   int retract_kernel = kSwitchUnset, pair_retract = kSwitchUnset;
   bool pair_passes = true;
+  bool future_wave = false;
 };
 inline Switches read_switches() {
   auto env = [](const char* name, int unset) {
@@ -83,6 +89,7 @@ inline Switches read_switches() {
   s.retract_kernel = env("CHMC_RETRACT_KERNEL", kSwitchUnset);
   s.pair_retract = env("CHMC_PAIR_RETRACT", kSwitchUnset);
   s.pair_passes = env("CHMC_PAIR_PASSES", 1) != 0;
+  s.future_wave = env("CHMC_FUTURE_WAVE", 0) == 1;
   return s;
 }
 
@@ -102,7 +109,7 @@ struct PlanInput {
   bool wave_kernels;     // CHMC_WAVE_KERNELS: without them every pass is a generic functor over the stored rows
   Switches sw;           // as read by chmc_create
   Switches call;         // as read on entry to the current call: no_fwd_scan, step_fusions, retract_kernel, pair_retract,
-                         // pair_passes; the comparator's scan
+                         // pair_passes, future_wave; the comparator's scan
 };
 
 enum RowFamily { RowsCompact, RowsStored, RowsStoredMfma };
@@ -175,6 +182,8 @@ struct KernelPlan {
   // blocks of at most 8 row slots with the one-launch solve (NewtonIvlFsm: at most 64 blocks per chain) in every partition;
   // every other plan, and CHMC_PAIR_PASSES=0, keeps one launch per problem and pass.  Same bits either way.
   bool pair_passes;
+  bool future_wave;    // chmc_score_future_device: k_future_score (CHMC_FUTURE_WAVE=1, and predict_pass's rule: the compact rows
+                       // are allocated) instead of the functor form
   PartitionPlan part[2];
 };
 
@@ -229,6 +238,7 @@ inline KernelPlan make_plan(const PlanInput& in) {
   const bool step_fusions = pl.pb_allocated && in.call.step_fusions && !rows16;
   pl.mom_fix_in_jp = step_fusions && in.V == 2 && in.even_dims;
   pl.rev_flow_in_update = step_fusions && !in.gaussian;
+  pl.future_wave = pl.pb_allocated && in.call.future_wave;
   pl.retract_kernel = in.call.retract_kernel;
   pl.pair_retract = in.call.pair_retract;
   pl.pair_retractions = in.call.pair_retract != 0 && sw.halves != 2 && pl.fwd != FwdPar &&

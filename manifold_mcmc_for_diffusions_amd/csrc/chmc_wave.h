@@ -5857,6 +5857,35 @@ __global__ void __launch_bounds__(64) k_predict_events(Sys sy, Slots sl, Predict
   predict_wave<M, true>(sy, sl, a, grp, &e, evraw);
 }
 
+// Scoring arrived observations (chmc_score_future_device): k_predict's geometry -- a wavefront per (chain, group of 64
+// consecutive candidates), a lane per candidate -- without its reductions.  The lane runs predict_replicate at stride S and
+// keeps the candidate's FutureAcc (chmc_core.h) in registers; at each of the H emitted points it loads the wave-uniform
+// y_future[c][p] (one scalar load per S steps, off the step loop, which stays free of global loads as in k_predict), parks
+// n_p in nscr [B][n_cand][H] and, at the end, stores logw.  Lanes past n_cand repeat the last candidate, so that every lane
+// runs the same trip counts, and store nothing.  No value crosses lanes: the bits are those of KFutureScore.
+template <class M>
+__global__ void __launch_bounds__(64) k_future_score(Sys sy, Slots sl, PredictArgs a, FutureArgs f) {
+  const int lane = threadIdx.x & 63;
+  const int G = (f.n_cand + 63) / 64;
+  const int c = blockIdx.x / G, g = blockIdx.x - c * G;
+  if (c >= sy.B) return;
+  if (a.mask && !a.mask[c]) return;
+  const int R = f.n_cand - 64 * g < 64 ? f.n_cand - 64 * g : 64;
+  const bool act = lane < R;
+  const int r = 64 * g + (act ? lane : R - 1);
+  const double* q = pick(sl.q, sl.cur[c]) + (size_t)c * sy.Q;
+  const double sig = sigma_at(sy, q, c);
+  const double* y = f.y + (size_t)c * f.H;
+  double* ns = f.nscr + ((size_t)c * f.n_cand + r) * f.H;
+  FutureAcc acc;
+  acc.open();
+  predict_replicate<M>(sy, a, q, c, r, [&](int p, const double* ch) {
+    const double n = acc.add(y[p], ch[M::X], sig);
+    if (act) ns[p] = n;
+  });
+  if (act) f.logw[(size_t)c * f.n_cand + r] = acc.logw(f.H, sig);
+}
+
 // Path-wise events of the latent path (chmc_path_events_device): one wavefront per chain over x [B][NP][X].  Lane j takes
 // the window's points p0 + j, p0 + j + 64, ... so that a wavefront's loads are consecutive points; the predecessor of each
 // point is read by the same lane (a second load of a line its neighbour has just fetched, no shuffle on the path).  Every

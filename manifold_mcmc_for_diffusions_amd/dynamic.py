@@ -151,7 +151,7 @@ class DynamicTransition:
 
 def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0, total_chains=None, n_head=6,
                         trace_dir=None, trace_func=None, callback=None, per_chain_step_size=True, path_posterior=None,
-                        groups=None, n_groups=None, predictive=None, path_events=None, **kw):
+                        groups=None, n_groups=None, predictive=None, path_events=None, future_score=None, **kw):
     """Momentum refresh -> dynamic transition -> partition switch, `n_iter` times for all chains of `ctx`, with
     dual-averaging step-size adaptation on the tree's accept statistic during warm-up: the reference's sampling loop
     (scripts/utils.py:292-306, 338-365), batched.  As in Mici every chain adapts its own step size during warm-up (the
@@ -171,7 +171,11 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     out["predictive_groups"] the list of the G groups' pooled results.
     path_events: a `paths.PathEvents` of `ctx`; after warm-up every state (after the partition switch) gets `update()`,
     out["path_events"] is [n_main, B, NE] and out["path_events_summary"] `traces.summarize` of it under the object's `names`
-    (per group with `groups`)."""
+    (per group with `groups`).
+    future_score: a `paths.FutureScore` of `ctx`; after warm-up every state (after the partition switch) gets
+    `future_score.update(it, chain_offset)`; out["future_score"] is its `pooled()` result and
+    out["future_log_pred"] the [n_main, B] scores.  Scoring reads the state and draws from keyed streams of its own:
+    the chain is bitwise what it is without it."""
     import time
     from .sampling import (DualAveragingStepSize, PerChainDualAveragingStepSize, _mean_over_all_chains,
                            _group_sums_over_all_chains, check_groups)
@@ -207,6 +211,8 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
             predictive.update(seed, it, chain_offset)
         if path_events is not None and it >= n_adapt:
             event_draws.append(path_events.update())
+        if future_score is not None and it >= n_adapt:
+            future_score.update(it, chain_offset)
         heads[it] = ctx.get_head(n_head)
         if trace_dir is not None:
             from .traces import TraceWriter
@@ -258,6 +264,9 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
         out["path_events"] = ev
         out["path_events_summary"] = summarize({k: ev[:, :, i].T for i, k in enumerate(path_events.names)}, path_events.names,
                                                groups=groups)
+    if future_score is not None:
+        out["future_score"] = future_score.pooled()
+        out["future_log_pred"] = future_score.log_pred
     if predictive is not None:
         out["predictive"] = predictive.pooled()
         if groups is not None:

@@ -424,3 +424,70 @@ class PredictivePosterior:
         np.savez(path, times=self.times, horizon=self.horizon, stride=self.stride, origin=self.origin, n_rep=self.n_rep, n=n,
                  chain_mean=mean, pooled_n=pool["n"], mean=pool["mean"], sd=pool["sd"], **extra)
         return path
+
+
+def log_mean_exp(a, axis=None):
+    """log of the mean of exp(a) over `axis` (None: all entries); -inf where every entry is -inf."""
+    a = np.asarray(a, dtype=np.float64)
+    m = np.max(a, axis=axis, keepdims=True)
+    m0 = np.where(np.isfinite(m), m, 0.0)
+    with np.errstate(divide="ignore"):
+        out = m0 + np.log(np.mean(np.exp(a - m0), axis=axis, keepdims=True))
+    return float(out.reshape(())) if axis is None else np.squeeze(out, axis)
+
+
+class FutureScore:
+    """Log predictive score of observations that arrived behind the fit (chmc_score_future_device, include/chmc.h):
+    log p(y_future | y_1..T) as the log-mean over posterior draws of the per-draw score, which the device estimates from
+    `n_cand` keyed forecast candidates of each chain's current state.  y_future [H] or [B, H].  The samplers call
+    `update(it, chain_offset)` at every post-warm-up state (`future_score=`); `seed` keys the candidates, independent of
+    the sampler's seed.  Pooling is over this process' chains; a chain's values do not depend on the sharding, so ranks can
+    gather `log_pred` themselves."""
+
+    def __init__(self, ctx, y_future, n_cand=64, seed=0):
+        y = np.asarray(y_future, dtype=np.float64)
+        if y.ndim == 1:
+            y = np.broadcast_to(y, (ctx.B, y.shape[0]))
+        if y.ndim != 2 or y.shape[0] != ctx.B or y.shape[1] < 1 or not np.isfinite(y).all():
+            raise ValueError(f"y_future must be finite with shape (H,) or ({ctx.B}, H)")
+        if not 1 <= int(n_cand) <= 65536:
+            raise ValueError("need 1 <= n_cand <= 65536")
+        self.ctx, self.y_future, self.n_cand, self.seed = ctx, np.ascontiguousarray(y), int(n_cand), int(seed)
+        self.horizon = y.shape[1]
+        self._draws = []
+
+    def update(self, draw, chain_offset=0, mask=None):
+        """[B]: the score of every chain's current state, kept as one more row of `log_pred`."""
+        lp, _ = self.ctx.score_future_device(self.seed, draw, chain_offset, self.y_future, self.n_cand, mask=mask)
+        self._draws.append(lp)
+        return lp
+
+    @property
+    def log_pred(self):
+        """[n_main, B]: the per-draw, per-chain scores in the order of the updates."""
+        return np.stack(self._draws) if self._draws else np.empty((0, self.ctx.B))
+
+    def pooled(self):
+        """dict(log_pred: log-mean-exp over draws and chains; chain_log_pred [B]: over the draws of each chain; mcse: the
+        standard error of log_pred from the spread of the chains' values, sd(exp(chain - max)) / sqrt(B) on the log scale
+        by the delta method (NaN with one chain); n_draws)."""
+        lp = self.log_pred
+        if lp.shape[0] == 0:
+            nan = float("nan")
+            return dict(log_pred=nan, chain_log_pred=np.full(self.ctx.B, nan), mcse=nan, n_draws=0)
+        chain = log_mean_exp(lp, axis=0)
+        total = log_mean_exp(lp)
+        mcse = float("nan")
+        if len(chain) > 1 and np.isfinite(total):
+            w = np.exp(chain - total)  # the chains' mean densities relative to the pooled one (mean 1)
+            mcse = float(np.std(w, ddof=1) / np.sqrt(len(chain)))
+        return dict(log_pred=total, chain_log_pred=chain, mcse=mcse, n_draws=lp.shape[0])
+
+    def save(self, directory):
+        """`future_score.npz` in `directory`: y_future, n_cand, seed, the [n_main, B] scores and the pooled results."""
+        os.makedirs(directory, exist_ok=True)
+        pool = self.pooled()
+        path = os.path.join(directory, "future_score.npz")
+        np.savez(path, y_future=self.y_future, n_cand=self.n_cand, seed=self.seed, log_pred=self.log_pred,
+                 pooled_log_pred=pool["log_pred"], chain_log_pred=pool["chain_log_pred"], mcse=pool["mcse"])
+        return path

@@ -112,7 +112,7 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
                        n_head=6, callback=None, trace_dir=None, trace_func=None, total_chains=None,
                        jitter_length=False, metric_adapter=None, metric_window=0.75, metric_skip=0.25,
                        path_posterior=None, groups=None, n_groups=None, metric_per_group=False, predictive=None,
-                       path_events=None):
+                       path_events=None, future_score=None):
     """Runs n_iter transitions on all chains of `ctx`; returns traces of the first `n_head` position components
     ([n_iter, B, n_head]), accept statistics and the step size used.  Directions are sampled per chain and
     transition (forward / backward in time), failed trajectories are rejected.
@@ -149,7 +149,11 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     out["predictive_groups"] the list of the G groups' pooled results.
     path_events: a `paths.PathEvents` of `ctx`; after warm-up every state (after the partition switch) gets `update()`,
     out["path_events"] is [n_main, B, NE] and out["path_events_summary"] `traces.summarize` of it under the object's `names`
-    (per group with `groups`)."""
+    (per group with `groups`).
+    future_score: a `paths.FutureScore` of `ctx`; after warm-up every state (after the partition switch) gets
+    `future_score.update(it, chain_offset)`; out["future_score"] is its `pooled()` result and
+    out["future_log_pred"] the [n_main, B] scores.  Scoring reads the state and draws from keyed streams of its own:
+    the chain is bitwise what it is without it."""
     if metric_per_group and (groups is None or metric_adapter is None):
         raise ValueError("metric_per_group needs groups and a metric_adapter")
     group_metrics = None
@@ -228,6 +232,8 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
             predictive.update(seed, it, chain_offset)
         if path_events is not None and it >= n_adapt:
             event_draws.append(path_events.update())
+        if future_score is not None and it >= n_adapt:
+            future_score.update(it, chain_offset)
         heads[it] = ctx.get_head(n_head)
         if trace_dir is not None:
             vals = {k: np.asarray(v) for k, v in trace_func(heads[it], ctx.hamiltonian()[:, 0]).items()}
@@ -278,6 +284,9 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
         out["path_events"] = ev
         out["path_events_summary"] = summarize({k: ev[:, :, i].T for i, k in enumerate(path_events.names)}, path_events.names,
                                                groups=groups)
+    if future_score is not None:
+        out["future_score"] = future_score.pooled()
+        out["future_log_pred"] = future_score.log_pred
     if predictive is not None:
         out["predictive"] = predictive.pooled()
         if groups is not None:
