@@ -613,7 +613,7 @@ int chmc_get_counters(const chmc_ctx* ctx, long long* out8);
  *   out80[76]      launches of the predictive wave kernel (k_predict, k_predict_events: chmc_predict_device /
  *                  chmc_predict_events_device with the compact rows on), and of k_future_score (chmc_score_future_device under
  *                  CHMC_FUTURE_WAVE=1: the same recursion and geometry; no slot is free for a counter of its own)
- *   out80[77]      launches of the predictive functor form (KPredict, KPredictEvents: CHMC_COMPACT_ROWS=0), and of
+ *   out80[77]      launches of the predictive functor form (KPredict<M, EVENTS>: CHMC_COMPACT_ROWS=0), and of
  *                  KFutureScore (chmc_score_future_device's default)
  *   out80[78]      launches of the path-events wave kernel (k_path_events: chmc_path_events_device, compact rows on)
  *   out80[79]      launches of the path-events functor form (KPathEvents: CHMC_COMPACT_ROWS=0)

@@ -5,6 +5,7 @@ own Welford statistics of the first `dim_param` position components, and `finali
 (of all ranks, when `torch.distributed` is initialised) with the parallel covariance update of Schubert and Gertz, in
 chain order, exactly as the reference combines the adapter states of its independent chains."""
 import numpy as np
+from .distributed import all_gather_objects
 from .errors import AdaptationError
 from .system import DensePositiveDefiniteMatrix, IdentityMatrix, PositiveDefiniteBlockDiagonalMatrix
 
@@ -58,16 +59,8 @@ class OnlineBlockDiagonalMetricAdapter:
     def finalize(self, adapt_state, system=None):  # :1892-1931
         """Returns the metric; assigns it to `system.metric` when a system is given."""
         iters, means, sums = adapt_state["iter"], adapt_state["mean"], adapt_state["sum_diff_outer"]
-        try:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                parts = [None] * dist.get_world_size()
-                dist.all_gather_object(parts, (iters, means, sums))  # rank order = global chain order
-                iters = np.concatenate([p[0] for p in parts])
-                means = np.concatenate([p[1] for p in parts])
-                sums = np.concatenate([p[2] for p in parts])
-        except ImportError:
-            pass
+        # rank order = global chain order
+        iters, means, sums = (np.concatenate(a) for a in zip(*all_gather_objects((iters, means, sums))))
         n_iter, _, covar_est = self.combine(iters, means, sums)
         if n_iter < 2:
             raise AdaptationError("At least two chain samples required to compute a variance estimates.")
@@ -87,17 +80,8 @@ class OnlineBlockDiagonalMetricAdapter:
         rank the same matrix."""
         groups = np.asarray(groups)
         iters, means, sums = adapt_state["iter"], adapt_state["mean"], adapt_state["sum_diff_outer"]
-        try:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                parts = [None] * dist.get_world_size()
-                dist.all_gather_object(parts, (groups, iters, means, sums))  # rank order = global chain order
-                groups = np.concatenate([p[0] for p in parts])
-                iters = np.concatenate([p[1] for p in parts])
-                means = np.concatenate([p[2] for p in parts])
-                sums = np.concatenate([p[3] for p in parts])
-        except ImportError:
-            pass
+        # rank order = global chain order
+        groups, iters, means, sums = (np.concatenate(a) for a in zip(*all_gather_objects((groups, iters, means, sums))))
         out = np.empty((int(n_groups), self.dim_param, self.dim_param))
         for g in range(int(n_groups)):
             sel = np.flatnonzero(groups == g)

@@ -10,6 +10,9 @@ from ._lib import ChmcConfig, as_c, ptr, iptr, check
 
 MODEL_IDS = {"fhn": 0, "sir": 1, "fhn_nb": 2}
 STATUS_NAMES = {0: "ok", 1: "not_converged", 2: "diverged", 3: "non_reversible", -1: "inactive"}
+# the reference scripts' Newton solver and tolerances (scripts/utils.py:131-166); users take a copy: dict(DEFAULT_SOLVER)
+DEFAULT_SOLVER = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
+                      reverse_check_tol=2e-8)
 
 
 class ChmcContext:
@@ -60,6 +63,7 @@ class ChmcContext:
         self.variable_sigma = isinstance(sigma, str)
         self.sigma = sigma
         self.device = int(device)
+        self.on_gpu = L.chmc_backend() == b"hip:gfx950"  # False: the library's "device" is host memory (emulation build)
         self._obs_interval = float(obs_interval)
         self._model, self._num_obs_per_subseq = model, num_obs_per_subseq  # (sibling)
         self._use_gaussian_splitting = bool(use_gaussian_splitting)

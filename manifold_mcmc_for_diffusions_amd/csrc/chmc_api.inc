@@ -1169,8 +1169,16 @@ static int path_check(chmc_ctx* ctx, const char* fn, int stride, bool current) {
   if (current && !ctx->have_state) return fail(std::string(fn) + ": no state has been set");
   return 0;
 }
-static void path_run(chmc_ctx* ctx, const double* q_dev, int stride, double* out_dev, int* sweeps) {
+// a call's chain mask on the device: d_path_ints ([2][B], allocated on first use) holds the sweeps, then the mask
+static int* path_mask(chmc_ctx* ctx, const int* mask) {
   if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)ctx->sy.B);
+  if (!mask) return nullptr;
+  int* d_mask = ctx->d_path_ints + ctx->sy.B;
+  h2d(d_mask, mask, sizeof(int) * ctx->sy.B);
+  return d_mask;
+}
+static void path_run(chmc_ctx* ctx, const double* q_dev, int stride, double* out_dev, int* sweeps) {
+  path_mask(ctx, nullptr);
   dispatch(ctx, [&](auto inst) { path_scan<typename decltype(inst)::M>(ctx, q_dev, stride, out_dev, sweeps ? ctx->d_path_ints : nullptr); });
   if (sweeps) d2h(sweeps, ctx->d_path_ints, sizeof(int) * ctx->sy.B);
 }
@@ -1201,8 +1209,7 @@ extern "C" int chmc_path_stats_update_device(chmc_ctx* ctx, int stride, const in
   const Sys& sy = ctx->sy;
   const int NP = sy.T * sy.S / stride + 1;
   path_run(ctx, nullptr, stride, (double*)x_seq_dev, nullptr);
-  int* d_mask = nullptr;
-  if (mask) h2d(d_mask = ctx->d_path_ints + sy.B, mask, sizeof(int) * sy.B);
+  const int* d_mask = path_mask(ctx, mask);
   dispatch(ctx, [&](auto inst) {
     using M = typename decltype(inst)::M;
     const KPathWelford<M> f{NP, 0, d_mask, (const double*)x_seq_dev, (long long*)n_dev, (double*)mean_dev, (double*)m2_dev};
@@ -1224,16 +1231,33 @@ static int predict_check(const chmc_ctx* ctx, const char* fn, int horizon, int s
     return fail(std::string(fn) + ": horizon too long for the 32-bit counter of the normal stream");
   return 0;
 }
+// the times of a call's NPF points: t0 + p stride dl, p = 1 .. NPF, t0 the last observation's time (origin 0) or 0
+static void predict_times(const chmc_ctx* ctx, int NPF, int stride, int origin, double* times) {
+  const double t0 = origin == 0 ? ctx->sy.T * ctx->cfg.obs_interval : 0.0;
+  for (int p = 1; p <= NPF; ++p) times[p - 1] = t0 + p * (stride * ctx->sy.dl);
+}
+// a forecast's arguments: the keyed streams of (seed, draw), the steps and points, and for origin 0 the start state x_T --
+// the last point of the path of the current states at the observation times, scanned HERE into d_pred_x
+static PredictArgs forecast_args(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset, int horizon,
+                                 int stride, int origin, int n_rep) {
+  const Sys& sy = ctx->sy;
+  PredictArgs a{};
+  a.seed = seed, a.key0 = CHMC_PREDICT_DRAW | (draw << 16);
+  a.chain_offset = chain_offset, a.HS = horizon * sy.S, a.stride = stride, a.NPF = a.HS / stride;
+  a.n_rep = n_rep;
+  if (origin == 0) {
+    if (!ctx->d_pred_x) ctx->d_pred_x = alloc<double>(ctx, (size_t)sy.B * (sy.T + 1) * sy.X);
+    path_run(ctx, nullptr, sy.S, ctx->d_pred_x, nullptr);
+    a.xstart = ctx->d_pred_x + (size_t)sy.T * sy.X, a.xld = (long long)(sy.T + 1) * sy.X;
+  }
+  return a;
+}
 extern "C" int chmc_predict_points(const chmc_ctx* ctx, int horizon, int stride, int origin, int* n_points, double* times) {
   if (!ctx) return fail("chmc_predict_points: null context");
   if (!n_points) return fail("chmc_predict_points: null output");
   if (predict_check(ctx, "chmc_predict_points", horizon, stride, origin)) return -1;
-  const Sys& sy = ctx->sy;
-  const int NPF = horizon * sy.S / stride;
-  *n_points = NPF;
-  const double t0 = origin == 0 ? sy.T * ctx->cfg.obs_interval : 0.0;
-  if (times)
-    for (int p = 1; p <= NPF; ++p) times[p - 1] = t0 + p * (stride * sy.dl);
+  *n_points = horizon * ctx->sy.S / stride;
+  if (times) predict_times(ctx, *n_points, stride, origin, times);
   return 0;
 }
 // the events of a chmc_predict_events_device call (null: chmc_predict_device)
@@ -1280,50 +1304,33 @@ static int predict_call(chmc_ctx* ctx, const char* name, unsigned long long seed
     if (event_thresholds(fn, ev->n_thresholds, ev->thresholds, e)) return -1;
     e.channel = ev->channel, e.p0 = ev->p0, e.p1 = ev->p1, e.h = stride * sy.dl;
   }
-  if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)sy.B);
-  PredictArgs a{};
-  a.seed = seed, a.key0 = CHMC_PREDICT_DRAW | (draw << 16);
-  a.chain_offset = chain_offset, a.HS = horizon * sy.S, a.stride = stride, a.NPF = a.HS / stride;
-  a.n_rep = n_rep, a.n_keep = paths_dev ? n_keep : 0, a.n_levels = n_levels;
+  PredictArgs a = forecast_args(ctx, seed, draw, chain_offset, horizon, stride, origin, n_rep);
+  a.n_keep = paths_dev ? n_keep : 0, a.n_levels = n_levels;
   a.paths = a.n_keep ? (double*)paths_dev : nullptr;
-  if (origin == 0) {  // x_T: the last point of the path of the current states at the observation times
-    if (!ctx->d_pred_x) ctx->d_pred_x = alloc<double>(ctx, (size_t)sy.B * (sy.T + 1) * sy.X);
-    path_run(ctx, nullptr, sy.S, ctx->d_pred_x, nullptr);
-    a.xstart = ctx->d_pred_x + (size_t)sy.T * sy.X, a.xld = (long long)(sy.T + 1) * sy.X;
-  }
-  if (mask) {
-    int* d_mask = ctx->d_path_ints + sy.B;
-    h2d(d_mask, mask, sizeof(int) * sy.B);
-    a.mask = d_mask;
-  }
+  a.mask = path_mask(ctx, mask);
   if (n_levels > 0) {
     if (ctx->d_pred_lev_cap < (size_t)n_levels)
       ctx->d_pred_lev = alloc<double>(ctx, (size_t)n_levels), ctx->d_pred_lev_cap = (size_t)n_levels;
     h2d(ctx->d_pred_lev, levels, sizeof(double) * n_levels);
     a.levels = ctx->d_pred_lev;
   }
-  if (!ev) {
-    dispatch(ctx, [&](auto inst) {
-      predict_pass<typename decltype(inst)::M>(ctx, a, (long long*)n_dev, (double*)mean_dev, (double*)m2_dev, (long long*)cdf_dev);
-    });
-    CHMC_LEAVE(name)
+  double* evraw = nullptr;
+  if (ev) {  // the point times, as chmc_predict_points gives them, and the replicates' raw events (the caller's buffer or scratch)
+    const int NE = 5 + 3 * e.L;
+    const size_t n_ev = ev->events_dev ? 0 : (size_t)sy.B * n_rep * NE;
+    if (ctx->d_pred_ev_cap < a.NPF + n_ev)
+      ctx->d_pred_ev = alloc<double>(ctx, a.NPF + n_ev), ctx->d_pred_ev_cap = a.NPF + n_ev;
+    std::vector<double> times(a.NPF);
+    predict_times(ctx, a.NPF, stride, origin, times.data());
+    h2d(ctx->d_pred_ev, times.data(), sizeof(double) * a.NPF);
+    e.times = ctx->d_pred_ev;
+    evraw = ev->events_dev ? (double*)ev->events_dev : ctx->d_pred_ev + a.NPF;
   }
-  // the point times, as chmc_predict_points gives them, and the replicates' raw events (the caller's buffer or scratch)
-  const int NE = 5 + 3 * e.L;
-  const size_t n_ev = ev->events_dev ? 0 : (size_t)sy.B * n_rep * NE;
-  if (ctx->d_pred_ev_cap < a.NPF + n_ev)
-    ctx->d_pred_ev = alloc<double>(ctx, a.NPF + n_ev), ctx->d_pred_ev_cap = a.NPF + n_ev;
-  std::vector<double> times(a.NPF);
-  const double t0 = origin == 0 ? sy.T * ctx->cfg.obs_interval : 0.0;
-  for (int p = 1; p <= a.NPF; ++p) times[p - 1] = t0 + p * (stride * sy.dl);
-  h2d(ctx->d_pred_ev, times.data(), sizeof(double) * a.NPF);
-  e.times = ctx->d_pred_ev;
-  double* evraw = ev->events_dev ? (double*)ev->events_dev : ctx->d_pred_ev + a.NPF;
   dispatch(ctx, [&](auto inst) {
-    predict_events_pass<typename decltype(inst)::M>(ctx, a, e, evraw, (long long*)n_dev, (double*)mean_dev, (double*)m2_dev,
-                                                    (long long*)cdf_dev);
+    predict_pass<typename decltype(inst)::M>(ctx, a, ev ? &e : nullptr, evraw, (long long*)n_dev, (double*)mean_dev,
+                                             (double*)m2_dev, (long long*)cdf_dev);
   });
-  event_fold(ctx, a, e, evraw, (long long*)ev->en_dev, (double*)ev->emean_dev, (double*)ev->em2_dev);
+  if (ev) event_fold(ctx, a, e, evraw, (long long*)ev->en_dev, (double*)ev->emean_dev, (double*)ev->em2_dev);
   CHMC_LEAVE(name)
 }
 extern "C" int chmc_predict_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset,
@@ -1367,7 +1374,6 @@ extern "C" int chmc_score_future_device(chmc_ctx* ctx, unsigned long long seed, 
   const size_t nBH = (size_t)sy.B * horizon;
   for (size_t i = 0; i < nBH; ++i)
     if (!(y_future[i] - y_future[i] == 0.0)) return fail(fn + ": y_future must be finite");
-  if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)sy.B);
   // scratch: y | log_pred | picked | n of every candidate | logw where the caller keeps none
   const size_t nB = (size_t)sy.B, nC = nB * n_cand, nI = (nB + 1) / 2;
   const size_t need = nBH + nB + nI + nC * horizon + (logw_dev ? 0 : nC);
@@ -1376,18 +1382,8 @@ extern "C" int chmc_score_future_device(chmc_ctx* ctx, unsigned long long seed, 
   double* d_lp = d_y + nBH;
   int* d_pk = reinterpret_cast<int*>(d_lp + nB);
   h2d(d_y, y_future, sizeof(double) * nBH);
-  PredictArgs a{};
-  a.seed = seed, a.key0 = CHMC_PREDICT_DRAW | (draw << 16);
-  a.chain_offset = chain_offset, a.HS = horizon * sy.S, a.stride = sy.S, a.NPF = horizon;
-  a.n_rep = n_cand;
-  if (!ctx->d_pred_x) ctx->d_pred_x = alloc<double>(ctx, (size_t)sy.B * (sy.T + 1) * sy.X);
-  path_run(ctx, nullptr, sy.S, ctx->d_pred_x, nullptr);  // x_T from the position, as the forecast takes it
-  a.xstart = ctx->d_pred_x + (size_t)sy.T * sy.X, a.xld = (long long)(sy.T + 1) * sy.X;
-  if (mask) {
-    int* d_mask = ctx->d_path_ints + sy.B;
-    h2d(d_mask, mask, sizeof(int) * sy.B);
-    a.mask = d_mask;
-  }
+  PredictArgs a = forecast_args(ctx, seed, draw, chain_offset, horizon, sy.S, 0, n_cand);  // (x_T as the forecast takes it)
+  a.mask = path_mask(ctx, mask);
   FutureArgs f{};
   f.H = horizon, f.n_cand = n_cand, f.y = d_y;
   f.nscr = d_lp + nB + nI;
@@ -1419,9 +1415,7 @@ extern "C" int chmc_path_events_device(chmc_ctx* ctx, const void* x_seq_dev, int
   EventArgs e{};
   if (event_thresholds(fn, n_thresholds, thresholds, e)) return -1;
   e.channel = channel, e.p0 = p0, e.p1 = p1, e.h = stride * sy.dl;
-  if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)sy.B);
-  int* d_mask = nullptr;
-  if (mask) h2d(d_mask = ctx->d_path_ints + sy.B, mask, sizeof(int) * sy.B);
+  const int* d_mask = path_mask(ctx, mask);
   dispatch(ctx, [&](auto inst) {
     path_events_pass<typename decltype(inst)::M>(ctx, n_points, e, d_mask, (const double*)x_seq_dev, (double*)events_dev);
   });
@@ -1815,18 +1809,13 @@ extern "C" int chmc_resample_q_device(chmc_ctx* ctx, const void* q_src_dev, int 
     }
     CHMC_LEAVE("chmc_resample_q_device")
   }
-  if (!ctx->d_path_ints) ctx->d_path_ints = alloc<int>(ctx, 2 * (size_t)sy.B);
   ResampleArgs a{};
   a.seed = seed, a.key = CHMC_RESAMPLE_DRAW | draw, a.chain_offset = chain_offset;
   a.B = sy.B, a.U = sy.U, a.V0 = sy.V0, a.T = sy.T, a.NT = NT;
   a.Sc = S_small, a.m = S_big / S_small, a.refine = sy.S > S_src;
   a.Qs = Qs, a.Qd = sy.Q;
   a.src = (const double*)q_src_dev, a.dst = (double*)q_dst_dev;
-  if (mask) {
-    int* d_mask = ctx->d_path_ints + sy.B;
-    h2d(d_mask, mask, sizeof(int) * sy.B);
-    a.mask = d_mask;
-  }
+  a.mask = path_mask(ctx, mask);
   dispatch(ctx, [&](auto inst) { resample_pass<typename decltype(inst)::M>(ctx, a); });
   CHMC_LEAVE("chmc_resample_q_device")
 }

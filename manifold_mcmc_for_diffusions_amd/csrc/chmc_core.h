@@ -21,6 +21,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 #include "chmc_model.h"
 
 // functors that the per-chain kernels (chmc_retract.h) call from inside their phase loops: a real call there makes the kernel
@@ -2235,28 +2236,7 @@ CHMC_HD CHMC_FI inline void predict_replicate(const Sys& sy, const PredictArgs& 
     }
   }
 }
-// The functor form, pass 1: one work item per (chain, replicate); the replicate's channels go to the library's scratch
-// raw [B][n_rep][NPF][XC], and to the kept paths for r < n_keep.
-template <class M>
-struct KPredict {
-  Sys sy;
-  Slots sl;
-  PredictArgs a;
-  double* raw;
-  CHMC_HD void operator()(int tid) const {
-    constexpr int XC = M::X + 2;
-    const int c = tid / a.n_rep, r = tid - c * a.n_rep;
-    if (a.mask && !a.mask[c]) return;
-    const double* q = pick(sl.q, sl.cur[c]) + (size_t)c * sy.Q;
-    double* o = raw + ((size_t)c * a.n_rep + r) * a.NPF * XC;
-    double* k = a.paths && r < a.n_keep ? a.paths + ((size_t)c * a.n_keep + r) * a.NPF * XC : nullptr;
-    predict_replicate<M>(sy, a, q, c, r, [&](int p, const double* ch) {
-      for (int i = 0; i < XC; ++i) o[(size_t)p * XC + i] = ch[i];
-      if (k)
-        for (int i = 0; i < XC; ++i) k[(size_t)p * XC + i] = ch[i];
-    });
-  }
-};
+// (The functor form's pass 1, KPredict<M, EVENTS>, stands behind EventArgs below.)
 // Chan's merge of a group (R values, mean mg, centred sum of squares sg) into running moments of nn values
 CHMC_HD CHMC_FI inline void predict_merge(double nn, double R, double mg, double sg, double& mu, double& s2) {
   const double n1 = nn + R, d = mg - mu;
@@ -2540,15 +2520,18 @@ struct KPathEvents {
                 a.first, a.above);
   }
 };
-// The predictive's events, functor form (pass 1 of chmc_predict_events_device): KPredict with the replicate's event vector
-// accumulated in the emit callback; evraw [B][n_rep][NE].
-template <class M>
-struct KPredictEvents {
+// The predictive's functor form, pass 1 (chmc_predict_device, chmc_predict_events_device): one work item per (chain,
+// replicate); the replicate's channels go to the library's scratch raw [B][n_rep][NPF][XC], and to the kept paths for
+// r < n_keep.  EVENTS (the twin of predict_wave<M, true>, chmc_wave.h): the replicate's event vector is accumulated in the
+// emit callback and stored into evraw [B][n_rep][NE] at the end; without it the functor carries no EventArgs.
+struct NoEventArgs {};
+template <class M, bool EVENTS>
+struct KPredict {
   Sys sy;
   Slots sl;
   PredictArgs a;
   double* raw;
-  EventArgs e;
+  std::conditional_t<EVENTS, EventArgs, NoEventArgs> e;
   double* evraw;
   CHMC_HD void operator()(int tid) const {
     constexpr int XC = M::X + 2;
@@ -2563,10 +2546,11 @@ struct KPredictEvents {
       for (int i = 0; i < XC; ++i) o[(size_t)p * XC + i] = ch[i];
       if (k)
         for (int i = 0; i < XC; ++i) k[(size_t)p * XC + i] = ch[i];
-      event_point(e, acc, p, ch[e.channel], vfirst, prev);
+      if constexpr (EVENTS) event_point(e, acc, p, ch[e.channel], vfirst, prev);
     });
-    event_write(e, evraw + ((size_t)c * a.n_rep + r) * (5 + 3 * e.L), acc.bad != 0, acc.vmax, acc.imax, acc.vmin, acc.imin,
-                acc.sum, vfirst, prev, acc.up, acc.first, acc.above);
+    if constexpr (EVENTS)
+      event_write(e, evraw + ((size_t)c * a.n_rep + r) * (5 + 3 * e.L), acc.bad != 0, acc.vmax, acc.imax, acc.vmin, acc.imin,
+                  acc.sum, vfirst, prev, acc.up, acc.first, acc.above);
   }
 };
 // The fold of the predictive's events, pass 2 of both forms: one work item per (chain, entry) merges the call's groups of 64

@@ -65,22 +65,20 @@ static void predict_fold(chmc_ctx* c, const PredictArgs& a, int grouped, const d
   launch(f, (long)c->sy.B * a.NPF, 8);
 }
 // the predictive by the generic functors: a work item per (chain, replicate) writes the raw channels, the fold sums them in
-// replicate order
+// replicate order.  e (null: chmc_predict_device): the replicates' event vectors go to evraw as well
 template <class M>
-static void predict_seq(chmc_ctx* c, const PredictArgs& a, long long* n, double* mean, double* m2, long long* cdf) {
+static void predict_seq(chmc_ctx* c, const PredictArgs& a, const EventArgs* e, double* evraw, long long* n, double* mean,
+                        double* m2, long long* cdf) {
   double* raw = predict_scratch(c, (size_t)c->sy.B * a.n_rep * a.NPF * (M::X + 2));
-  launch(KPredict<M>{c->sy, c->sl, a, raw}, (long)c->sy.B * a.n_rep, 7), c->diag[13]++;
+  const long tasks = (long)c->sy.B * a.n_rep;
+  if (e)
+    launch(KPredict<M, true>{c->sy, c->sl, a, raw, *e, evraw}, tasks, 7);
+  else
+    launch(KPredict<M, false>{c->sy, c->sl, a, raw, {}, nullptr}, tasks, 7);
+  c->diag[13]++;
   predict_fold<M>(c, a, 0, raw, n, mean, m2, cdf);
 }
-
-// the predictive with events by the generic functors (KPredictEvents), and the events' fold of both forms (KEventFold)
-template <class M>
-static void predict_events_seq(chmc_ctx* c, const PredictArgs& a, const EventArgs& e, double* evraw, long long* n, double* mean,
-                               double* m2, long long* cdf) {
-  double* raw = predict_scratch(c, (size_t)c->sy.B * a.n_rep * a.NPF * (M::X + 2));
-  launch(KPredictEvents<M>{c->sy, c->sl, a, raw, e, evraw}, (long)c->sy.B * a.n_rep, 7), c->diag[13]++;
-  predict_fold<M>(c, a, 0, raw, n, mean, m2, cdf);
-}
+// the events' fold of both forms (KEventFold)
 static void event_fold(chmc_ctx* c, const PredictArgs& a, const EventArgs& e, const double* evraw, long long* en, double* emean,
                        double* em2) {
   const int NE = 5 + 3 * e.L;
@@ -116,23 +114,18 @@ static void resample_seq(chmc_ctx* c, const ResampleArgs& a) {
 constexpr bool kWaveKernels = true;  // PlanInput::wave_kernels of every context of this build
 // chmc_predict_device: a wavefront per (chain, group of 64 replicates) where the library keeps the compact rows (the
 // default; path_scan's rule) leaves the groups' statistics to the fold; CHMC_COMPACT_ROWS=0 runs the functor form, the A/B
-// partner
+// partner.  e (chmc_predict_events_device; null: none): the EVENTS instantiation of the wave kernel, by the same rule
 template <class M>
-static void predict_pass(chmc_ctx* c, const PredictArgs& a, long long* n, double* mean, double* m2, long long* cdf) {
-  if (!c->plan.pb_allocated) return predict_seq<M>(c, a, n, mean, m2, cdf);
+static void predict_pass(chmc_ctx* c, const PredictArgs& a, const EventArgs* e, double* evraw, long long* n, double* mean,
+                         double* m2, long long* cdf) {
+  if (!c->plan.pb_allocated) return predict_seq<M>(c, a, e, evraw, n, mean, m2, cdf);
   const int G = (a.n_rep + 63) / 64;
   double* grp = predict_scratch(c, (size_t)c->sy.B * G * a.NPF * (2 * (M::X + 2) + a.n_levels));
-  launch_blocks(k_predict<M>, (long)c->sy.B * G, 64, 7, c->sy, c->sl, a, grp), c->diag[12]++;
-  predict_fold<M>(c, a, 1, grp, n, mean, m2, cdf);
-}
-// chmc_predict_events_device: predict_pass's rule, with the EVENTS instantiation of the wave kernel
-template <class M>
-static void predict_events_pass(chmc_ctx* c, const PredictArgs& a, const EventArgs& e, double* evraw, long long* n, double* mean,
-                                double* m2, long long* cdf) {
-  if (!c->plan.pb_allocated) return predict_events_seq<M>(c, a, e, evraw, n, mean, m2, cdf);
-  const int G = (a.n_rep + 63) / 64;
-  double* grp = predict_scratch(c, (size_t)c->sy.B * G * a.NPF * (2 * (M::X + 2) + a.n_levels));
-  launch_blocks(k_predict_events<M>, (long)c->sy.B * G, 64, 7, c->sy, c->sl, a, grp, e, evraw), c->diag[12]++;
+  if (e)
+    launch_blocks(k_predict_events<M>, (long)c->sy.B * G, 64, 7, c->sy, c->sl, a, grp, *e, evraw);
+  else
+    launch_blocks(k_predict<M>, (long)c->sy.B * G, 64, 7, c->sy, c->sl, a, grp);
+  c->diag[12]++;
   predict_fold<M>(c, a, 1, grp, n, mean, m2, cdf);
 }
 // chmc_score_future_device: the functor form unless CHMC_FUTURE_WAVE=1 asks for the wave kernel -- a wavefront per (chain,
@@ -583,13 +576,9 @@ static void path_scan(chmc_ctx* c, const double* q, int stride, double* out, int
   path_seq<M>(c, q, stride, out, sweeps);
 }
 template <class M>
-static void predict_pass(chmc_ctx* c, const PredictArgs& a, long long* n, double* mean, double* m2, long long* cdf) {
-  predict_seq<M>(c, a, n, mean, m2, cdf);
-}
-template <class M>
-static void predict_events_pass(chmc_ctx* c, const PredictArgs& a, const EventArgs& e, double* evraw, long long* n, double* mean,
-                                double* m2, long long* cdf) {
-  predict_events_seq<M>(c, a, e, evraw, n, mean, m2, cdf);
+static void predict_pass(chmc_ctx* c, const PredictArgs& a, const EventArgs* e, double* evraw, long long* n, double* mean,
+                         double* m2, long long* cdf) {
+  predict_seq<M>(c, a, e, evraw, n, mean, m2, cdf);
 }
 template <class M>
 static void future_pass(chmc_ctx* c, const PredictArgs& a, const FutureArgs& f) {

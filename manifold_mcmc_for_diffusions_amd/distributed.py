@@ -38,6 +38,53 @@ def shard_chains(total_chains, rank, world):
     return offset, count
 
 
+def process_group():
+    """None for a single process (no torch.distributed, no process group, or one rank); otherwise (world size, the device
+    the group's collectives work on: "cuda" under "nccl", which is RCCL on ROCm, else "cpu")."""
+    try:
+        import torch.distributed as dist
+    except ImportError:
+        return None
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return None
+    return dist.get_world_size(), "cuda" if dist.get_backend() == "nccl" else "cpu"
+
+
+def all_gather_vectors(vec):
+    """All-gather of one float64 vector (the same length on every rank): the ranks' numpy vectors in rank order."""
+    import torch
+    import torch.distributed as dist
+    world, dev = process_group()
+    t = torch.from_numpy(np.ascontiguousarray(vec, dtype=np.float64)).to(dev)
+    parts = [torch.empty_like(t) for _ in range(world)]
+    dist.all_gather(parts, t)
+    return [p.cpu().numpy() for p in parts]
+
+
+def all_gather_objects(obj):
+    """The ranks' picklable objects in rank order; [obj] for a single process."""
+    pg = process_group()
+    if pg is None:
+        return [obj]
+    import torch.distributed as dist
+    parts = [None] * pg[0]
+    dist.all_gather_object(parts, obj)
+    return parts
+
+
+def all_reduce_array(a, dtype, op="SUM"):
+    """`a` as a numpy array of `dtype`, reduced over the ranks with `op` (as it is for a single process)."""
+    a = np.asarray(a, dtype=dtype)
+    pg = process_group()
+    if pg is None:
+        return a
+    import torch
+    import torch.distributed as dist
+    t = torch.from_numpy(a.copy()).to(pg[1])
+    dist.all_reduce(t, op=getattr(dist.ReduceOp, op))
+    return t.cpu().numpy()
+
+
 def barrier():
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
@@ -51,7 +98,8 @@ def gather_samples(local, dst=0, equal_shards=False):
     sizes: the segment then costs exactly one collective."""
     import torch
     import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+    pg = process_group()
+    if pg is None:
         return local.detach().cpu().numpy() if isinstance(local, torch.Tensor) else np.asarray(local)
     backend = dist.get_backend()
     t = local if isinstance(local, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(local))
@@ -59,7 +107,7 @@ def gather_samples(local, dst=0, equal_shards=False):
         t = t.cuda()
     if backend == "gloo" and t.is_cuda:
         t = t.cpu()
-    world, rank = dist.get_world_size(), dist.get_rank()
+    world, rank = pg[0], dist.get_rank()
     if equal_shards:
         counts = [t.shape[0]] * world
     else:
@@ -83,8 +131,8 @@ def gather_samples(local, dst=0, equal_shards=False):
 
 def world_size():
     """World size read back from the initialised process group (1 without one)."""
-    import torch.distributed as dist
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    pg = process_group()
+    return 1 if pg is None else pg[0]
 
 
 def backend_name():
@@ -94,23 +142,8 @@ def backend_name():
 
 
 def max_over_ranks(value):
-    import torch
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return float(value)
-    dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
-    t = torch.tensor([float(value)], dtype=torch.float64, device=dev)
-    dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return float(t.item())
+    return float(all_reduce_array([float(value)], np.float64, "MAX")[0])
 
 
 def sum_over_ranks(values):
-    import torch
-    import torch.distributed as dist
-    v = np.asarray(values, dtype=np.float64)
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return v
-    dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
-    t = torch.tensor(v, dtype=torch.float64, device=dev)
-    dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    return t.cpu().numpy()
+    return all_reduce_array(values, np.float64)

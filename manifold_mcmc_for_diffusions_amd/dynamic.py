@@ -25,6 +25,7 @@ alone -- blocks per chain, block length, rows -- never from the number of chains
 few_long_blocks; GPU test test_results_do_not_depend_on_the_shard_size).
 """
 import numpy as np
+from .context import DEFAULT_SOLVER
 
 
 class TreeUniforms:
@@ -63,8 +64,7 @@ class DynamicTransition:
         self.ctx, self.seed = ctx, seed
         self.step_size = step_size  # a number, or one step size per chain [B] (per-chain warm-up adaptation)
         self.max_tree_depth, self.max_delta_h = int(max_tree_depth), float(max_delta_h)
-        self.solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
-                           reverse_check_tol=2e-8) if solver is None else solver
+        self.solver = dict(DEFAULT_SOLVER) if solver is None else solver
         self.off = chain_offset
         self.total = ctx.B + chain_offset if total_chains is None else total_chains
         if device is None:
@@ -160,23 +160,14 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     averaged over all chains (round 2's scheme): the batched trees of a doubling then all have the same number of leaves to
     offer, which keeps the lock-step batch full during warm-up (the FitzHugh-Nagumo example: 30 k against 24 k leapfrog
     steps/s end to end), but a chain that starts where that step size is far too long never moves.
-    path_posterior: a `paths.PathPosterior` of `ctx`; the latent path of every post-warm-up state (after the partition
-    switch) is folded into its running moments, and out["path_posterior"] is its `pooled()` result.
     groups [B], n_groups: chains that sample different posteriors in one context (per-chain observations): groups[c] is the
     global id of chain c's data set.  Warm-up is per chain as before; the main phase of a chain runs with the mean of the
     adapted step sizes of ITS group over all ranks instead of the all-chain mean (out["group_step_sizes"] [G]; one group
     gives the numbers of the call without `groups`).  Needs per_chain_step_size.
-    predictive: a `paths.PredictivePosterior` of `ctx`; after warm-up every state (after the partition switch) gets
-    `predictive.update(seed, it, chain_offset)`, out["predictive"] is its `pooled()` result and, with `groups`,
-    out["predictive_groups"] the list of the G groups' pooled results.
-    path_events: a `paths.PathEvents` of `ctx`; after warm-up every state (after the partition switch) gets `update()`,
-    out["path_events"] is [n_main, B, NE] and out["path_events_summary"] `traces.summarize` of it under the object's `names`
-    (per group with `groups`).
-    future_score: a `paths.FutureScore` of `ctx`; after warm-up every state (after the partition switch) gets
-    `future_score.update(it, chain_offset)`; out["future_score"] is its `pooled()` result and
-    out["future_log_pred"] the [n_main, B] scores.  Scoring reads the state and draws from keyed streams of its own:
-    the chain is bitwise what it is without it."""
-    import time
+    path_posterior, predictive, path_events, future_score: summaries of the post-warm-up states and their entries of
+    `out` (paths.SamplerSummaries); trace_dir, trace_func: as in sample_static_chmc (traces.SamplerTrace)."""
+    from .paths import SamplerSummaries
+    from .traces import SamplerTrace
     from .sampling import (DualAveragingStepSize, PerChainDualAveragingStepSize, _mean_over_all_chains,
                            _group_sums_over_all_chains, check_groups)
     group_eps = None
@@ -190,36 +181,22 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
     if n_adapt > 0:
         adapter = PerChainDualAveragingStepSize(step_size, B) if per_chain_step_size else DualAveragingStepSize(step_size)
     heads = np.empty((n_iter, B, n_head))
-    event_draws = []
     acc_hist, eps_hist, nstep_hist = np.empty(n_iter), np.empty(n_iter), np.empty(n_iter)
     err_hist = np.empty(n_iter)
     # per chain, main phase (after warm-up): transitions that moved the chain / did not, trees ended by an integrator error,
     # by a divergence, trees with no leaf at all (first step failed), non-finite root Hamiltonian; leaves and accept-stat sums
     outcome = np.zeros((B, 6), dtype=np.int64)
     per_chain = dict(n_step=np.zeros(B), accept=np.zeros(B), err=np.zeros(B))
-    writer, t0, c0 = None, time.perf_counter(), ctx.counters()
-    if trace_func is None:
-        def trace_func(head, ham):
-            return {"pos_head": head, "hamiltonian": ham}
+    summaries = SamplerSummaries(path_posterior=path_posterior, predictive=predictive, path_events=path_events,
+                                 future_score=future_score)
+    trace = SamplerTrace(ctx, trace_dir, trace_func, n_iter)
     for it in range(n_iter):
         ctx.sample_momentum(seed, it + 1, chain_offset)
         st = tr.sample(it)
         ctx.switch_partition()
-        if path_posterior is not None and it >= n_adapt:
-            path_posterior.update()
-        if predictive is not None and it >= n_adapt:
-            predictive.update(seed, it, chain_offset)
-        if path_events is not None and it >= n_adapt:
-            event_draws.append(path_events.update())
-        if future_score is not None and it >= n_adapt:
-            future_score.update(it, chain_offset)
+        summaries.update(seed, it, chain_offset, n_adapt)
         heads[it] = ctx.get_head(n_head)
-        if trace_dir is not None:
-            from .traces import TraceWriter
-            vals = {k: np.asarray(v) for k, v in trace_func(heads[it], ctx.hamiltonian()[:, 0]).items()}
-            if writer is None:
-                writer = TraceWriter(trace_dir, B, n_iter, {k: v.shape[1:] for k, v in vals.items()})
-            writer.write(it, vals)
+        trace.write(it, heads[it])
         acc = _mean_over_all_chains(st["accept_stat"].sum(), B)
         acc_hist[it], eps_hist[it] = acc, float(np.mean(tr.step_size))
         nstep_hist[it], err_hist[it] = st["n_step"].mean(), st["integrator_error"].mean()
@@ -256,28 +233,6 @@ def sample_dynamic_chmc(ctx, n_iter, step_size, seed, n_adapt=0, chain_offset=0,
                per_chain={k: v / n_main for k, v in per_chain.items()})
     if groups is not None:
         out["group_step_sizes"] = group_eps
-    if path_posterior is not None:
-        out["path_posterior"] = path_posterior.pooled()
-    if path_events is not None:
-        from .traces import summarize
-        ev = np.stack(event_draws) if event_draws else np.empty((0, B, path_events.NE))
-        out["path_events"] = ev
-        out["path_events_summary"] = summarize({k: ev[:, :, i].T for i, k in enumerate(path_events.names)}, path_events.names,
-                                               groups=groups)
-    if future_score is not None:
-        out["future_score"] = future_score.pooled()
-        out["future_log_pred"] = future_score.log_pred
-    if predictive is not None:
-        out["predictive"] = predictive.pooled()
-        if groups is not None:
-            out["predictive_groups"] = [predictive.pooled(np.flatnonzero(groups == g)) for g in range(G)]
-    if writer is not None:
-        from .traces import save_summary
-        writer.flush()
-        c1 = ctx.counters()
-        main = {k: np.asarray(v)[:, n_adapt:] for k, v in writer.arrays().items()}
-        out["summary"] = save_summary(trace_dir, main, None, time.perf_counter() - t0, float(np.mean(tr.step_size)),
-                                      {k: c1[k] - c0[k] for k in c1 if k != "_"}, groups=groups)
-        import os
-        out["trace_files"] = {k: os.path.join(trace_dir, f"trace_{k}.npy") for k in writer.arrays()}
+    summaries.fill(out, groups, G if groups is not None else None)
+    trace.finish(out, n_adapt, float(np.mean(tr.step_size)), groups)
     return out

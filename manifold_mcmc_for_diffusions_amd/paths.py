@@ -7,6 +7,8 @@ library call: path scan + moment update) and the chains are merged at the end (`
 components followed by obs_func(x)."""
 import os
 import numpy as np
+from .devbuf import DeviceBuffers
+from .distributed import process_group, all_gather_vectors, all_reduce_array
 
 
 def merge_moments(a, b):
@@ -24,22 +26,11 @@ def merge_moments(a, b):
 
 def merge_ranks(acc):
     """Under torch.distributed with more than one rank: the ranks' (n, mean, m2) merged in rank order; otherwise `acc`."""
-    try:
-        import torch
-        import torch.distributed as dist
-    except ImportError:
+    if process_group() is None:
         return acc
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return acc
-    dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
-    flat = np.concatenate(([float(acc[0])], acc[1].ravel(), acc[2].ravel()))
-    t = torch.from_numpy(flat).to(dev)
-    parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
-    dist.all_gather(parts, t)
     shape, k = acc[1].shape, acc[1].size
     out = (0, np.zeros(shape), np.zeros(shape))
-    for p in parts:
-        p = p.cpu().numpy()
+    for p in all_gather_vectors(np.concatenate(([float(acc[0])], acc[1].ravel(), acc[2].ravel()))):
         out = merge_moments(out, (int(round(p[0])), p[1:1 + k].reshape(shape), p[1 + k:].reshape(shape)))
     return out
 
@@ -62,21 +53,11 @@ def merge_moments_per_entry(a, b):
 
 def merge_ranks_per_entry(acc):
     """Under torch.distributed with more than one rank: the ranks' per-entry (n, mean, m2) merged in rank order."""
-    try:
-        import torch
-        import torch.distributed as dist
-    except ImportError:
+    if process_group() is None:
         return acc
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return acc
-    dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
-    t = torch.from_numpy(np.concatenate([acc[0].astype(np.float64), acc[1], acc[2]])).to(dev)
-    parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
-    dist.all_gather(parts, t)
     k = len(acc[0])
     out = (np.zeros(k, dtype=np.int64), np.zeros(k), np.zeros(k))
-    for p in parts:
-        p = p.cpu().numpy()
+    for p in all_gather_vectors(np.concatenate([acc[0].astype(np.float64), acc[1], acc[2]])):
         out = merge_moments_per_entry(out, (np.rint(p[:k]).astype(np.int64), p[k:2 * k], p[2 * k:]))
     return out
 
@@ -119,31 +100,30 @@ class PathEvents:
         self.path_posterior = path_posterior
         self.names = event_names(len(self.thresholds))
         self.NE = len(self.names)
-        B = ctx.B
-        self._hip = ctx.L.chmc_backend() == b"hip:gfx950"
-        if self._hip:  # torch-ROCm tensors; the library works on their pointers
-            import torch
-            dev = torch.device("cuda", ctx.device)
-            self._ev = torch.zeros((B, self.NE), dtype=torch.float64, device=dev)
-            self._x = None if path_posterior is not None else torch.zeros((B, self.NP, ctx.X), dtype=torch.float64, device=dev)
-            torch.cuda.synchronize(dev)
-        else:  # the library's "device" is host memory (the emulation build of the tests)
-            self._ev = np.zeros((B, self.NE))
-            self._x = None if path_posterior is not None else np.zeros((B, self.NP, ctx.X))
-
-    def _ptr(self, a):
-        return a.data_ptr() if self._hip else a.ctypes.data
+        f64 = dict(ev=(ctx.B, self.NE))
+        if path_posterior is None:  # a scratch path of its own
+            f64["x"] = (ctx.B, self.NP, ctx.X)
+        self._buf = DeviceBuffers(ctx, f64)
 
     def update(self, mask=None):
         """[B, NE]: the events of every chain's current path (rows of chains with mask[c] == 0 keep their last values)."""
         if self.path_posterior is not None:
             x_ptr = self.path_posterior._ptr("x")
         else:
-            self.ctx.generate_x_seq_device(self.stride, self._ptr(self._x))
-            x_ptr = self._ptr(self._x)
+            x_ptr = self._buf.ptr("x")
+            self.ctx.generate_x_seq_device(self.stride, x_ptr)
         self.ctx.path_events_device(x_ptr, self.NP, self.stride, self.channel, self.window[0], self.window[1],
-                                    self.thresholds, self._ptr(self._ev), mask=mask)
-        return self._ev.cpu().numpy() if self._hip else self._ev.copy()
+                                    self.thresholds, self._buf.ptr("ev"), mask=mask)
+        return self._buf.host("ev")
+
+    def sampler_update(self, seed, it, chain_offset):
+        return self.update()
+
+    def sampler_out(self, draws, groups, G):
+        from .traces import summarize
+        ev = np.stack(draws) if draws else np.empty((0, self.ctx.B, self.NE))
+        return dict(path_events=ev, path_events_summary=summarize({k: ev[:, :, i].T for i, k in enumerate(self.names)},
+                                                                  self.names, groups=groups))
 
 
 class PathPosterior:
@@ -152,20 +132,15 @@ class PathPosterior:
         self.NP, self.times = ctx.path_points(self.stride)
         self.XC = ctx.X + 1
         B = ctx.B
-        shapes = dict(x=(B, self.NP, ctx.X), mean=(B, self.NP, self.XC), m2=(B, self.NP, self.XC))
-        if ctx.L.chmc_backend() == b"hip:gfx950":  # torch-ROCm tensors; the library works on their pointers
-            import torch
-            dev = torch.device("cuda", ctx.device)
-            self._buf = {k: torch.zeros(s, dtype=torch.float64, device=dev) for k, s in shapes.items()}
-            self._buf["n"] = torch.zeros(B, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize(dev)
-            self._ptr = lambda k: self._buf[k].data_ptr()
-            self._host = lambda k: self._buf[k].cpu().numpy()
-        else:  # the library's "device" is host memory (the emulation build of the tests)
-            self._buf = {k: np.zeros(s) for k, s in shapes.items()}
-            self._buf["n"] = np.zeros(B, dtype=np.int64)
-            self._ptr = lambda k: self._buf[k].ctypes.data
-            self._host = lambda k: self._buf[k].copy()
+        self._buf = DeviceBuffers(ctx, dict(x=(B, self.NP, ctx.X), mean=(B, self.NP, self.XC), m2=(B, self.NP, self.XC)),
+                                  dict(n=(B,)))
+        self._ptr, self._host = self._buf.ptr, self._buf.host
+
+    def sampler_update(self, seed, it, chain_offset):
+        self.update()
+
+    def sampler_out(self, draws, groups, G):
+        return dict(path_posterior=self.pooled())
 
     def update(self, mask=None):
         """Fold the path of every chain's current state (chains with mask[c] != 0; None: all) into its moments."""
@@ -212,16 +187,7 @@ class PathPosterior:
 
 def sum_ranks(a):
     """Under torch.distributed with more than one rank: the ranks' integer arrays added up; otherwise `a`."""
-    try:
-        import torch
-        import torch.distributed as dist
-    except ImportError:
-        return a
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return a
-    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to("cuda" if dist.get_backend() == "nccl" else "cpu")
-    dist.all_reduce(t)
-    return t.cpu().numpy()
+    return a if process_group() is None else all_reduce_array(a, np.int64)
 
 
 class PredictivePosterior:
@@ -275,19 +241,17 @@ class PredictivePosterior:
                 f64["events"] = (B, self.n_rep, ne)
         elif keep_events:
             raise ValueError("keep_events needs events=")
-        if ctx.L.chmc_backend() == b"hip:gfx950":  # torch-ROCm tensors; the library works on their pointers
-            import torch
-            dev = torch.device("cuda", ctx.device)
-            self._buf = {k: torch.zeros(s, dtype=torch.float64, device=dev) for k, s in f64.items()}
-            self._buf.update({k: torch.zeros(s, dtype=torch.int64, device=dev) for k, s in i64.items()})
-            torch.cuda.synchronize(dev)
-            self._ptr = lambda k: self._buf[k].data_ptr() if k in self._buf else None
-            self._host = lambda k: self._buf[k].cpu().numpy()
-        else:  # the library's "device" is host memory (the emulation build of the tests)
-            self._buf = {k: np.zeros(s) for k, s in f64.items()}
-            self._buf.update({k: np.zeros(s, dtype=np.int64) for k, s in i64.items()})
-            self._ptr = lambda k: self._buf[k].ctypes.data if k in self._buf else None
-            self._host = lambda k: self._buf[k].copy()
+        self._buf = DeviceBuffers(ctx, f64, i64)
+        self._ptr, self._host = self._buf.ptr, self._buf.host  # (_ptr: None for an output that was not asked for)
+
+    def sampler_update(self, seed, it, chain_offset):
+        self.update(seed, it, chain_offset)
+
+    def sampler_out(self, draws, groups, G):
+        out = dict(predictive=self.pooled())
+        if groups is not None:
+            out["predictive_groups"] = [self.pooled(np.flatnonzero(groups == g)) for g in range(G)]
+        return out
 
     def update(self, seed, draw, chain_offset=0, mask=None):
         """n_rep replicates of every chain's current state (chains with mask[c] != 0; None: all), keyed by (seed, draw,
@@ -462,6 +426,12 @@ class FutureScore:
         self._draws.append(lp)
         return lp
 
+    def sampler_update(self, seed, it, chain_offset):
+        self.update(it, chain_offset)
+
+    def sampler_out(self, draws, groups, G):
+        return dict(future_score=self.pooled(), future_log_pred=self.log_pred)
+
     @property
     def log_pred(self):
         """[n_main, B]: the per-draw, per-chain scores in the order of the updates."""
@@ -491,3 +461,36 @@ class FutureScore:
         np.savez(path, y_future=self.y_future, n_cand=self.n_cand, seed=self.seed, log_pred=self.log_pred,
                  pooled_log_pred=pool["log_pred"], chain_log_pred=pool["chain_log_pred"], mcse=pool["mcse"])
         return path
+
+
+SUMMARY_KEYWORDS = ("path_posterior", "predictive", "path_events", "future_score")
+
+
+class SamplerSummaries:
+    """The samplers' keywords for summaries of the post-warm-up states, each an object of the sampler's `ctx` that sees
+    every state after the partition switch:
+    path_posterior: a `PathPosterior`; the latent path of every such state is folded into its running moments (`update()`),
+    and out["path_posterior"] is its `pooled()` result.
+    predictive: a `PredictivePosterior`; every such state gets `predictive.update(seed, it, chain_offset)`,
+    out["predictive"] is its `pooled()` result and, with `groups`, out["predictive_groups"] the list of the G groups'
+    pooled results.
+    path_events: a `PathEvents`; every such state gets `update()`, out["path_events"] is [n_main, B, NE] and
+    out["path_events_summary"] `traces.summarize` of it under the object's `names` (per group with `groups`).
+    future_score: a `FutureScore`; every such state gets `future_score.update(it, chain_offset)`; out["future_score"] is
+    its `pooled()` result and out["future_log_pred"] the [n_main, B] scores.  Scoring reads the state and draws from
+    keyed streams of its own: the chain is bitwise what it is without it.
+    The summaries run in the order of SUMMARY_KEYWORDS: a PathEvents(path_posterior=pp) reads the scratch path of pp's
+    update of the same iteration.  A summary takes part through `sampler_update(seed, it, chain_offset)`, whose return
+    values the helper keeps per run, and `sampler_out(kept, groups, G)`, its entries of the sampler's `out`."""
+
+    def __init__(self, **summaries):
+        self.items = [(summaries[k], []) for k in SUMMARY_KEYWORDS if summaries.get(k) is not None]
+
+    def update(self, seed, it, chain_offset, n_adapt):
+        if it >= n_adapt:
+            for s, kept in self.items:
+                kept.append(s.sampler_update(seed, it, chain_offset))
+
+    def fill(self, out, groups=None, G=None):
+        for s, kept in self.items:
+            out.update(s.sampler_out(kept, groups, G))

@@ -10,22 +10,16 @@ lies on the manifold of the chain's data (chmc_set_state_solve_noise_device; con
 rung, the main phase at the last one."""
 import time
 import numpy as np
+from .devbuf import DeviceBuffers
+from .paths import SUMMARY_KEYWORDS
+
+# keywords of sample_static_chmc that belong to one context (or one directory): only the rung they were made for gets them
+ONE_CONTEXT_KEYWORDS = SUMMARY_KEYWORDS + ("trace_dir",)
+METRIC_KEYWORDS = ("metric_adapter", "metric_window", "metric_skip")  # (the first warm-up alone adapts the metric)
 
 
-class _DeviceRows:
-    """[rows, cols] doubles where the library's kernels can reach them: a torch-ROCm tensor, or host memory under the
-    emulation build of the tests."""
-
-    def __init__(self, ctx, rows, cols):
-        if ctx.L.chmc_backend() == b"hip:gfx950":
-            import torch
-            dev = torch.device("cuda", ctx.device)
-            self._t = torch.zeros((rows, cols), dtype=torch.float64, device=dev)
-            torch.cuda.synchronize(dev)
-            self.ptr = self._t.data_ptr()
-        else:
-            self._t = np.zeros((rows, cols))
-            self.ptr = self._t.ctypes.data
+def without(kw, names):
+    return {k: v for k, v in kw.items() if k not in names}
 
 
 def _src_row_length(src):
@@ -39,11 +33,11 @@ def transfer_state(src, dst, seed, draw=0, chain_offset=0, partition=None):
     Returns dict(moved [B] = max_t |n_t new - n_t old|, max_constr = max |constraint| of dst afterwards)."""
     if (src.B, src.T, src.U, src.V, src.V0, src.noisy) != (dst.B, dst.T, dst.U, dst.V, dst.V0, dst.noisy):
         raise ValueError("transfer_state needs two contexts of the same model, T, noise kind and number of chains")
-    q_src = _DeviceRows(src, src.B, _src_row_length(src))
-    q_dst = _DeviceRows(dst, dst.B, dst.Q)
-    src.get_state_device(q_src.ptr, None)
-    dst.resample_q_device(q_src.ptr, src.S, seed, q_dst.ptr, draw=draw, chain_offset=chain_offset)
-    moved = dst.set_state_solve_noise(q_dst.ptr, src.partition if partition is None else partition)
+    q_src = DeviceBuffers(src, dict(q=(src.B, _src_row_length(src))))
+    q_dst = DeviceBuffers(dst, dict(q=(dst.B, dst.Q)))
+    src.get_state_device(q_src.ptr("q"), None)
+    dst.resample_q_device(q_src.ptr("q"), src.S, seed, q_dst.ptr("q"), draw=draw, chain_offset=chain_offset)
+    moved = dst.set_state_solve_noise(q_dst.ptr("q"), src.partition if partition is None else partition)
     return dict(moved=moved, max_constr=float(np.abs(dst.constr()).max()))
 
 
@@ -67,13 +61,12 @@ def coarse_to_fine_static_chmc(coarse_ctx, fine_ctxs, n_warm_coarse, n_warm_fine
     ladder = list(fine_ctxs) if isinstance(fine_ctxs, (list, tuple)) else [fine_ctxs]
     if not ladder:
         raise ValueError("fine_ctxs must hold at least one context")
-    fine_kw = {k: v for k, v in sampler_kw.items() if k not in ("metric_adapter", "metric_window", "metric_skip")}
+    fine_kw = without(sampler_kw, METRIC_KEYWORDS)
     chain_offset = int(sampler_kw.get("chain_offset", 0))
     rungs = []
     t0 = time.perf_counter()
     out = sample_static_chmc(coarse_ctx, n_warm_coarse, n_step, step_size, seed, n_adapt=n_warm_coarse,
-                             **{k: v for k, v in sampler_kw.items()
-                                if k not in ("path_posterior", "predictive", "path_events", "trace_dir")})
+                             **without(sampler_kw, ONE_CONTEXT_KEYWORDS))
     eps = out["final_step_size"]
     rungs.append(dict(S=coarse_ctx.S, seconds=time.perf_counter() - t0, first_step_size=step_size, final_step_size=eps,
                       mean_accept_stat=float(np.mean(out["accept_stat"])) if n_warm_coarse else float("nan"), moved=None,
@@ -84,8 +77,7 @@ def coarse_to_fine_static_chmc(coarse_ctx, fine_ctxs, n_warm_coarse, n_warm_fine
         t0 = time.perf_counter()
         transfer_metric(prev, ctx)
         tr = transfer_state(prev, ctx, seed, draw=i, chain_offset=chain_offset)
-        kw = fine_kw if last else {k: v for k, v in fine_kw.items()
-                                   if k not in ("path_posterior", "predictive", "path_events", "trace_dir")}
+        kw = fine_kw if last else without(fine_kw, ONE_CONTEXT_KEYWORDS)
         out = sample_static_chmc(ctx, n_warm_fine + (n_main if last else 0), n_step, eps, seed + i, n_adapt=n_warm_fine, **kw)
         eps = out["final_step_size"]
         acc = out["accept_stat"][n_warm_fine:] if last and n_main else out["accept_stat"]

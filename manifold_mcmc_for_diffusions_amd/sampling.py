@@ -6,8 +6,11 @@ The reference drives the same integrator with Mici's dynamic multinomial (NUTS-s
 (scripts/utils.py:292-306); the batched counterpart of that transition is dynamic.py.  This static variant targets the
 same posterior (it is a valid Markov kernel for it), costs no per-leaf bookkeeping and is what bench-like workloads
 use: momentum -> L constrained leapfrog steps -> accept / reject -> SwitchPartitionTransition."""
-import os
 import numpy as np
+from .context import DEFAULT_SOLVER
+from .distributed import sum_over_ranks
+from .paths import SamplerSummaries
+from .traces import SamplerTrace
 
 
 class DualAveragingStepSize:
@@ -68,15 +71,8 @@ class PerChainDualAveragingStepSize:
 def _mean_over_all_chains(local_sum, local_count):
     """Mean of a per-chain statistic over the chains of every rank (one tiny all-reduce; SURVEY.md 8f #3: warm-up
     adaptation combines the chains of all GPUs so that every rank integrates with the same step size)."""
-    try:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            from . import distributed as D
-            tot = D.sum_over_ranks([float(local_sum), float(local_count)])
-            return float(tot[0]) / float(tot[1])
-    except ImportError:
-        pass
-    return float(local_sum) / float(local_count)
+    tot = sum_over_ranks([float(local_sum), float(local_count)])
+    return float(tot[0]) / float(tot[1])
 
 
 def _group_sums_over_all_chains(values, groups, n_groups):
@@ -87,13 +83,7 @@ def _group_sums_over_all_chains(values, groups, n_groups):
     for g in np.unique(groups):
         sel = groups == g
         local[g], local[n_groups + g] = values[sel].sum(), sel.sum()
-    try:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            from . import distributed as D
-            local = np.asarray(D.sum_over_ranks(local), dtype=np.float64)
-    except ImportError:
-        pass
+    local = sum_over_ranks(local)
     return local[:n_groups], local[n_groups:]
 
 
@@ -118,10 +108,9 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     transition (forward / backward in time), failed trajectories are rejected.
 
     trace_dir: write memory-mapped traces (`trace_<var>.npy`, [chain, draw, ...]) and `summary.json` there;
-    trace_func(head [B, n_head], hamiltonian [B]) -> {name: [B, ...]} chooses the traced variables (default: the
-    head components as `pos_head` and `hamiltonian`).  Under torch.distributed the accept statistic that drives the
-    step-size adaptation is averaged over the chains of all ranks; with `total_chains` (the number of chains of the
-    whole job) the per-chain directions and accept draws are taken from one stream indexed by the global chain
+    trace_func chooses the traced variables (traces.SamplerTrace).  Under torch.distributed the accept statistic that
+    drives the step-size adaptation is averaged over the chains of all ranks; with `total_chains` (the number of chains
+    of the whole job) the per-chain directions and accept draws are taken from one stream indexed by the global chain
     number, so that any sharding of the chains reproduces the single-process run.
     jitter_length: every chain draws its number of leapfrog steps uniformly from 1..n_step per transition (a mixture
     of reversible kernels, so still a valid sampler); chains in regions where the retraction often fails then still
@@ -132,8 +121,6 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     out, like the first window of a staged warm-up) and `metric_window` of the warm-up; the block metric it produces
     (per-chain statistics combined over all chains and ranks) is installed with `ctx.set_metric` there, and the
     remaining warm-up transitions re-tune the step size for the new metric.
-    path_posterior: a `paths.PathPosterior` of `ctx`; the latent path of every post-warm-up state (after the partition
-    switch) is folded into its running moments, and out["path_posterior"] is its `pooled()` result.
     groups [B], n_groups: chains that sample different posteriors in one context (per-chain observations,
     ChmcContext.set_observations): groups[c] is the GLOBAL id of the data set chain c belongs to, n_groups their number over
     the whole job (default: max + 1 of this rank's).  Every group then has its own dual-averaging state, driven by the mean
@@ -144,16 +131,8 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     metric_per_group: unless this is set.  The adapter then produces one M_0 per group from the statistics of that group's
     chains over all ranks (`finalize_groups`), in the same window; they are installed with `ctx.set_metric(M, groups=...)`,
     every group's dual averaging restarts from that group's current step size, and out["metric_M_0"] is [G, U, U].
-    predictive: a `paths.PredictivePosterior` of `ctx`; after warm-up every state (after the partition switch) gets
-    `predictive.update(seed, it, chain_offset)`, out["predictive"] is its `pooled()` result and, with `groups`,
-    out["predictive_groups"] the list of the G groups' pooled results.
-    path_events: a `paths.PathEvents` of `ctx`; after warm-up every state (after the partition switch) gets `update()`,
-    out["path_events"] is [n_main, B, NE] and out["path_events_summary"] `traces.summarize` of it under the object's `names`
-    (per group with `groups`).
-    future_score: a `paths.FutureScore` of `ctx`; after warm-up every state (after the partition switch) gets
-    `future_score.update(it, chain_offset)`; out["future_score"] is its `pooled()` result and
-    out["future_log_pred"] the [n_main, B] scores.  Scoring reads the state and draws from keyed streams of its own:
-    the chain is bitwise what it is without it."""
+    path_posterior, predictive, path_events, future_score: summaries of the post-warm-up states and their entries of
+    `out` (paths.SamplerSummaries)."""
     if metric_per_group and (groups is None or metric_adapter is None):
         raise ValueError("metric_per_group needs groups and a metric_adapter")
     group_metrics = None
@@ -161,8 +140,7 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
         groups, G = check_groups(groups, n_groups, ctx.B)
         if metric_adapter is not None and G > 1 and not metric_per_group:
             raise ValueError("the block metric is one M_0 per context: no metric_adapter with more than one group")
-    solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
-                  reverse_check_tol=2e-8) if solver is None else solver
+    solver = dict(DEFAULT_SOLVER) if solver is None else solver
     rng = np.random.default_rng(seed) if rng is None else rng
     adapter = DualAveragingStepSize(step_size) if n_adapt > 0 else None
     B = ctx.B
@@ -187,18 +165,12 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
     # not converge (status 1), diverged (2), non-reversible step (3)] -- the diagnosis of a chain that does not move
     outcome = np.zeros((B, 5), dtype=np.int64)
     heads = np.empty((n_iter, B, n_head))
-    event_draws = []
     acc_hist, eps_hist, fail_hist = np.empty(n_iter), np.empty(n_iter), np.empty(n_iter)
     if groups is not None:
         eps_hist, group_acc_hist = np.empty((n_iter, G)), np.empty((n_iter, G))
-    if trace_func is None:
-        def trace_func(head, ham):
-            return {"pos_head": head, "hamiltonian": ham}
-    writer, t_start, c_start = None, None, None
-    if trace_dir is not None:
-        import time
-        from .traces import TraceWriter
-        t_start, c_start = time.perf_counter(), ctx.counters()
+    summaries = SamplerSummaries(path_posterior=path_posterior, predictive=predictive, path_events=path_events,
+                                 future_score=future_score)
+    trace = SamplerTrace(ctx, trace_dir, trace_func, n_iter)
     for it in range(n_iter):
         ctx.sample_momentum(seed, it + 1, chain_offset)
         h0 = ctx.hamiltonian()[:, 0]
@@ -226,20 +198,9 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
             outcome[np.arange(B), col] += 1
         ctx.restore((~accept).astype(np.int32))
         ctx.switch_partition()
-        if path_posterior is not None and it >= n_adapt:
-            path_posterior.update()
-        if predictive is not None and it >= n_adapt:
-            predictive.update(seed, it, chain_offset)
-        if path_events is not None and it >= n_adapt:
-            event_draws.append(path_events.update())
-        if future_score is not None and it >= n_adapt:
-            future_score.update(it, chain_offset)
+        summaries.update(seed, it, chain_offset, n_adapt)
         heads[it] = ctx.get_head(n_head)
-        if trace_dir is not None:
-            vals = {k: np.asarray(v) for k, v in trace_func(heads[it], ctx.hamiltonian()[:, 0]).items()}
-            if writer is None:
-                writer = TraceWriter(trace_dir, B, n_iter, {k: v.shape[1:] for k, v in vals.items()})
-            writer.write(it, vals)
+        trace.write(it, heads[it])
         if n_metric and n_skip <= it < n_metric:
             if metric_state is None:
                 metric_state = metric_adapter.initialize(np.zeros((B, ctx.Q)))
@@ -276,32 +237,10 @@ def sample_static_chmc(ctx, n_iter, n_step, step_size, seed, chain_offset=0, n_a
                chain_outcomes=outcome)
     if groups is not None:
         out["group_accept_stat"] = group_acc_hist
-    if path_posterior is not None:
-        out["path_posterior"] = path_posterior.pooled()
-    if path_events is not None:
-        from .traces import summarize
-        ev = np.stack(event_draws) if event_draws else np.empty((0, B, path_events.NE))
-        out["path_events"] = ev
-        out["path_events_summary"] = summarize({k: ev[:, :, i].T for i, k in enumerate(path_events.names)}, path_events.names,
-                                               groups=groups)
-    if future_score is not None:
-        out["future_score"] = future_score.pooled()
-        out["future_log_pred"] = future_score.log_pred
-    if predictive is not None:
-        out["predictive"] = predictive.pooled()
-        if groups is not None:
-            out["predictive_groups"] = [predictive.pooled(np.flatnonzero(groups == g)) for g in range(G)]
+    summaries.fill(out, groups, G if groups is not None else None)
     if n_metric and metric_per_group:
         out["metric_M_0"] = group_metrics
     elif n_metric:
         out["metric_M_0"] = None if ctx.M_0 is None else ctx.M_0.copy()
-    if writer is not None:
-        import time
-        from .traces import save_summary
-        writer.flush()
-        c_end = ctx.counters()
-        main = {k: np.asarray(v)[:, n_adapt:] for k, v in writer.arrays().items()}  # summary over the post-warm-up draws
-        out["summary"] = save_summary(trace_dir, main, None, time.perf_counter() - t_start, step_size,
-                                      {k: c_end[k] - c_start[k] for k in c_end if k != "_"}, groups=groups)
-        out["trace_files"] = {k: os.path.join(trace_dir, f"trace_{k}.npy") for k in writer.arrays()}
+    trace.finish(out, n_adapt, step_size, groups)
     return out

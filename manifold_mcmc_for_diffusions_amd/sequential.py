@@ -11,24 +11,15 @@ observations given the chain's draw.  `sequential_static_chmc` is the driver on 
 re-tune briefly and sample."""
 import time
 import numpy as np
-from .resolution import _DeviceRows, transfer_metric
-from .paths import log_mean_exp
+from .devbuf import DeviceBuffers
+from .resolution import METRIC_KEYWORDS, transfer_metric, without
+from .paths import SUMMARY_KEYWORDS, log_mean_exp
 
 
 def _same_but_T(src, dst):
     keys = ("B", "U", "V", "V0", "X", "S", "noisy", "variable_sigma", "_model", "_obs_interval", "_num_obs_per_subseq",
             "_use_gaussian_splitting", "device")
     return all(getattr(src, k) == getattr(dst, k) for k in keys)
-
-
-def _sync(ctx):
-    if ctx.L.chmc_backend() == b"hip:gfx950":
-        import torch
-        torch.cuda.synchronize(torch.device("cuda", ctx.device))
-
-
-def _host(rows):
-    return rows._t.cpu().numpy() if hasattr(rows._t, "cpu") else rows._t.copy()
 
 
 def extend_state(src, dst, seed, draw=0, chain_offset=0, n_cand=64, partition=None):
@@ -50,24 +41,23 @@ def extend_state(src, dst, seed, draw=0, chain_offset=0, n_cand=64, partition=No
         raise ValueError("extend_state: the first observations and the noise levels of dst must be those of src")
     T, H, B = src.T, dst.T - src.T, src.B
     head, nv = src.U + src.V0 + T * src.S * src.V, H * src.S * src.V
-    q_src = _DeviceRows(src, B, src.Q)
-    tail = _DeviceRows(src, B, nv + H)
-    logw = _DeviceRows(src, B, int(n_cand))
-    q_dst = _DeviceRows(dst, B, dst.Q)
-    src.get_state_device(q_src.ptr, None)
-    log_pred, picked = src.score_future_device(seed, draw, chain_offset, y_dst[:, T:], n_cand, logw_dev_ptr=logw.ptr,
-                                               tail_dev_ptr=tail.ptr)
+    sbuf = DeviceBuffers(src, dict(q=(B, src.Q), tail=(B, nv + H), logw=(B, int(n_cand))))
+    dbuf = DeviceBuffers(dst, dict(q=(B, dst.Q)))
+    src.get_state_device(sbuf.ptr("q"), None)
+    log_pred, picked = src.score_future_device(seed, draw, chain_offset, y_dst[:, T:], n_cand,
+                                               logw_dev_ptr=sbuf.ptr("logw"), tail_dev_ptr=sbuf.ptr("tail"))
     if (picked < 0).any():
         raise ValueError(f"extend_state: no forecast candidate of chains {np.flatnonzero(picked < 0).tolist()} has a finite "
                          "weight for the new observations")
     # [u | v_0 | v_seq | tail v] and [n | tail n]: column copies between device buffers
-    q_dst._t[:, :head] = q_src._t[:, :head]
-    q_dst._t[:, head:head + nv] = tail._t[:, :nv]
-    q_dst._t[:, head + nv:head + nv + T] = q_src._t[:, head:]
-    q_dst._t[:, head + nv + T:] = tail._t[:, nv:]
-    _sync(dst)
-    moved = dst.set_state_solve_noise(q_dst.ptr, src.partition if partition is None else partition)
-    lw = _host(logw)
+    q_src, tail, q_dst = sbuf.array("q"), sbuf.array("tail"), dbuf.array("q")
+    q_dst[:, :head] = q_src[:, :head]
+    q_dst[:, head:head + nv] = tail[:, :nv]
+    q_dst[:, head + nv:head + nv + T] = q_src[:, head:]
+    q_dst[:, head + nv + T:] = tail[:, nv:]
+    dbuf.sync()
+    moved = dst.set_state_solve_noise(dbuf.ptr("q"), src.partition if partition is None else partition)
+    lw = sbuf.host("logw")
     w = np.exp(lw - lw.max(1, keepdims=True))
     return dict(log_pred=log_pred, picked=picked, ess_cand=w.sum(1) ** 2 / (w * w).sum(1), moved=moved,
                 max_constr=float(np.abs(dst.constr()).max()))
@@ -90,12 +80,10 @@ def sequential_static_chmc(ctx, y_batches, n_warm_first, n_warm_next, n_main, n_
     log-mean-exp), chain_log_pred [B], ess_cand [B], moved [B], max_constr, first_head [B, n_head]: the stage's first
     state); log_pred, chain_log_pred, ess_cand, moved are None for stage 0."""
     from .sampling import sample_static_chmc
-    # (summaries that belong to ctx itself -- path_posterior, predictive, path_events, future_score -- see stage 0 only)
+    # (summaries that belong to ctx itself, paths.SUMMARY_KEYWORDS, see stage 0 only)
     sampler_kw = dict(sampler_kw)
     trace_dir = sampler_kw.pop("trace_dir", None)
-    later_kw = {k: v for k, v in sampler_kw.items()
-                if k not in ("metric_adapter", "metric_window", "metric_skip", "path_posterior", "predictive", "path_events",
-                             "future_score")}
+    later_kw = without(sampler_kw, METRIC_KEYWORDS + SUMMARY_KEYWORDS)
     chain_offset = int(sampler_kw.get("chain_offset", 0))
     n_head = int(sampler_kw.get("n_head", 6))
     stages = []

@@ -8,6 +8,7 @@ memory-mapped `.npy` per variable with the ArviZ axis order [chain, draw, ...], 
 reference records (`total_sampling_time`, `final_integrator_step_size`, `total_<op>_calls`)."""
 import json
 import os
+import time
 import numpy as np
 
 
@@ -104,3 +105,35 @@ def save_summary(directory, traces, var_names, sampling_time, step_size, call_co
     with open(os.path.join(directory, "summary.json"), "w") as f:
         json.dump(s, f, ensure_ascii=False, indent=2)
     return s
+
+
+class SamplerTrace:
+    """The trace output of one sampler run (trace_dir=None: none): `write` after every transition, `finish` at the end.
+    trace_func(head [B, n_head], hamiltonian [B]) -> {name: [B, ...]} chooses the traced variables (default: the head
+    components as `pos_head` and `hamiltonian`); the files are created at the first draw, when the shapes are known.  The
+    run's time and call counts are taken from the construction on."""
+
+    def __init__(self, ctx, trace_dir, trace_func, n_iter):
+        self.ctx, self.directory, self.n_iter, self.writer = ctx, trace_dir, n_iter, None
+        self.func = (lambda head, ham: {"pos_head": head, "hamiltonian": ham}) if trace_func is None else trace_func
+        if trace_dir is not None:
+            self.t_start, self.c_start = time.perf_counter(), ctx.counters()
+
+    def write(self, it, head):
+        if self.directory is None:
+            return
+        vals = {k: np.asarray(v) for k, v in self.func(head, self.ctx.hamiltonian()[:, 0]).items()}
+        if self.writer is None:
+            self.writer = TraceWriter(self.directory, self.ctx.B, self.n_iter, {k: v.shape[1:] for k, v in vals.items()})
+        self.writer.write(it, vals)
+
+    def finish(self, out, n_adapt, step_size, groups=None):
+        """out["summary"]: summary.json over the post-warm-up draws with the run totals; out["trace_files"]."""
+        if self.writer is None:
+            return
+        self.writer.flush()
+        c_end = self.ctx.counters()
+        main = {k: np.asarray(v)[:, n_adapt:] for k, v in self.writer.arrays().items()}
+        out["summary"] = save_summary(self.directory, main, None, time.perf_counter() - self.t_start, step_size,
+                                      {k: c_end[k] - self.c_start[k] for k in c_end if k != "_"}, groups=groups)
+        out["trace_files"] = {k: os.path.join(self.directory, f"trace_{k}.npy") for k in self.writer.arrays()}

@@ -2,7 +2,7 @@
 multi-GPU driver): data simulation, contexts, initial states, momentum refresh, static-trajectory transitions."""
 import numpy as np
 from . import example_models as em
-from .context import ChmcContext
+from .context import ChmcContext, DEFAULT_SOLVER
 from .init import fhn_initial_states, fhn_initial_states_device
 
 SEED = 20200710  # scripts/utils.py:75-77
@@ -44,8 +44,7 @@ class FhnWorkload:
                                                   sigma is not None, seed=seed, chain_offset=chain_offset,
                                                   total_chains=total_chains)
             self.ctx.set_state(q, None, xo, 0)
-        self.solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
-                           reverse_check_tol=2e-8)  # scripts/utils.py:131-166
+        self.solver = dict(DEFAULT_SOLVER)
         self._torch_gen = None
 
     # momentum refresh: IndependentMomentumTransition -> system.sample_momentum (sde/mici_extensions.py:1256-1259)
@@ -113,8 +112,7 @@ class SirWorkload(FhnWorkload):
             _, _, self.init_tries = init.find_initial_states_by_gradient_descent_noisy_system(
                 self.ctx, rng, adam_step_size=adam_step_size, max_iters=5000, log=log)
         self.rngs = [rng]
-        self.solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
-                           reverse_check_tol=2e-8)
+        self.solver = dict(DEFAULT_SOLVER)
         self._torch_gen = None
 
 
@@ -166,8 +164,7 @@ class GridWorkload:
                 raise ValueError("linear-interpolation initial states are the FitzHugh-Nagumo scripts'")
             self.rngs = fhn_initial_states_device(self.ctx, em.fhn, self.y[:, :, None], seed=seed, chain_offset=self.chain_offset,
                                                   total_chains=self.total_chains)
-        self.solver = dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10, max_iters=50,
-                           reverse_check_tol=2e-8)  # scripts/utils.py:131-166
+        self.solver = dict(DEFAULT_SOLVER)
 
     @classmethod
     def fhn_noise_grid(cls, sigmas, data_seeds, chains_per_cell, num_obs=100, obs_interval=0.2, num_steps_per_obs_data=10000,

@@ -58,7 +58,7 @@ def one_run(n_warm, n_main, run):
     from manifold_mcmc_for_diffusions_amd.workload import FhnWorkload
     from manifold_mcmc_for_diffusions_amd.sampling import sample_static_chmc
     from manifold_mcmc_for_diffusions_amd.resolution import transfer_state, coarse_to_fine_static_chmc
-    from manifold_mcmc_for_diffusions_amd.resolution import _DeviceRows
+    from manifold_mcmc_for_diffusions_amd.devbuf import DeviceBuffers
     lines = [f"== run {run}: carrying {B} FitzHugh-Nagumo chains (configs[1]) between resolutions, "
              f"{torch.cuda.get_device_name(0)} on {socket.gethostname()}"]
     # ---- (a)
@@ -69,18 +69,18 @@ def one_run(n_warm, n_main, run):
         src = FhnWorkload(B, num_steps_per_obs=S_src, device_init=True)
         dst = src.ctx.sibling(400)
         t_all = median_ms(lambda: transfer_state(src.ctx, dst, 7))
-        q_src = _DeviceRows(src.ctx, B, src.ctx.Q)
-        q_dst = _DeviceRows(dst, B, dst.Q)
-        src.ctx.get_state_device(q_src.ptr, None)
-        t_call = median_ms(lambda: dst.resample_q_device(q_src.ptr, src.ctx.S, 7, q_dst.ptr))
-        k_ms, k_n = kernel_ms(L, lambda: [dst.resample_q_device(q_src.ptr, src.ctx.S, 7, q_dst.ptr, draw=d) for d in range(REPS)])
+        buf_src, buf_dst = DeviceBuffers(src.ctx, dict(q=(B, src.ctx.Q))), DeviceBuffers(dst, dict(q=(B, dst.Q)))
+        q_src, q_dst = buf_src.ptr("q"), buf_dst.ptr("q")
+        src.ctx.get_state_device(q_src, None)
+        t_call = median_ms(lambda: dst.resample_q_device(q_src, src.ctx.S, 7, q_dst))
+        k_ms, k_n = kernel_ms(L, lambda: [dst.resample_q_device(q_src, src.ctx.S, 7, q_dst, draw=d) for d in range(REPS)])
         k_ms = k_ms / k_n if k_n and k_ms > 0 else float("nan")
         stored = 8.0 * B * dst.T * dst.S * dst.V
         lines.append(f"(a) transfer_state {S_src} -> 400: {ms(t_all)}; chmc_resample_q_device alone {ms(t_call)}; its kernel by HIP "
                      f"events {k_ms * 1e3:.1f} us per launch ({k_n} launches) = {stored / (k_ms * 1e-3) / 1e12:.2f} TB/s of stores "
                      f"({stored / 1e6:.0f} MB) = {100 * stored / (k_ms * 1e-3) / PEAK:.1f} % of the 8 TB/s peak")
         dst.close(), src.ctx.close()
-        del q_src, q_dst
+        del buf_src, buf_dst
     for _ in range(2):
         fine.refresh_momentum()
         fine.ctx.leapfrog_steps(EPS0 / 4, N_STEP, **fine.solver)
