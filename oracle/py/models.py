@@ -2,8 +2,10 @@
 
 Closed-form one-step maps of the two example diffusions, written with torch fp64
 ops so that `torch.func` can differentiate them the way JAX differentiates the
-SymNum-generated `forward_func` in the reference.  PARITY UNPINNED: the reference
-ships no tests / golden vectors for this path.
+SymNum-generated `forward_func` in the reference.  The reference ships no tests /
+golden vectors for this path; tests/test_reference_runs.py holds
+these maps against the reference's own programs, executed by oracle/ref_programs.py
+(fixtures: tests/golden/reference_runs).
 
 Follows (behaviour, not text):
   sde/example_models/fhn.py:10-65   (FitzHugh-Nagumo, strong-order-1.5 step)
