@@ -16,7 +16,15 @@ the notebook's linear interpolation; candidates are screened in the same way.
 
 usage: fhn_notebook_posterior.py [chains] [iterations] [warm-up] [steps per trajectory] [output dir] [static|dynamic]
                                  [--init linear-interpolation|gradient-descent] [--path-posterior STRIDE] [--forecast H]
-                                 [--spikes THETA]
+                                 [--spikes THETA] [--coarse-warmup M]
+--coarse-warmup M: the warm-up runs at S / M steps per observation (M divides the 25): the initial states are found and
+screened there, four fifths of the warm-up transitions run there, the chains are carried to S = 25 by the projection of
+resolution.transfer_state (noiseless observations: chmc_set_state_project_device) and the step size is re-tuned over the
+last fifth (resolution.coarse_to_fine_static_chmc / coarse_to_fine_dynamic_chmc).  The check against the table is unchanged.
+Measured (profiles/resolution_noiseless_timing.txt): at the notebook's S = 25 the only such M is 5, and 5 steps of 0.1 per
+interval are too few for this model -- the scheme is unstable at the posterior's time-scale separation, the refined path
+misses the data by the size of the signal, most chains diverge in the projection and transfer_state raises, naming them.
+The option is for a finer notebook_data()["S"]; at 25 the plain run is the one to use.
 --spikes THETA: the posterior of the number of spikes of the observed component, counted as up-crossings of THETA along the
 latent path of every post-warm-up state (paths.PathEvents on the device, traced like the parameters).
 --forecast H: posterior predictive forecast of the observed component over H observation intervals beyond the last
@@ -64,13 +72,18 @@ def print_path_posterior(pp, pool, path, y, per_obs, verbose=True):
 
 def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=20200710, verbose=True,
         transition="static", init="linear-interpolation", path_posterior=None, forecast=None,
-        spikes=None):
+        spikes=None, coarse_warmup=None):
     """forecast: a number of observation intervals beyond the last observation (see the usage text).
     path_posterior: a stride (a divisor of the steps per observation); the posterior moments of the latent path x(t) at every
     stride-th step are accumulated over the main phase and written to `path_posterior.npz` next to the traces."""
     if init not in ("linear-interpolation", "gradient-descent"):
         raise ValueError("init must be linear-interpolation or gradient-descent")
     d = notebook_data()
+    S_init = d["S"]  # the resolution the initial states are found at and the warm-up starts at
+    if coarse_warmup:
+        if coarse_warmup < 2 or d["S"] % coarse_warmup:
+            raise ValueError(f"--coarse-warmup must be a divisor of {d['S']} above 1")
+        S_init = d["S"] // coarse_warmup
     m = em.fhn_nb
     rng = np.random.default_rng(seed)
 
@@ -80,7 +93,7 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
                                 0.5 * rng.standard_normal((n, d["T"], 1))], -1))
 
     def context(n):
-        return ChmcContext("fhn_nb", d["obs_interval"], d["S"], 5, d["y"], sigma=None, use_gaussian_splitting=True,
+        return ChmcContext("fhn_nb", d["obs_interval"], S_init, 5, d["y"], sigma=None, use_gaussian_splitting=True,
                            num_chains=n)
 
     # Prior draws with a small time-scale separation eps make the explicit step unstable at this step size (the
@@ -114,6 +127,11 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
         ctx.set_state(q_init[keep], None, x_obs_init[keep], 0)
     else:
         ctx.init_by_linear_interpolation(u[keep], v_0[keep], x_obs_init[keep])
+    coarse = None
+    if coarse_warmup:  # the summaries, the traces and the main phase belong to the fine context
+        coarse, ctx = ctx, ctx.sibling(d["S"])
+        n_warm_fine = max(2, n_warm // 5)
+        n_warm_coarse, n_main = n_warm - n_warm_fine, n_iter - n_warm
 
     def trace_func(head, ham):  # cell 41
         z = m.generate_z(head[:, :4])
@@ -134,8 +152,13 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
         extra["path_events"] = PathEvents(ctx, ctx.X, [float(spikes)], stride=int(path_posterior or 1), path_posterior=pp)
     t0 = time.time()
     if transition == "dynamic":
-        from manifold_mcmc_for_diffusions_amd.dynamic import sample_dynamic_chmc
-        res = sample_dynamic_chmc(ctx, n_iter, 0.1, seed=seed, n_adapt=n_warm, trace_dir=tmp, trace_func=trace_func,
+        from manifold_mcmc_for_diffusions_amd.dynamic import sample_dynamic_chmc as sample
+        if coarse is not None:
+            from manifold_mcmc_for_diffusions_amd.resolution import coarse_to_fine_dynamic_chmc
+
+            def sample(_, n, eps, seed, n_adapt, **kw):
+                return coarse_to_fine_dynamic_chmc(coarse, ctx, n_warm_coarse, n_warm_fine, n_main, eps, seed, **kw)
+        res = sample(ctx, n_iter, 0.1, seed=seed, n_adapt=n_warm, trace_dir=tmp, trace_func=trace_func,
                                   path_posterior=pp, **extra,
                                   solver=dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10,
                                               max_iters=50, reverse_check_tol=2e-8),
@@ -144,13 +167,29 @@ def run(num_chains=64, n_iter=700, n_warm=200, n_step=24, out_dir=None, seed=202
                                       f"integrator errors {st['integrator_error'].mean():.2f}", flush=True)) if verbose else None)
         res["fail_rate"] = res["integrator_error"]
     else:
-      res = sample_static_chmc(ctx, n_iter, n_step, 0.1, seed=seed, n_adapt=n_warm, trace_dir=tmp, trace_func=trace_func,
+      sample = sample_static_chmc
+      if coarse is not None:
+          from manifold_mcmc_for_diffusions_amd.resolution import coarse_to_fine_static_chmc
+
+          def sample(_, n, n_step, eps, seed, n_adapt, **kw):
+              return coarse_to_fine_static_chmc(coarse, ctx, n_warm_coarse, n_warm_fine, n_main, n_step, eps, seed, **kw)
+      res = sample(ctx, n_iter, n_step, 0.1, seed=seed, n_adapt=n_warm, trace_dir=tmp, trace_func=trace_func,
                              jitter_length=True, path_posterior=pp, **extra,
                              solver=dict(newton=True, constraint_tol=1e-9, position_tol=1e-8, divergence_tol=1e10,
                                          max_iters=50, reverse_check_tol=2e-8),  # cell 33
                              callback=(lambda it, h, a, e: (it % 50 == 0) and print(
                                  f"  iter {it:4d} accept {a:.2f} step {e:.3f}", flush=True)) if verbose else None)
     el = time.time() - t0
+    if coarse is not None:  # the last rung's record: its own warm-up transitions, then the main phase
+        if verbose:
+            for r in res["rungs"]:
+                carried = "" if r["moved"] is None else (
+                    f"; carried over with defect <= {r['defect'].max():.1e}, {r['proj_iters'].min()} to {r['proj_iters'].max()} "
+                    f"Newton iterations, tries <= {r['tries'].max()}, moved <= {r['moved'].max():.1e}, max |c| {r['max_constr']:.1e}")
+                print(f"  rung S = {r['S']}: {r['seconds']:.1f} s, step size {float(np.mean(r['first_step_size'])):.3f} -> "
+                      f"{float(np.mean(r['final_step_size'])):.3f}, accept {r['mean_accept_stat']:.2f}{carried}")
+        coarse.close()
+        n_warm, n_iter = n_warm_fine, n_warm_fine + n_main
     if pp is not None:
         print_path_posterior(pp, res["path_posterior"], pp.save(tmp), d["y"], d["S"] // pp.stride, verbose)
     if spikes is not None and verbose:
@@ -247,10 +286,15 @@ if __name__ == "__main__":
         i = a.index("--forecast")
         forecast = int(a[i + 1])
         del a[i:i + 2]
+    coarse_warmup = None
+    if "--coarse-warmup" in a:
+        i = a.index("--coarse-warmup")
+        coarse_warmup = int(a[i + 1])
+        del a[i:i + 2]
     spikes = None
     if "--spikes" in a:
         i = a.index("--spikes")
         spikes = float(a[i + 1])
         del a[i:i + 2]
-    run(*(int(x) for x in a[:4]), init=init, path_posterior=stride, forecast=forecast, spikes=spikes, out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
+    run(*(int(x) for x in a[:4]), init=init, path_posterior=stride, forecast=forecast, spikes=spikes, coarse_warmup=coarse_warmup, out_dir=a[4] if len(a) > 4 and a[4] != "-" else None,
         transition=a[5] if len(a) > 5 else "static")

@@ -139,8 +139,35 @@ int chmc_resample_q_device(chmc_ctx* ctx, const void* q_src_dev, int S_src, unsi
  *   q', x_obs' chmc_get_state returns.  Every observation row and every state row of the constraint is zero to rounding.
  *   moved[c] = max_t |n_t new - n_t given| (host [B]; may be NULL).
  * A context WITHOUT observation noise (noisy == 0) is not supported and returns an error: there x_obs_seq must satisfy
- * obs_func(x) = y and is part of the constraint's definition; moving it is a separate design, out of scope here. */
+ * obs_func(x) = y and is part of the constraint's definition, so closing the defect is a projection, not a substitution:
+ * chmc_set_state_project_device below. */
 int chmc_set_state_solve_noise_device(chmc_ctx* ctx, const void* q_dev, int partition, double* moved);
+/* The same placement WITHOUT observation noise (noisy == 0; a noisy context returns an error that names
+ * chmc_set_state_solve_noise_device).  For every chain c with mask[c] != 0 (host [B]; NULL = all chains), from row c of
+ * q_dev [B][Q] (device; never written):
+ *   1. x_obs_seq = the path of the row at the observation times, scanned from q itself as above.
+ *   2. defect[c] = max_t |y_t - obs_func(x_t)| (y_t: the chain's own after chmc_set_observations); then every x_t moves along
+ *      obs_grad until the observation holds: x <- x + g (y - obs(x)) / (g . g), at most 8 rounds, done when
+ *      |y - obs(x)| <= 8 eps max(1, |y|) -- one round for the linear obs_func of both FitzHugh-Nagumo models, Newton on exp
+ *      for SIR.  A chain with an observation that does not get there or is not finite (SIR with y <= 0) gets status 2 and
+ *      the solver is not run for it.
+ *   3. The state (row, mom = 0, the pinned x_obs_seq, partition 0) is evaluated and the row is projected from it
+ *      (state_prev = state, dt = 1) by the solver of chmc_project with the given settings: the sequence of
+ *      chmc_gd_project_device.  On convergence the projected point becomes the chain's position.
+ *   4. x_obs_seq of the converged chains is scanned again from the projected path, and the caches are evaluated in the given
+ *      partition (for partition 1, the evaluation chmc_switch_partition ends with).  mom = 0.
+ * The result is bitwise the state of chmc_set_state(q', NULL, x_obs', partition) for the q', x_obs' chmc_get_state returns.
+ * Outputs (host [B], each may be NULL): status = the codes of chmc_project (CHMC_INACTIVE for chains outside the mask),
+ * iters, defect, moved[c] = max_j |q placed - q given| (0 unless converged).
+ * A chain that did not converge keeps the pinned, unprojected state: off the manifold and flagged by its status; the caller
+ * retries it (another row under `mask`) or refuses to go on.  Chains outside the mask keep position, momentum and x_obs_seq;
+ * the context as a whole ends in `partition`, and where the call passes through another partition than the one they were
+ * evaluated in, their caches are evaluated again from those.  A context that holds no state yet takes all chains only.
+ * A chain's result depends on its own row and data alone: any sharding gives the same bits.
+ * Errors: NULL q_dev, partition out of range, max_iters < 0, a noisy context, a partial mask without a state. */
+int chmc_set_state_project_device(chmc_ctx* ctx, const void* q_dev, int partition, const int* mask, int newton,
+                                  double constraint_tol, double position_tol, double divergence_tol, int max_iters,
+                                  int* status, int* iters, double* defect, double* moved);
 /* find_initial_state_by_linear_interpolation (sde/mici_extensions.py:1479-1547) for all chains at once, on the
  * device: given u [B][U], v_0 [B][V0] and full states at the observation times x_obs_seq_init [B][T][X]
  * (generate_x_obs_seq_init of the scripts), solves per time step for the noise increments that make the discretised
@@ -362,8 +389,8 @@ int chmc_predict_device(chmc_ctx* ctx, unsigned long long seed, unsigned long lo
  * section 4.13) and, under CHMC_FUTURE_WAVE=1 where the compact rows are allocated, a wavefront per (chain, group of 64
  * candidates) with a lane per candidate (k_future_score).  Neither reduces over candidates and both use the same
  * accumulator, so the two forms give the same bits.
- * Errors: no state set; noisy == 0 (not supported: without observation noise the weights are degenerate and placing the
- * state is a projection, out of scope as in chmc_set_state_solve_noise_device); horizon < 1; n_cand outside [1, 65536];
+ * Errors: no state set; noisy == 0 (not supported: without observation noise the weights are degenerate, and the state
+ * would be placed by the projection of chmc_set_state_project_device, not through n); horizon < 1; n_cand outside [1, 65536];
  * draw >= 2^45; chain_offset < 0; a NULL y_future or log_pred; a non-finite y_future. */
 #define CHMC_FUTURE_DRAW (1ULL << 59)
 int chmc_score_future_device(chmc_ctx* ctx, unsigned long long seed, unsigned long long draw, int chain_offset, int horizon,

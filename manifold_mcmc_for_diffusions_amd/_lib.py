@@ -42,6 +42,8 @@ SYMBOLS = [
     ("chmc_resample_q_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_int, ip,
                                          C.c_void_p]),
     ("chmc_set_state_solve_noise_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, dp]),
+    ("chmc_set_state_project_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, ip, C.c_int, C.c_double, C.c_double,
+                                                C.c_double, C.c_int, ip, ip, dp, dp]),
     ("chmc_init_linear_interpolation", C.c_int, [C.c_void_p, dp, dp, dp, C.c_int]),
     ("chmc_set_metric", C.c_int, [C.c_void_p, dp]),
     ("chmc_set_metrics", C.c_int, [C.c_void_p, dp]),

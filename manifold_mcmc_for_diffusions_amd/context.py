@@ -111,7 +111,8 @@ class ChmcContext:
         check(self.L.chmc_get_observations(self.h, ptr(y), ptr(sg)), "chmc_get_observations")
         return y, sg
 
-    # ---- carrying chains between time resolutions (chmc_resample_q_device, chmc_set_state_solve_noise_device; resolution.py)
+    # ---- carrying chains between time resolutions (chmc_resample_q_device, chmc_set_state_solve_noise_device,
+    # chmc_set_state_project_device; resolution.py)
     def sibling(self, num_steps_per_obs):
         """A new context with `num_steps_per_obs` steps per observation interval and everything else as here: model, T, R,
         obs_interval, noise kind, splitting, B and device, the per-chain observations and the metric (per chain or shared)."""
@@ -146,6 +147,22 @@ class ChmcContext:
               "chmc_set_state_solve_noise_device")
         self.partition = int(partition)
         return moved
+
+    def set_state_project(self, q_dev_ptr, partition=0, mask=None, **solver):
+        """The same placement without observation noise: the rows of q [B, Q] (device) of the chains with mask[c] != 0 (None:
+        all) are projected onto the manifold of the chains' data from x_obs_seq of their own path, pinned to the data
+        (chmc_set_state_project_device, include/chmc.h; noiseless contexts only).  solver: the keywords of DEFAULT_SOLVER.
+        Returns dict(status, iters, defect, moved), each [B]; a chain with status != 0 holds the pinned, unprojected state."""
+        s = dict(DEFAULT_SOLVER, **solver)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        status, iters = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+        defect, moved = np.empty(self.B), np.empty(self.B)
+        check(self.L.chmc_set_state_project_device(self.h, C.c_void_p(q_dev_ptr), int(partition), iptr(m), int(s["newton"]),
+                                                   float(s["constraint_tol"]), float(s["position_tol"]),
+                                                   float(s["divergence_tol"]), int(s["max_iters"]), iptr(status), iptr(iters),
+                                                   ptr(defect), ptr(moved)), "chmc_set_state_project_device")
+        self.partition = int(partition)
+        return dict(status=status, iters=iters, defect=defect, moved=moved)
 
     def close(self):
         if getattr(self, "h", None):

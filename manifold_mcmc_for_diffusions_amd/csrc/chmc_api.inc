@@ -43,6 +43,7 @@ struct chmc_ctx : ChainView {  // sy, sl, w and the per-chain arrays handed to k
   int* d_order_ident = nullptr;          // identity work order [B] for that one-block-per-chain layout
   unsigned long long* d_fill_keys = nullptr;  // chmc_fill_normal*: [B][2] (stream, draw) of the listed rows, then [B] ints: the rows
   double* d_gd = nullptr;  // chmc_gd_objective_device: [B][T][X] c, [B][T][Z + 2] interval partials, [B][2] chain sums (whole-batch launches only)
+  double* d_place = nullptr;  // chmc_set_state_project_device: [B][T][X] scanned x_obs_seq, [B][T] dobs, [B][T] pok, [B] defect, [B] pinfail, [B] moved
   bool mom_tangent = false;  // every chain's momentum is known to lie in the cotangent space of its current point
   bool snap_tangent = false; // ... at the time of chmc_snapshot
   bool have_state = false;   // a chain state has been set (chmc_set_metric then refreshes its cached factors)
@@ -1830,7 +1831,7 @@ extern "C" int chmc_set_state_solve_noise_device(chmc_ctx* ctx, const void* q_de
   const Sys& sy = ctx->sy;
   if (!sy.noisy)
     return fail(fn + ": a context without observation noise is not supported (x_obs_seq is part of the constraint there; "
-                     "placing a refined state in it is out of scope)");
+                     "chmc_set_state_project_device places a refined state in it)");
   const size_t n = sizeof(double) * (size_t)sy.B * sy.Q;
   dev_zero(ctx->sl.cur, sizeof(int) * sy.B);
   d2d(ctx->sl.q[0], q_dev, n);
@@ -1979,9 +1980,29 @@ extern "C" int chmc_project(chmc_ctx* ctx, int newton, const double* q, const do
   CHMC_LEAVE("chmc_project")
 }
 
-// The projection step of find_initial_state_by_gradient_descent (:1654-1669) on the caller's device rows: the masked chains'
-// states become (q_dev row, zero momentum, xo_dev row, partition 0), the position is projected from that state with dt = 1
-// by the solver of chmc_project, and a converged point replaces both the row and the state.
+// The projection step of find_initial_state_by_gradient_descent (:1654-1669) for the chains of ctx->d_act, whose current
+// slots hold (row of q_dev, zero momentum) with their x_obs_seq in the context, partition 0: the state is evaluated, the
+// position is projected from it with dt = 1 by the solver of chmc_project, and a converged point replaces the state's
+// position (and the row of q_out, where given).  Afterwards d_act holds the chains that converged; their caches are the
+// caller's to re-evaluate.  Shared by chmc_gd_project_device and chmc_set_state_project_device.
+static void project_rows(chmc_ctx* ctx, const double* q_dev, double* q_out, const Solver& so, int* st, int* iters, double* err) {
+  const Sys& sy = ctx->sy;
+  begin_all(ctx, nullptr, ctx->d_act);  // the state caches of the masked chains only
+  state_eval(ctx, 0);
+  const std::vector<double> ones(sy.B, 1.0);
+  h2d(ctx->w.err, ones.data(), sizeof(double) * sy.B);  // staging for dt
+  ctx->last_dt.clear();                                 // the step-size cache of chmc_leapfrog_step is now stale
+  begin_all(ctx, ctx->w.err, ctx->d_act);
+  launch(KCopyToOther{sy, ctx->sl, q_dev}, (long)sy.B * sy.Q);
+  run_projection(ctx, so, 0, 0);
+  d2h(st, ctx->w.nstat, sizeof(int) * sy.B);
+  if (iters) d2h(iters, ctx->w.iters, sizeof(int) * sy.B);
+  if (err) d2h(err, ctx->w.err, sizeof(double) * sy.B);
+  launch(KGdConverged{ctx->w, ctx->d_act}, sy.B);
+  launch(KGdAdopt{sy, ctx->sl, ctx->d_act, q_out}, (long)sy.B * sy.Q, 8);
+}
+// chmc_gd_project_device (include/chmc.h): the masked chains' states become (q_dev row, zero momentum, xo_dev row, partition
+// 0), project_rows, and the caches of the chains that moved onto the manifold
 extern "C" int chmc_gd_project_device(chmc_ctx* ctx, const int* mask, void* q_dev, const void* xo_dev, int newton, double ctol,
                                       double ptol, double dtol, int max_iters, int* status, int* iters, double* err) {
   CHMC_ENTER("chmc_gd_project_device")
@@ -1994,20 +2015,8 @@ extern "C" int chmc_gd_project_device(chmc_ctx* ctx, const int* mask, void* q_de
   ctx->last_active_null = true;
   ctx->last_active.clear();
   launch(KGdSetRows{sy, ctx->sl, (const double*)q_dev, (const double*)xo_dev, ctx->d_xobs, ctx->d_act}, (long)sy.B * sy.Q, 8);
-  begin_all(ctx, nullptr, ctx->d_act);  // the state caches of the masked chains only
-  state_eval(ctx, 0);
-  const std::vector<double> ones(sy.B, 1.0);
-  h2d(ctx->w.err, ones.data(), sizeof(double) * sy.B);  // staging for dt
-  ctx->last_dt.clear();                                 // the step-size cache of chmc_leapfrog_step is now stale
-  begin_all(ctx, ctx->w.err, ctx->d_act);
-  launch(KCopyToOther{sy, ctx->sl, (const double*)q_dev}, (long)sy.B * sy.Q);
-  run_projection(ctx, Solver{newton, ctol, ptol, dtol, max_iters}, 0, 0);
   std::vector<int> st(sy.B);
-  d2h(st.data(), ctx->w.nstat, sizeof(int) * sy.B);
-  if (iters) d2h(iters, ctx->w.iters, sizeof(int) * sy.B);
-  if (err) d2h(err, ctx->w.err, sizeof(double) * sy.B);
-  launch(KGdConverged{ctx->w, ctx->d_act}, sy.B);
-  launch(KGdAdopt{sy, ctx->sl, ctx->d_act, (double*)q_dev}, (long)sy.B * sy.Q, 8);
+  project_rows(ctx, (const double*)q_dev, (double*)q_dev, Solver{newton, ctol, ptol, dtol, max_iters}, st.data(), iters, err);
   begin_all(ctx, nullptr, ctx->d_act);  // ... and of the chains that moved onto the manifold
   state_eval(ctx, 0);
   if (dev_sync()) return fail(std::string("chmc_gd_project_device: ") + g_err);
@@ -2017,6 +2026,73 @@ extern "C" int chmc_gd_project_device(chmc_ctx* ctx, const int* mask, void* q_de
       if (iters) iters[c] = 0;
       if (err) err[c] = 0.0;
     }
+  }
+  return 0;
+}
+// A position placed on the manifold of the chain's data WITHOUT observation noise (include/chmc.h): x_obs_seq scanned from
+// the row itself (KXobs, as chmc_set_state_solve_noise_device), its observed coordinate pinned to the data (pin_obs), the
+// projection of chmc_gd_project_device from that state (project_rows), x_obs_seq again from the projected path, and the
+// caches in the partition asked for.
+extern "C" int chmc_set_state_project_device(chmc_ctx* ctx, const void* q_dev, int partition, const int* mask, int newton,
+                                             double ctol, double ptol, double dtol, int max_iters, int* status, int* iters,
+                                             double* defect, double* moved) {
+  CHMC_ENTER("chmc_set_state_project_device")
+  const std::string fn = "chmc_set_state_project_device";
+  if (!q_dev) return fail(fn + ": null argument");
+  if (partition < 0 || partition >= ctx->num_partition) return fail(fn + ": partition out of range");
+  if (max_iters < 0) return fail(fn + ": max_iters < 0");
+  const Sys& sy = ctx->sy;
+  if (sy.noisy)
+    return fail(fn + ": a context with observation noise places a position exactly and without a solver: "
+                     "use chmc_set_state_solve_noise_device");
+  const int B = sy.B;
+  std::vector<int> m(B, 1);
+  bool all = true;
+  if (mask)
+    for (int c = 0; c < B; ++c) m[c] = mask[c] != 0, all = all && m[c];
+  if (!all && !ctx->have_state) return fail(fn + ": a context that holds no state yet takes all chains (mask NULL or all non-zero)");
+  if ((long long)B * sy.T * sy.X > 0x7fffffffLL) return fail(fn + ": too many observations for one call");
+  const size_t nxo = (size_t)B * sy.T * sy.X, bt = (size_t)B * sy.T;
+  if (!ctx->d_place) ctx->d_place = alloc<double>(ctx, nxo + 2 * bt + 3 * (size_t)B);
+  double *xs = ctx->d_place, *scr = xs + nxo, *d_defect = scr + 2 * bt, *d_moved = d_defect + 2 * (size_t)B;
+  // a partial call leaves the other chains' positions, momenta and x_obs_seq alone; their caches are evaluated again below
+  // whenever the call passes through another partition than the one they were evaluated in
+  const bool whole = all || ctx->part != 0 || partition != 0;
+  const bool tangent = all || (ctx->mom_tangent && ctx->part == partition);
+  select_partition(ctx, 0);
+  if (all) dev_zero(ctx->sl.cur, sizeof(int) * B);
+  h2d(ctx->d_act, m.data(), sizeof(int) * B);
+  ctx->last_active_null = true;
+  ctx->last_active.clear();
+  ctx->have_tree = ctx->pair_ready = false;
+  launch(KGdSetRows{sy, ctx->sl, (const double*)q_dev, nullptr, ctx->d_xobs, ctx->d_act}, (long)B * sy.Q, 8);
+  dispatch(ctx, [&](auto inst) {
+    using M = typename decltype(inst)::M;
+    launch(KXobs<M>{sy, ctx->sl, xs}, B);  // x_obs_seq of the given positions
+    pin_obs<M>(ctx, ctx->d_act, xs, scr);
+  });
+  std::vector<double> hd(2 * (size_t)B), hm(B, 0.0);
+  d2h(hd.data(), d_defect, sizeof(double) * 2 * (size_t)B);  // defect, pinfail
+  std::vector<int> st(B), it(B);
+  project_rows(ctx, (const double*)q_dev, nullptr, Solver{newton, ctol, ptol, dtol, max_iters}, st.data(), it.data(), nullptr);
+  dev_zero(d_moved, sizeof(double) * B);
+  launch_colmax(KPlacedMoved{sy, ctx->sl, ctx->d_act, (const double*)q_dev, reinterpret_cast<unsigned long long*>(d_moved)}, sy.Q, B, 8);
+  d2h(hm.data(), d_moved, sizeof(double) * B);
+  dispatch(ctx, [&](auto inst) { launch(KXobs<typename decltype(inst)::M>{sy, ctx->sl, xs}, B); });  // ... of the projected ones
+  launch(KCopyXobsRows{sy.T * sy.X, ctx->d_act, xs, ctx->d_xobs}, (long)nxo, 8);
+  h2d(ctx->d_act, m.data(), sizeof(int) * B);
+  select_partition(ctx, partition);
+  begin_all(ctx, nullptr, whole ? nullptr : ctx->d_act);
+  state_eval(ctx, 0);
+  ctx->have_state = true;
+  ctx->mom_tangent = tangent;  // zero momentum in the call's chains
+  if (dev_sync()) return fail(fn + ": " + g_err);
+  for (int c = 0; c < B; ++c) {
+    const bool pinfail = hd[B + c] != 0.0;
+    if (status) status[c] = !m[c] ? CHMC_INACTIVE : pinfail ? 2 : st[c];
+    if (iters) iters[c] = m[c] && !pinfail ? it[c] : 0;
+    if (defect) defect[c] = m[c] ? hd[c] : 0.0;
+    if (moved) moved[c] = m[c] ? hm[c] : 0.0;
   }
   return 0;
 }

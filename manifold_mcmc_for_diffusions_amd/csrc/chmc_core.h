@@ -3674,11 +3674,12 @@ struct KGdSetRows {
     pick(sl.q, s)[tid] = qin[tid];
     pick(sl.p, s)[tid] = 0.0;
     const int nx = sy.T * sy.X;
+    if (!xo) return;  // chmc_set_state_project_device: x_obs_seq comes from the row's own path (KPinObs)
     for (int i = col; i < nx; i += sy.Q) xobs[(size_t)c * nx + i] = xo[(size_t)c * nx + i];
   }
 };
 // ... and, for the chains whose projection converged, the projected point (the other slot) replaces both the state's
-// position and the caller's row
+// position and the caller's row (qout null: the state alone, chmc_set_state_project_device)
 struct KGdConverged {
   Work w;
   int* act;  // in: the caller's mask; out: masked and converged
@@ -3695,7 +3696,7 @@ struct KGdAdopt {
     const int s = sl.cur[c];
     const double v = pick(sl.q, s ^ 1)[tid];
     pick(sl.q, s)[tid] = v;
-    qout[tid] = v;
+    if (qout) qout[tid] = v;
   }
 };
 
@@ -3846,6 +3847,91 @@ struct KSolveNoise {
       n[t] = nn;
     }
     moved[c] = mv;
+  }
+};
+
+// chmc_set_state_project_device: without observation noise x_obs_seq itself has to satisfy obs_func(x_t) = y_t, and the path
+// of a refined position misses that by the discretisation defect.  One work item per (chain, observation): dobs = |y_t -
+// obs_func(x_t)| of the scanned path xs (KXobs), then x_t moves along obs_grad until the observation holds,
+//   x <- x + g (y - obs(x)) / (g . g),   at most 8 rounds, done when |y - obs(x)| <= 8 eps max(1, |y|)
+// (one round for a linear obs_func, Newton on exp for SIR), and goes into the context's x_obs_seq.  Every product-plus-sum is
+// an explicit fma, as in resample_*: no contraction choice differs between the library and the host emulation.
+template <class M>
+struct KPinObs {
+  Sys sy;
+  const int* act;    // [B] the call's chains
+  const double* xs;  // [B][T][X] the rows' paths at the observation times
+  double* xobs;      // [B][T][X] of the context
+  double* dobs;      // [B][T]
+  double* pok;       // [B][T] 1: the observation holds at the pinned x_t, 0: not converged or not finite
+  CHMC_HD void operator()(int tid) const {
+    constexpr int X = M::X;
+    const int c = tid / sy.T, t = tid - c * sy.T;
+    if (!act[c]) return;
+    const double yv = y_of(sy, c)[t];
+    double x[X], g[X];
+    for (int a = 0; a < X; ++a) x[a] = xs[(size_t)tid * X + a];
+    double r = yv - M::obs(x);
+    dobs[tid] = fabs(r);
+    const double ay = fabs(yv), tol = 8.0 * 2.220446049250313e-16 * (ay > 1.0 ? ay : 1.0);
+    for (int round = 0; round < 8 && !(fabs(r) <= tol); ++round) {
+      M::obs_grad(x, g);
+      double gg = 0.0;
+      for (int a = 0; a < X; ++a) gg = fma(g[a], g[a], gg);
+      const double s = r / gg;
+      for (int a = 0; a < X; ++a) x[a] = fma(g[a], s, x[a]);
+      r = yv - M::obs(x);
+    }
+    pok[tid] = fabs(r) <= tol ? 1.0 : 0.0;
+    for (int a = 0; a < X; ++a) xobs[(size_t)tid * X + a] = x[a];
+  }
+};
+// ... per chain: defect[c] = max_t dobs (a NaN stays one), and a chain with an observation that could not be pinned leaves the
+// call's mask (the solver is not run for it) with pinfail[c] = 1
+struct KPinChain {
+  int T;
+  int* act;
+  const double* dobs;
+  const double* pok;
+  double* defect;   // [B]
+  double* pinfail;  // [B]
+  CHMC_HD void operator()(int c) const {
+    defect[c] = 0.0, pinfail[c] = 0.0;
+    if (!act[c]) return;
+    double mx = 0.0;
+    bool ok = true;
+    for (int t = 0; t < T; ++t) {
+      const double d = dobs[(size_t)c * T + t];
+      mx = d > mx || d != d ? d : mx;
+      ok = ok && pok[(size_t)c * T + t] != 0.0;
+    }
+    defect[c] = mx;
+    if (!ok) pinfail[c] = 1.0, act[c] = 0;
+  }
+};
+// ... moved[c] = max_j |q placed - q given| of the chains whose projection converged; column-max kernel (zeroed targets)
+struct KPlacedMoved {
+  static constexpr bool kFinish = false;
+  Sys sy;
+  Slots sl;
+  const int* act;
+  const double* qin;
+  unsigned long long* moved;  // [B] bit patterns
+  CHMC_HD bool active(int c) const { return act[c] != 0; }
+  CHMC_HD unsigned long long* red(int c) const { return &moved[c]; }
+  CHMC_FI CHMC_HD unsigned long long operator()(int c, int col) const {
+    const size_t i = (size_t)c * sy.Q + col;
+    return absbits(pick(sl.q, sl.cur[c])[i] - qin[i]);
+  }
+};
+// ... and x_obs_seq of those chains from the projected path
+struct KCopyXobsRows {
+  int n;  // T X
+  const int* act;
+  const double* src;
+  double* dst;
+  CHMC_HD void operator()(int tid) const {
+    if (act[tid / n]) dst[tid] = src[tid];
   }
 };
 

@@ -109,6 +109,16 @@ static void resample_seq(chmc_ctx* c, const ResampleArgs& a) {
   (void)c;
   launch(KResample<M>{a}, (long)a.B * a.T * a.Sc, 8);
 }
+// chmc_set_state_project_device: the observed coordinate of the scanned x_obs_seq `xs` pinned to the data, a work item per
+// (chain, observation), then the chains' defects and the mask without the chains that could not be pinned.  Once per rung
+// and a handful of flops per work item: the functor form in both builds.  `scr`: [B][T] dobs, [B][T] pok, [B] defect, [B] pinfail
+template <class M>
+static void pin_obs(chmc_ctx* c, int* act, const double* xs, double* scr) {
+  const Sys& sy = c->sy;
+  const size_t bt = (size_t)sy.B * sy.T;
+  launch(KPinObs<M>{sy, act, xs, c->d_xobs, scr, scr + bt}, (long)bt, 8);
+  launch(KPinChain{sy.T, act, scr, scr + bt, scr + 2 * bt, scr + 2 * bt + sy.B}, sy.B);
+}
 
 #ifdef CHMC_WAVE_KERNELS
 constexpr bool kWaveKernels = true;  // PlanInput::wave_kernels of every context of this build

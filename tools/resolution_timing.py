@@ -1,5 +1,6 @@
 """Cost and effect of carrying chains between time resolutions on one MI355X.
 usage: python tools/resolution_timing.py [warm-up transitions] [main transitions] [output file]
+       python tools/resolution_timing.py --noiseless [warm-up transitions] [main transitions] [output file]
 
 FitzHugh-Nagumo configs[1] (256 chains, T = 100, R = 5, sigma = 0.1, 16-step transitions), two runs in ONE process; the
 record is appended per run and the second one is the figure to quote (the first carries the one-off costs of the process).
@@ -10,7 +11,13 @@ record is appended per run and the second one is the figure to quote (the first 
       50 -> 100 -> 400 with the same total number of warm-up transitions: wall times, final step sizes, the main phase's
       accept statistic, moved;
   (c) posterior means and sds of the u components from the routes' main phases, with R-hat over the pooled chains of the
-      plain and each coarse route."""
+      plain and each coarse route.
+--noiseless: the same question at configs[2] (no observation noise, 256 chains), where the carried state is PROJECTED
+(chmc_set_state_project_device), one run, appended to profiles/resolution_noiseless_timing.txt:
+  (a) one transfer_state 50 -> 400 and 200 -> 400, host clock around the call (it ends in a synchronise), the second of two
+      runs; the Newton iterations per chain, defect, moved and tries;
+  (b) the warm-up (default 150 transitions) plain at S = 400 against four fifths of it at S = 50 and one fifth at S = 400:
+      wall times, final step sizes and the main phase's accept statistic, both routes in this one session."""
 import ctypes as C
 import os
 import socket
@@ -143,7 +150,78 @@ def one_run(n_warm, n_main, run):
     return lines
 
 
+def noiseless_run(n_warm, n_main):
+    import torch
+    from manifold_mcmc_for_diffusions_amd.workload import FhnWorkload
+    from manifold_mcmc_for_diffusions_amd.sampling import sample_static_chmc
+    from manifold_mcmc_for_diffusions_amd.resolution import transfer_state, coarse_to_fine_static_chmc
+    lines = [f"== carrying {B} noiseless FitzHugh-Nagumo chains (configs[2]) between resolutions, "
+             f"{torch.cuda.get_device_name(0)} on {socket.gethostname()}"]
+    for S_src in (50, 200):
+        src = FhnWorkload(B, num_steps_per_obs=S_src, sigma=None)
+        dst = src.ctx.sibling(400)
+        took = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            tr = transfer_state(src.ctx, dst, 7)
+            took.append((time.perf_counter() - t0) * 1e3)
+        it, df = tr["iters"], tr["defect"]
+        lines.append(f"(a) transfer_state {S_src} -> 400: {took[1]:.1f} ms (first call {took[0]:.1f} ms); Newton iterations per chain "
+                     f"min {it.min()} mean {it.mean():.2f} max {it.max()}, chains per count {np.bincount(it).tolist()}; defect min "
+                     f"{df.min():.1e} median {np.median(df):.1e} max {df.max():.1e}; moved max {tr['moved'].max():.1e}; tries max "
+                     f"{tr['tries'].max()}; max |constraint| afterwards {tr['max_constr']:.1e}")
+        dst.close(), src.ctx.close()
+    n_fine = max(2, n_warm // 5)
+    routes = {}
+    t0 = time.perf_counter()
+    plain = FhnWorkload(B, num_steps_per_obs=400, sigma=None)
+    t_setup = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    res = sample_static_chmc(plain.ctx, n_warm, N_STEP, EPS0, seed=plain.seed, n_adapt=n_warm)
+    t_warm = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    main = sample_static_chmc(plain.ctx, n_main, N_STEP, res["final_step_size"], seed=plain.seed + 100)
+    routes["plain 400"] = dict(warm_s=t_warm, main_s=time.perf_counter() - t0, eps=[res["final_step_size"]], setup_s=t_setup,
+                               acc=float(main["accept_stat"].mean()), fail=float(main["fail_rate"].mean()), extra="")
+    plain.ctx.close()
+    t0 = time.perf_counter()
+    coarse = FhnWorkload(B, num_steps_per_obs=50, sigma=None)
+    fine = coarse.ctx.sibling(400)
+    t_setup = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    out = coarse_to_fine_static_chmc(coarse.ctx, fine, n_warm - n_fine, n_fine, 0, N_STEP, EPS0, seed=coarse.seed)
+    t_warm = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    main = sample_static_chmc(fine, n_main, N_STEP, out["final_step_size"], seed=coarse.seed + 100)
+    r1 = out["rungs"][1]
+    routes["50 -> 400"] = dict(
+        warm_s=t_warm, main_s=time.perf_counter() - t0, eps=[r["final_step_size"] for r in out["rungs"]], setup_s=t_setup,
+        acc=float(main["accept_stat"].mean()), fail=float(main["fail_rate"].mean()),
+        extra=f"; transitions per rung {[n_warm - n_fine, n_fine]}, seconds per rung {[round(r['seconds'], 2) for r in out['rungs']]}; "
+              f"carried over with {r1['proj_iters'].min()} to {r1['proj_iters'].max()} Newton iterations, defect max "
+              f"{r1['defect'].max():.1e}, moved max {r1['moved'].max():.1e}, tries max {r1['tries'].max()}")
+    fine.close(), coarse.ctx.close()
+    p = routes["plain 400"]
+    lines.append(f"(b) warm-up of {n_warm} transitions, then {n_main} main transitions at S = 400 ({N_STEP} steps each):")
+    for name, r in routes.items():
+        lines.append(f"    {name:10s} warm-up {r['warm_s']:.2f} s = {r['warm_s'] / p['warm_s']:.3f} x plain (set-up {r['setup_s']:.2f} s "
+                     f"apart); final step sizes {[round(float(np.mean(e)), 4) for e in r['eps']]}; main phase {r['main_s']:.2f} s, "
+                     f"accept statistic {r['acc']:.3f}, failed trajectories {r['fail']:.3f}{r['extra']}")
+    return lines
+
+
 def main():
+    if "--noiseless" in sys.argv:
+        sys.argv.remove("--noiseless")
+        n_warm = int(sys.argv[1]) if len(sys.argv) > 1 else 150
+        n_main = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+        out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "resolution_noiseless_timing.txt")
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        lines = noiseless_run(n_warm, n_main)
+        print("\n".join(lines), flush=True)
+        with open(out_path, "a") as f:
+            f.write("\n".join(lines) + "\n\n")
+        return
     n_warm = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     n_main = int(sys.argv[2]) if len(sys.argv) > 2 else 20
     out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "resolution_timing.txt")
